@@ -24,6 +24,13 @@ line carries "parity_sample": one output crop checked against the oracle
 outside the timed region (on N > 1 across the cut between rank 0 and rank 1),
 and "build": the library's source hash (of3d_build_info).
 
+A plain run (--gpus 1 --steps K --warmup W) does only what the headline needs: set-up, W
+warmup steps, the K timed steps, --dump-outputs DIR if given (the last timed step's outputs
+as DIR/<name>.npy, see dump_outputs), and the result line ("roofline", "cpu_baseline" and
+"parity_sample" are null in it).  Everything else described here — the per-stage profile
+and roofline, the parity sample, cpu_baseline, single_window / single_frame, and at N > 1
+"replicas", the other axis's split and compute / exchange alone — runs only with --full.
+
 Roofline: the dominant kernel's average duration from HIP events recorded on
 the launch stream over the timed region (of3d_plan_set_timing ring), with its
 algorithmic bytes and fp64 VALU op count; HBM traffic
@@ -124,6 +131,39 @@ def synthetic_slab(nt, nz, ny, nx, z0, z1, seed, device, out=None, zchunk=32, ro
     return out
 
 
+DUMP_BUDGET = 60 * 1000 * 1000  # payload bytes of one --dump-outputs (64 MB with room for the .npy headers)
+DUMP_SEED = 20260206
+
+
+def dump_outputs(outdir, named, rank=0, world=1):
+    """--dump-outputs: the arrays the timed path left on the device in its last timed step, as
+    outdir/<name>.npy (<name>_rank<r>.npy at N > 1) in the precision they were computed in
+    (float32 / float64).  Arrays of more than DUMP_BUDGET bytes in all are sampled: the same
+    sorted flat voxel indices from every array, drawn from a generator seeded by DUMP_SEED and
+    fixed by the arrays' length alone, so two builds dump the same voxels.  Returns the
+    description the result line carries."""
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    n = int(named[0][1].numel())
+    assert all(int(t.numel()) == n for _, t in named)
+    per_voxel = sum(t.element_size() for _, t in named)
+    k = n if n * per_voxel <= DUMP_BUDGET else DUMP_BUDGET // per_voxel
+    idx = None
+    if k < n:
+        host_idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=k))
+        idx = torch.from_numpy(host_idx).to(named[0][1].device)
+    files = []
+    for name, t in named:
+        a = (t if idx is None else t.reshape(-1)[idx]).cpu().numpy()  # whole arrays keep their shape
+        assert a.dtype in (np.float32, np.float64)
+        files.append((name if world == 1 else f"{name}_rank{rank}") + ".npy")
+        np.save(os.path.join(outdir, files[-1]), a)
+    return {"files": files, "values_per_array": k, "of": n,
+            "sample": None if idx is None else f"sorted flat indices numpy.random.default_rng({DUMP_SEED})"
+                                               f".integers(0, {n}, size={k})"}
+
+
 def stage_model_2d(nt_win, rd, rs, rt, rw, plane):
     """2D (calc_flow2D, calc_flow.py:18-173) per-launch algorithmic bytes / ops of each stage:
     grad_xy = K0 + the y and x passes (dt: y(G) x(G); dy: y(D) x(S); dx: y(S) x(D)), products +
@@ -162,7 +202,8 @@ def run_2d(args, world, rank, dev):
     d_vx = torch.empty(nout * plane, dtype=torch.float64, device=dev)
     d_vy = torch.empty_like(d_vx)
     d_rel = torch.empty_like(d_vx)
-    plan = _lib.Plan(2, nout, ny, nx, make_taps(s, t, w), device=dev.index, timing=max(args.steps, 1))
+    plan = _lib.Plan(2, nout, ny, nx, make_taps(s, t, w), device=dev.index,
+                     timing=max(args.steps, 1) if args.full else 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
     ptrs = [d_in[i].data_ptr() for i in range(nt)]
 
@@ -170,37 +211,47 @@ def run_2d(args, world, rank, dev):
         plan.execute(ptrs[:nwin], _lib.OF3D_U16, 0, 0, nout, d_vx.data_ptr(), d_vy.data_ptr(), 0, d_rel.data_ptr(),
                      stream)
 
-    elapsed, profile, dom, dom_ms = timed_region(step, plan, args, world, dev)
+    elapsed, profile, dom, dom_ms = timed_region(step, plan if args.full else None, args, world, dev)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, [(n, o.view(nout, ny, nx)) for n, o in
+                                                  (("vx", d_vx), ("vy", d_vy), ("rel", d_rel))], rank, world)
     if world > 1:
         (elapsed,) = max_over_ranks([elapsed], dev)
     kernels = set(plan.kernels())
     geometry = plan.geometry()
     plan.close()
-    # the same series one output frame per execute (a 1-plane plan, window j)
-    plan1 = _lib.Plan(2, 1, ny, nx, make_taps(s, t, w), device=dev.index)
-    s_vx, s_vy, s_rel = (torch.empty(plane, dtype=torch.float64, device=dev) for _ in range(3))
-    last = {"i": 0}
+    ms1 = None
+    if args.full:
+        # the same series one output frame per execute (a 1-plane plan, window j)
+        plan1 = _lib.Plan(2, 1, ny, nx, make_taps(s, t, w), device=dev.index)
+        s_vx, s_vy, s_rel = (torch.empty(plane, dtype=torch.float64, device=dev) for _ in range(3))
+        last = {"i": 0}
 
-    def step1():
-        j = last["i"] % nout
-        last["i"] += 1
-        plan1.execute(ptrs[j:j + nwin], _lib.OF3D_U16, 0, 0, 1, s_vx.data_ptr(), s_vy.data_ptr(), 0, s_rel.data_ptr(),
-                      stream)
+        def step1():
+            j = last["i"] % nout
+            last["i"] += 1
+            plan1.execute(ptrs[j:j + nwin], _lib.OF3D_U16, 0, 0, 1, s_vx.data_ptr(), s_vy.data_ptr(), 0,
+                          s_rel.data_ptr(), stream)
 
-    el1 = timed_steps(step1, nout * args.steps, nout * args.warmup, world, dev)
-    plan1.close()
+        el1 = timed_steps(step1, nout * args.steps, nout * args.warmup, world, dev)
+        plan1.close()
+        ms1 = el1 / (nout * args.steps) * 1e3
     if rank != 0:
         return
     from oracle import cpu_ref
 
     host = d_in.cpu().numpy().view(np.uint16)
-    same = []
-    for j in range(nout):  # every output frame of the last timed step vs the oracle, bitwise
-        want = cpu_ref.calc_flow2D(host[j:j + nwin], s, t, w, backend="scipy")
-        got = [o.view(nout, ny, nx)[j].cpu().numpy() for o in (d_vx, d_vy, d_rel)]
-        same += [np.array_equal(a.view(np.uint64), np.ascontiguousarray(b).view(np.uint64)) for a, b in zip(got, want)]
-    parity = {"ok": all(same), "crop_out": f"all {nout} output frames of the last step",
-              "vx_vy_rel": "bitwise" if all(same) else "MISMATCH", "checker": "oracle/cpu_ref.py (scipy backend)"}
+    parity = None
+    if not args.no_parity_sample:
+        same = []
+        for j in range(nout):  # every output frame of the last timed step vs the oracle, bitwise
+            want = cpu_ref.calc_flow2D(host[j:j + nwin], s, t, w, backend="scipy")
+            got = [o.view(nout, ny, nx)[j].cpu().numpy() for o in (d_vx, d_vy, d_rel)]
+            same += [np.array_equal(a.view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+                     for a, b in zip(got, want)]
+        parity = {"ok": all(same), "crop_out": f"all {nout} output frames of the last step",
+                  "vx_vy_rel": "bitwise" if all(same) else "MISMATCH", "checker": "oracle/cpu_ref.py (scipy backend)"}
     cpu = None
     if world == 1 and not args.no_cpu_baseline:
         from threadpoolctl import threadpool_limits
@@ -223,11 +274,12 @@ def run_2d(args, world, rank, dev):
     plane = nout * plane  # per launch: the batch's planes
     C = lambda r: 1 + 3 * r
     frame_ops = (C(rt) + 4 * C(rd) + 2 * C(rs) + 5 + 10 * C(rw) + 30) * plane
-    roof = roofline(profile, dom, dom_ms, stage_model_2d(nwin, rd, rs, rt, rw, plane), "c1",
-                    (nwin * 2 + 3 * 8) * plane, frame_ops, nwin, 8, used=kernels)
-    roof["frame"]["bytes_per_voxel"] = nwin * 2 + 3 * 8  # vx, vy, rel: fp64 (2D rel is fp64)
+    roof = None
+    if args.full:
+        roof = roofline(profile, dom, dom_ms, stage_model_2d(nwin, rd, rs, rt, rw, plane), "c1",
+                        (nwin * 2 + 3 * 8) * plane, frame_ops, nwin, 8, used=kernels)
+        roof["frame"]["bytes_per_voxel"] = nwin * 2 + 3 * 8  # vx, vy, rel: fp64 (2D rel is fp64)
     ms = elapsed / args.steps * 1e3
-    ms1 = el1 / (nout * args.steps) * 1e3
     line = {
         "metric": "Mvoxels/s per frame-pair (and HBM GB/s fraction) at 1/2/4/8 MI355X",
         "value": round(world * plane * args.steps / elapsed / 1e6, 3), "unit": "Mvoxels/s", "n_gpus": world,
@@ -238,10 +290,14 @@ def run_2d(args, world, rank, dev):
                    "inputs": f"a series of {nt} uint16 frames resident in HBM; one step = its {nout} output "
                              f"frames as one batch (a 2D plan of {nout} planes)",
                    "frames_per_step": nout, "kernels": sorted(kernels), "geometry": geometry},
-        "roofline": roof, "cpu_baseline": cpu, "parity_sample": parity, "build": build_stamp(),
-        "single_frame": {"ms_per_frame": round(ms1, 5), "value": round(world * plane_b / (ms1 * 1e-3) / 1e6, 3),
-                         "unit": "Mvoxels/s", "what": "the same series one output frame per execute (a 1-plane plan)"},
+        "roofline": roof, "cpu_baseline": cpu, "parity_sample": parity, "build": build_stamp(), "full": args.full,
     }
+    if ms1 is not None:
+        line["single_frame"] = {"ms_per_frame": round(ms1, 5),
+                                "value": round(world * plane_b / (ms1 * 1e-3) / 1e6, 3), "unit": "Mvoxels/s",
+                                "what": "the same series one output frame per execute (a 1-plane plan)"}
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     print(json.dumps(line), flush=True)
 
 
@@ -410,6 +466,8 @@ def timed_region(step, plan, args, world, dev, align=None):
     synchronize, with HIP events only around the dominant stage (the roofline kernel).
     align: called (untimed) before the profile pass and the timed region — K0 batching puts
     both on a batch boundary, so K steps hold ceil(K / M) batched K0 launches.
+    plan=None (a plain run, without --full): no profile pass and no events, warmup -> the
+    timed region only; the profile is then empty and the dominant stage None.
     Returns (elapsed_s, stage profile ms, dominant stage, its ms inside the timed region)."""
     import torch
     import torch.distributed as dist
@@ -923,7 +981,8 @@ def run_slab(args, world, rank, local_rank, dev):
     # (one GPU per rank under RCCL; gloo rehearsals share a device between ranks)
     if replicas is not None and os.environ.get("OF3D_BENCH_BACKEND", "nccl") == "nccl" and base_used > 8.0:
         raise RuntimeError(f"replica buffers not freed before the split: {base_used} GB still in use")
-    sb = SlabBench((nz, ny, nx), (s, t, w), axis, rank, world, dev, fp32=fp32, timing=max(args.steps, 1),
+    sb = SlabBench((nz, ny, nx), (s, t, w), axis, rank, world, dev, fp32=fp32,
+                   timing=max(args.steps, 1) if args.full else 0,
                    vrank=(prank, pworld) if vr else None, seed=seed, pipeline=not args.no_pipeline, k0_batch=kb)
     split_used = device_used_gb(dev)[0]
     plan = sb.plan
@@ -932,14 +991,19 @@ def run_slab(args, world, rank, local_rank, dev):
         while sb.k % sb.batch:
             sb.step()
 
-    elapsed, profile, dom, dom_ms = timed_region(sb.step, plan, args, world, dev, align=align if sb.batch else None)
+    elapsed, profile, dom, dom_ms = timed_region(sb.step, plan if args.full else None, args, world, dev,
+                                                 align=align if sb.batch else None)
+    dumped = None
+    if args.dump_outputs and sb.n_out:
+        dumped = dump_outputs(args.dump_outputs, [(n, o[:sb.n_out]) for n, o in
+                                                  zip(("vx", "vy", "vz", "rel"), sb.outs + [sb.rel])], rank, world)
     finite = sb.finite()
     if world > 1:
         elapsed, bad, split_used = max_over_ranks([elapsed, 0.0 if finite else 1.0, split_used], dev)
         finite = bad == 0.0
     parity = None if args.no_parity_sample or vr else slab_parity(sb, fp32)
     split_detail = None
-    if world > 1 and not vr:  # compute alone / exchange alone on the same ranks and ring
+    if world > 1 and not vr and args.full:  # compute alone / exchange alone on the same ranks and ring
         comp = timed_steps(lambda: sb.step(exchange=False), args.steps, args.warmup, world, dev)
         xchg = timed_steps(lambda: sb.step(compute=False), args.steps, args.warmup, world, dev)
         split_detail = {"compute_ms_max_rank": round(comp / args.steps * 1e3, 5),
@@ -972,11 +1036,13 @@ def run_slab(args, world, rank, local_rank, dev):
         else:
             nb = no = ng = nz
             plane = (ai1 - ai0) * nx
-        roof = roofline(profile, dom, dom_ms, stage_model(nwin, rd, rs, rt, rw, nb, ng, no, plane, sv), cfg,
-                        (nwin * 2 + 3 * sv + 4) * own, frame_ops_per_voxel(rd, rs, rt, rw) * own, nwin, sv,
-                        used=kernels)
-        roof["frame"]["note"] = "this rank's share: " + describe
-        if world > 1 or vr:
+        roof = None
+        if args.full:
+            roof = roofline(profile, dom, dom_ms, stage_model(nwin, rd, rs, rt, rw, nb, ng, no, plane, sv), cfg,
+                            (nwin * 2 + 3 * sv + 4) * own, frame_ops_per_voxel(rd, rs, rt, rw) * own, nwin, sv,
+                            used=kernels)
+            roof["frame"]["note"] = "this rank's share: " + describe
+        if roof is not None and (world > 1 or vr):
             # the committed PMC profile measured a whole-volume launch: its bytes do not describe
             # this rank's slab launch (fewer planes + the halo), and no slab PMC pass exists
             whole = roof["traffic"]
@@ -1010,6 +1076,7 @@ def run_slab(args, world, rank, local_rank, dev):
                        "series": (f"K0 batching: {kb} windows per K0 pass (of3d_plan_execute_ahead)") if kb >= 2 else
                                  ("frame pipelining (of3d_plan_execute_next)" if not args.no_pipeline else "plain")},
             "roofline": roof, "cpu_baseline": cpu, "parity_sample": parity, "build": build_stamp(),
+            "full": args.full,
             "memory": {"device_total_GB": total_gb, "before_split_GB": base_used,
                        "split_GB_max_rank": split_used,
                        "replicas_GB_max_rank": (replicas or {}).get("device_used_GB")},
@@ -1020,6 +1087,8 @@ def run_slab(args, world, rank, local_rank, dev):
             line["replicas"] = replicas
         if other is not None:
             line["row_slabs" if axis == 0 else "z_slabs"] = other
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         print(json.dumps(line), flush=True)
 
 
@@ -1113,7 +1182,20 @@ def main():
     ap.add_argument("--no-parity-sample", action="store_true", help="skip the oracle check of one output crop")
     ap.add_argument("--precision", default="fp64", choices=("fp64", "fp32"),
                     help="fp64 = bit-exact path (the metric's); fp32 = OF3D_FP32 (configs[4]'s path; c5 forces it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (vx, vy, vz, rel; 2D: vx, vy, "
+                         "rel) as DIR/<name>.npy, at most 64 MB in all (a fixed seeded sample of larger outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-stage profile and roofline, the oracle parity sample, "
+                         "cpu_baseline, the single-window / single-frame measurement and, at N > 1, the replicas, "
+                         "the other axis's split and compute / exchange alone (each a run of its own; the "
+                         "--no-* options apply to these)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the result line
+        args.no_cpu_baseline = args.no_parity_sample = args.no_single_window = True
+        args.no_replicas = args.no_strong = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1167,8 +1249,8 @@ def main():
     d_vz = torch.empty_like(d_vx)
     d_rel = torch.empty(vox, dtype=torch.float32, device=dev)
 
-    plan = _lib.Plan(3, nz, ny, nx, make_taps(s, t, w), device=dev.index, timing=max(args.steps, 1),
-                     mode=_lib.OF3D_FP32 if fp32 else 0)
+    plan = _lib.Plan(3, nz, ny, nx, make_taps(s, t, w), device=dev.index,
+                     timing=max(args.steps, 1) if args.full else 0, mode=_lib.OF3D_FP32 if fp32 else 0)
     if args.overlap >= 0:
         plan.set_overlap(args.overlap)
     aptrs = [d_in[i].data_ptr() for i in range(nres)]
@@ -1199,7 +1281,13 @@ def main():
         while last["i"] % kb:
             step()
 
-    elapsed, profile, dom, dom_ms = timed_region(step, plan, args, world, dev, align=align if kb else None)
+    elapsed, profile, dom, dom_ms = timed_region(step, plan if args.full else None, args, world, dev,
+                                                 align=align if kb else None)
+    dumped = None
+    if args.dump_outputs:  # before anything else writes d_v*: the last timed step's outputs
+        dumped = dump_outputs(args.dump_outputs, [(n, o.view(nz, ny, nx)) for n, o in
+                                                  (("vx", d_vx), ("vy", d_vy), ("vz", d_vz), ("rel", d_rel))],
+                              rank, world)
     if world > 1:
         (elapsed,) = max_over_ranks([elapsed], dev)
 
@@ -1253,9 +1341,11 @@ def main():
 
     if rank == 0:
         value = world * vox * args.steps / elapsed / 1e6
-        roof = roofline(profile, dom, dom_ms, stage_model(nwin, rd, rs, rt, rw, nz, nz, nz, ny * nx, sv),
-                        args.config if not fp32 else args.config + "_fp32", (nwin * 2 + 3 * sv + 4) * vox,
-                        frame_ops_per_voxel(rd, rs, rt, rw) * vox, nwin, sv, used=kernels)
+        roof = None
+        if args.full:
+            roof = roofline(profile, dom, dom_ms, stage_model(nwin, rd, rs, rt, rw, nz, nz, nz, ny * nx, sv),
+                            args.config if not fp32 else args.config + "_fp32", (nwin * 2 + 3 * sv + 4) * vox,
+                            frame_ops_per_voxel(rd, rs, rt, rw) * vox, nwin, sv, used=kernels)
         cpu = None
         if world == 1 and not args.no_cpu_baseline:
             sub = min(cpu_sample_planes(nz, ny, nx, args.cpu_budget), nz)
@@ -1282,8 +1372,10 @@ def main():
                                        f"{args.steps} steps"))
                        if kb else None},
             "roofline": roof, "cpu_baseline": cpu,
-            "parity_sample": parity, "build": build_stamp(),
+            "parity_sample": parity, "build": build_stamp(), "full": args.full,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if single is not None:
             line["single_window_ms"] = single["ms_per_step"]
             line["single_window_value"] = single["value"]

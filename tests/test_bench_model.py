@@ -80,3 +80,30 @@ def test_parity_box_straddles_the_first_cut(cfg, world, axis):
         assert 0 <= box[2 * d] < box[2 * d + 1] <= dims[d] and box[2 * d + 1] - box[2 * d] == 16
     lo, hi = box[2 * axis], box[2 * axis + 1]
     assert lo < cut < hi
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: arrays within the budget are written whole, in their own precision and
+    shape; larger ones as the same seeded, sorted flat sample of every array, identical from
+    call to call, and the files stay within the budget."""
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(3)
+    vx = torch.rand((5, 6, 7), dtype=torch.float64, generator=g)
+    rel = torch.rand((5, 6, 7), dtype=torch.float32, generator=g)
+    d = bench.dump_outputs(str(tmp_path / "whole"), [("vx", vx), ("rel", rel)])
+    assert d["files"] == ["vx.npy", "rel.npy"] and d["sample"] is None and d["values_per_array"] == 210
+    got = np.load(tmp_path / "whole" / "vx.npy")
+    assert got.dtype == np.float64 and got.shape == (5, 6, 7) and np.array_equal(got, vx.numpy())
+    assert np.load(tmp_path / "whole" / "rel.npy").dtype == np.float32
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 12 * 50)  # 12 bytes per voxel: 50 of the 210 voxels
+    a = bench.dump_outputs(str(tmp_path / "a"), [("vx", vx), ("rel", rel)])
+    b = bench.dump_outputs(str(tmp_path / "b"), [("vx", vx), ("rel", rel)], rank=1, world=2)
+    assert a["values_per_array"] == 50 and a["of"] == 210 and b["files"] == ["vx_rank1.npy", "rel_rank1.npy"]
+    sx, sr = np.load(tmp_path / "a" / "vx.npy"), np.load(tmp_path / "a" / "rel.npy")
+    assert sx.shape == sr.shape == (50,) and sx.nbytes + sr.nbytes <= 12 * 50
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, 210, size=50))
+    assert np.array_equal(sx, vx.numpy().ravel()[idx]) and np.array_equal(sr, rel.numpy().ravel()[idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "vx_rank1.npy"), sx)

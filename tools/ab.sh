@@ -9,7 +9,7 @@ for cfg in ${CFGS:-c2}; do
     name=${arm%%:*}; envs=${arm#*:}
     [ "$envs" = "$arm" ] && envs=""
     ( IFS=','; for e in $envs; do export "$e"; done; unset IFS
-      timeout -k 10 ${TMO:-150} python bench.py --config $cfg --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/ab_${cfg}_$name.log 2>&1 )
+      timeout -k 10 ${TMO:-150} python bench.py --full --config $cfg --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/ab_${cfg}_$name.log 2>&1 )
     rc=$?; echo "$cfg $name rc=$rc $(grep -o '"ms_per_step": [0-9.]*' $OUT/ab_${cfg}_$name.log) $(grep -o '"stage_ms": {[^}]*}' $OUT/ab_${cfg}_$name.log)"
     [ $rc -eq 0 ] || { tail -5 $OUT/ab_${cfg}_$name.log; exit $rc; }
   done

@@ -16,7 +16,7 @@ for run in $RUNS; do
   IFS=: read cfg prec steps <<< "$run"
   for lib in opticalflow3d_dev_amd/libof3d.so tools/variants/*.so; do
     v=$(basename $lib .so)
-    OF3D_LIB=$PWD/$lib timeout -k 10 300 python bench.py --config $cfg --precision $prec --steps $steps --warmup 2 --no-cpu-baseline > $OUT/ab_${v}_$cfg$prec.log 2>&1
+    OF3D_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --config $cfg --precision $prec --steps $steps --warmup 2 --no-cpu-baseline > $OUT/ab_${v}_$cfg$prec.log 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "$v $cfg bench rc=$rc"; tail -5 $OUT/ab_${v}_$cfg$prec.log; exit $rc; }
     echo "$cfg $prec $v $(grep -o '"ms_per_step": [0-9.]*' $OUT/ab_${v}_$cfg$prec.log) $(grep -o '"stage_ms": {[^}]*}' $OUT/ab_${v}_$cfg$prec.log)"
   done

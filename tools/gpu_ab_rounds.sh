@@ -20,7 +20,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     cfg=${run%%:*}; steps=${run#*:}
     for a in $ARMS; do
       name=${a%%=*}
-      OF3D_ALLOW_STALE=1 OF3D_LIB=$PWD/${a#*=} timeout -k 10 ${BTMO:-300} python bench.py --config $cfg --steps $steps \
+      OF3D_ALLOW_STALE=1 OF3D_LIB=$PWD/${a#*=} timeout -k 10 ${BTMO:-300} python bench.py --full --config $cfg --steps $steps \
         --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/${cfg}_${name}_$r.log 2>&1
       rc=$?; [ $rc -eq 0 ] || { echo "$cfg $name bench rc=$rc"; tail -5 $OUT/${cfg}_${name}_$r.log; exit $rc; }
       echo "$cfg r$r $name $(grep -o '"ms_per_step": [0-9.]*' $OUT/${cfg}_${name}_$r.log | head -1) $(grep -o '"stage_ms": {[^}]*}' $OUT/${cfg}_${name}_$r.log | head -1) $(grep -o '"vxyz": "[^"]*"' $OUT/${cfg}_${name}_$r.log | head -1)"

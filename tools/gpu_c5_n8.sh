@@ -11,7 +11,7 @@ S=${STEPS:-20}; W=${WARMUP:-5}
 run() {  # name, env, args
   local name=$1; shift; local envs=$1; shift
   local t0=$SECONDS
-  env $envs OF3D_VERBOSE=1 timeout -k 10 ${TMO:-400} python bench.py --config c5 --steps $S --warmup $W --no-cpu-baseline "$@" \
+  env $envs OF3D_VERBOSE=1 timeout -k 10 ${TMO:-400} python bench.py --full --config c5 --steps $S --warmup $W --no-cpu-baseline "$@" \
     > $OUT/c5n8_${TAG}_$name.log 2>&1 || { tail -5 $OUT/c5n8_${TAG}_$name.log; exit 1; }
   echo "$name wall_s=$((SECONDS - t0)) $(grep -o '"ms_per_step": [0-9.]*' $OUT/c5n8_${TAG}_$name.log | head -1) $(grep -o '"memory": {[^}]*}' $OUT/c5n8_${TAG}_$name.log) $(grep -o '"stage_ms": {[^}]*}' $OUT/c5n8_${TAG}_$name.log | head -1) $(grep -o '"vxyz": "[^"]*"' $OUT/c5n8_${TAG}_$name.log | head -1)"
 }
