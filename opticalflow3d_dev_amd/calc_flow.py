@@ -156,13 +156,17 @@ def _flow_fp32(images, ndim, xyzSig, tSig, wSig):
 def calc_flow3D_fp32(images, xyzSig=3, tSig=1, wSig=4):
     """calc_flow3D on the fp32 path (OF3D_FP32, configs[4]): filter passes and
     the structure tensor in float32 (scipy order), solve and eigenvalue in
-    fp64 on that tensor; returns float32 vx, vy, vz, rel.  Not bit-exact:
-    max|dv| <= 1e-4 max|v| against calc_flow3D on smooth data."""
+    fp64 on that tensor; returns float32 vx, vy, vz, rel.  vx, vy, vz are
+    bit-identical to the float32 restatement of the reference (oracle.cpu_ref,
+    dtype float32: frames and taps rounded to float32, every pass and product in
+    float32, no FMA, solve in fp64, results rounded to float32), and within
+    max|dv| <= 1e-4 max|v| of calc_flow3D on smooth data."""
     return _flow_fp32(images, 3, xyzSig, tSig, wSig)
 
 
 def calc_flow2D_fp32(images, xySig=3, tSig=1, wSig=4):
-    """calc_flow2D on the fp32 path; float32 vx, vy, rel."""
+    """calc_flow2D on the fp32 path; float32 vx, vy, rel, bit-identical to the
+    float32 restatement (oracle.cpu_ref, dtype float32; rel NaN at the same pixels)."""
     return _flow_fp32(images, 2, xySig, tSig, wSig)
 
 

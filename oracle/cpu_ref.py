@@ -22,6 +22,14 @@ Two backends for the separable 1-D correlation:
 * ``"scipy"`` — ``scipy.ndimage.correlate1d`` itself (the primitive the
   reference calls, ``calc_flow.py:8``); used for the timed CPU baseline
   because it is the reference's own speed.
+
+``dtype=np.float32`` on ``correlate1d_restated`` / ``structure_tensor3d`` /
+``structure_tensor2d`` restates the library's fp32 mode (OF3D_FP32): frames cast and
+taps rounded to float32, every pass and product in float32 in the same order; with
+``calc_flow3D_fp32_oracle`` / ``calc_flow2D_fp32_oracle`` (solve in float64 on the promoted
+tensor, results rounded to float32) it is what the device's fp32 outputs are held to bit
+for bit.  Its float64 instance is the golden-pinned code itself; its distance from the
+fp64 goldens is pinned in ``tests/test_oracle_fp32.py``.
 """
 
 from __future__ import annotations
@@ -81,23 +89,33 @@ def _symmetry(w):
     return 0
 
 
-def correlate1d_restated(a, w, axis):
-    """From-scratch scipy.ndimage.correlate1d(a, w, axis, mode='nearest')."""
-    a = np.asarray(a, dtype=np.float64)
+def correlate1d_restated(a, w, axis, dtype=np.float64):
+    """From-scratch scipy.ndimage.correlate1d(a, w, axis, mode='nearest').
+
+    dtype=np.float32 restates the library's fp32 mode (OF3D_FP32): the same summation
+    order with the taps rounded to float32 (``w.astype(np.float32)``, round to nearest)
+    and every product and sum in float32; the symmetry test stays on the fp64 taps."""
+    dtype = np.dtype(dtype)
     w = np.asarray(w, dtype=np.float64)
+    sym = _symmetry(w)
+    a = np.asarray(a, dtype=dtype)
+    w = w.astype(dtype)
     r = len(w) // 2
     L = a.shape[axis]
-    sym = _symmetry(w)
-    base = np.arange(L)
+    axis = axis % a.ndim
+    # mode='nearest': the edge values repeated len(w) times each side, once; a shifted line is a view
+    pad = len(w)
+    padded = np.pad(a, [(pad, pad) if d == axis else (0, 0) for d in range(a.ndim)], mode="edge")
 
     def shifted(off):
-        return np.take(a, np.clip(base + off, 0, L - 1), axis=axis)
+        return padded[(slice(None),) * axis + (slice(pad + off, pad + off + L),)]
 
     if sym == 0:  # general branch: o = c[+r']*w[last]; for j=-r..r'-1: o += c[j]*w[j]
         r2 = len(w) - r - 1
         out = shifted(r2) * w[r + r2]
         for j in range(-r, r2):
             out = out + shifted(j) * w[r + j]
+        assert out.dtype == dtype, out.dtype
         return out
     out = a * w[r]
     for j in range(-r, 0):
@@ -105,17 +123,47 @@ def correlate1d_restated(a, w, axis):
             out = out + (shifted(j) + shifted(-j)) * w[r + j]
         else:
             out = out + (shifted(j) - shifted(-j)) * w[r + j]
+    assert out.dtype == dtype, out.dtype  # no silent NumPy promotion
     return out
 
 
-def _correlate(backend):
+def _pass_dtype(dtype):
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"oracle passes run in float64 or float32, not {dtype}")
+    return dtype
+
+
+def _correlate(backend, dtype=np.float64):
+    dtype = _pass_dtype(dtype)
     if backend == "restated":
-        return correlate1d_restated
+        return lambda a, w, axis: correlate1d_restated(a, w, axis, dtype)
     if backend == "scipy":
+        if dtype != np.float64:  # scipy.ndimage.correlate1d accumulates in double whatever the arrays are
+            raise ValueError("the scipy backend computes in float64: use backend='restated' for float32")
         from scipy.ndimage import correlate1d
 
         return lambda a, w, axis: correlate1d(a, w, axis=axis, mode="nearest")
     raise ValueError(backend)
+
+
+def _tderiv_centre(imgs, c, T, dtype):
+    """T2: the centre output line of the time correlation (antisymmetric taps T), in dtype."""
+    rt = len(T) // 2
+    Nt = imgs.shape[0]
+    Tq = np.asarray(T, np.float64).astype(dtype)
+    frame = lambda k: imgs[min(max(k, 0), Nt - 1)].astype(dtype)
+    dt0 = frame(c) * Tq[rt]
+    for j in range(-rt, 0):
+        dt0 = dt0 + (frame(c + j) - frame(c - j)) * Tq[rt + j]
+    assert dt0.dtype == dtype, dt0.dtype
+    return dt0
+
+
+def _prod(a, b, dtype):
+    out = a * b
+    assert out.dtype == dtype, out.dtype
+    return out
 
 
 # --------------------------------------------------------------------------
@@ -142,34 +190,31 @@ def _check(images, ndim, tSig, msg_ndim):
 # --------------------------------------------------------------------------
 # 3D — calc_flow.py:175-360
 # --------------------------------------------------------------------------
-def structure_tensor3d(images, xyzSig=3, tSig=1, wSig=4, backend="restated", taps=None):
-    """Steps T2-T5: returns the nine windowed products (fp64 volumes)."""
+def structure_tensor3d(images, xyzSig=3, tSig=1, wSig=4, backend="restated", taps=None, dtype=np.float64):
+    """Steps T2-T5: returns the nine windowed products (volumes of dtype: float64, or
+    float32 for the restatement of the library's fp32 mode — frames cast to float32, taps
+    rounded to float32, every pass and product in float32; "restated" backend only)."""
     c = _check(images, 4, tSig, MSG_NDIM_3D)
-    cor = _correlate(backend)
+    dtype = _pass_dtype(dtype)
+    cor = _correlate(backend, dtype)
     tp = make_taps(xyzSig, tSig, wSig) if taps is None else taps
     G, D, S, T, W = tp["gauss"], tp["deriv"], tp["smooth"], tp["tderiv"], tp["window"]
     imgs = np.asarray(images)
     # T2 (calc_flow.py:276-277): temporal derivative, only the centre frame is
     # kept, so only the centre output line of the time correlation is formed.
-    rt = len(T) // 2
-    Nt = imgs.shape[0]
-    dt0 = None
-    frame = lambda k: imgs[min(max(k, 0), Nt - 1)].astype(np.float64)
-    dt0 = frame(c) * T[rt]
-    for j in range(-rt, 0):
-        dt0 = dt0 + (frame(c + j) - frame(c - j)) * T[rt + j]
-    I = imgs[c].astype(np.float64)
+    dt0 = _tderiv_centre(imgs, c, T, dtype)
+    I = imgs[c].astype(dtype)
     # T4 (calc_flow.py:279-288): y (axis 1) -> x (axis 2) -> z (axis 0)
     dt = cor(cor(cor(dt0, G, 1), G, 2), G, 0)
     dy = cor(cor(cor(I, D, 1), S, 2), S, 0)
     dx = cor(cor(cor(I, S, 1), D, 2), S, 0)
     dz = cor(cor(cor(I, S, 1), S, 2), D, 0)
     # T5 (calc_flow.py:300-313)
-    wf = lambda p: cor(cor(cor(p, W, 1), W, 2), W, 0)
+    wf = lambda a, b: cor(cor(cor(_prod(a, b, dtype), W, 1), W, 2), W, 0)
     return {
-        "tx": wf(dx * dt), "ty": wf(dy * dt), "tz": wf(dz * dt),
-        "xy": wf(dx * dy), "xz": wf(dx * dz), "x2": wf(dx * dx),
-        "yz": wf(dy * dz), "y2": wf(dy * dy), "z2": wf(dz * dz),
+        "tx": wf(dx, dt), "ty": wf(dy, dt), "tz": wf(dz, dt),
+        "xy": wf(dx, dy), "xz": wf(dx, dz), "x2": wf(dx, dx),
+        "yz": wf(dy, dz), "y2": wf(dy, dy), "z2": wf(dz, dz),
     }
 
 
@@ -217,26 +262,23 @@ def calc_flow3D(images, xyzSig=3, tSig=1, wSig=4, backend="restated"):
 # --------------------------------------------------------------------------
 # 2D — calc_flow.py:18-173
 # --------------------------------------------------------------------------
-def structure_tensor2d(images, xySig=3, tSig=1, wSig=4, backend="restated", taps=None):
+def structure_tensor2d(images, xySig=3, tSig=1, wSig=4, backend="restated", taps=None, dtype=np.float64):
+    """The five windowed products, in dtype (float64 / float32: see structure_tensor3d)."""
     c = _check(images, 3, tSig, MSG_NDIM_2D)
-    cor = _correlate(backend)
+    dtype = _pass_dtype(dtype)
+    cor = _correlate(backend, dtype)
     tp = make_taps(xySig, tSig, wSig) if taps is None else taps
     G, D, S, T, W = tp["gauss"], tp["deriv"], tp["smooth"], tp["tderiv"], tp["window"]
     imgs = np.asarray(images)
-    Nt = imgs.shape[0]
-    rt = len(T) // 2
-    frame = lambda k: imgs[min(max(k, 0), Nt - 1)].astype(np.float64)
-    dt0 = frame(c) * T[rt]
-    for j in range(-rt, 0):
-        dt0 = dt0 + (frame(c + j) - frame(c - j)) * T[rt + j]
-    I = imgs[c].astype(np.float64)
+    dt0 = _tderiv_centre(imgs, c, T, dtype)
+    I = imgs[c].astype(dtype)
     # calc_flow.py:116-122: y (axis 0) -> x (axis 1)
     dt = cor(cor(dt0, G, 0), G, 1)
     dy = cor(cor(I, D, 0), S, 1)
     dx = cor(cor(I, S, 0), D, 1)
-    wf = lambda p: cor(cor(p, W, 0), W, 1)
-    return {"tx": wf(dx * dt), "ty": wf(dy * dt), "xy": wf(dx * dy),
-            "x2": wf(dx * dx), "y2": wf(dy * dy)}
+    wf = lambda a, b: cor(cor(_prod(a, b, dtype), W, 0), W, 1)
+    return {"tx": wf(dx, dt), "ty": wf(dy, dt), "xy": wf(dx, dy),
+            "x2": wf(dx, dx), "y2": wf(dy, dy)}
 
 
 def solve2d(st):
@@ -256,6 +298,33 @@ def solve2d(st):
 def calc_flow2D(images, xySig=3, tSig=1, wSig=4, backend="restated"):
     """Restated calc_flow.py:18-173 -> (vx, vy, rel[float64])."""
     return solve2d(structure_tensor2d(images, xySig, tSig, wSig, backend))
+
+
+# --------------------------------------------------------------------------
+# The library's fp32 mode (OF3D_FP32), restated: frames cast to float32, taps rounded to
+# float32, every pass and product in float32 in the scipy order (structure_tensor*d with
+# dtype=float32); the float32 tensor promoted to float64, the solve (and the eigenvalue)
+# in float64 exactly as above, and the results rounded to float32.
+# --------------------------------------------------------------------------
+def _promote(st):
+    for k, v in st.items():
+        assert v.dtype == np.float32, (k, v.dtype)
+    return {k: v.astype(np.float64) for k, v in st.items()}
+
+
+def calc_flow3D_fp32_oracle(images, xyzSig=3, tSig=1, wSig=4, taps=None):
+    """-> (vx, vy, vz [float32], lambda_min, lambda_max [float64 eigvalsh of the promoted
+    float32 tensor; the device's float32 rel is held to 1e-6 * lambda_max of these])."""
+    st = _promote(structure_tensor3d(images, xyzSig, tSig, wSig, "restated", taps, dtype=np.float32))
+    vx, vy, vz = (v.astype(np.float32) for v in solve3d(st))
+    lmin, lmax = eig_fp64_3d(st)
+    return vx, vy, vz, lmin, lmax
+
+
+def calc_flow2D_fp32_oracle(images, xySig=3, tSig=1, wSig=4, taps=None):
+    """-> (vx, vy, rel), float32; rel NaN where the fp64 discriminant rounds negative."""
+    st = _promote(structure_tensor2d(images, xySig, tSig, wSig, "restated", taps, dtype=np.float32))
+    return tuple(v.astype(np.float32) for v in solve2d(st))
 
 
 # --------------------------------------------------------------------------
@@ -288,6 +357,25 @@ def synthetic_stack_np(shape, seed=20260206, motion=(0.3, -0.2, -0.1)):
         noise = rng.integers(-8, 9, size=sp)
         out[t] = np.clip(1000 + 300 * s + noise, 0, 65535).astype(np.uint16)
     return out
+
+
+# Inputs a float32 cannot hold (the fp32 mode casts each frame first, rounding to nearest)
+CAST_DTYPES = (np.uint32, np.int32, np.float64)
+
+
+def cast_case_images(shape, dtype, seed):
+    """Frames whose astype(float32) rounds: integers above 2^24 (odd ones included), float64
+    values with fractions float32 has no bits for.  Smooth enough that the flow is not noise."""
+    rng = np.random.default_rng(seed)
+    grids = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
+    s = sum(np.sin(0.5 * g + 0.9 * k) for k, g in enumerate(grids))
+    if np.dtype(dtype).kind == "f":
+        return (1000 + 300 * s + rng.uniform(-3, 3, size=shape)).astype(dtype)  # 52-bit fractions
+    base = (1 << 24) + 20000  # |3000 s| <= 3000 * (number of axes) < 20000 - 40
+    img = base + (3000 * s).astype(np.int64) + rng.integers(-40, 41, size=shape)
+    if np.dtype(dtype).kind == "i":
+        img = np.where(grids[-1] % 2 == 0, img, -img)  # both signs
+    return img.astype(dtype)
 
 
 def analysis_reference(vx, vy, vz, rel, relPer=90, xyscale=1.0, zscale=1.0, tscale=1.0):

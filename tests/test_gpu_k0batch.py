@@ -91,6 +91,13 @@ def test_batching_off_paths(env, monkeypatch):
             for a, b in zip(got, calc_flow3D(stack[k:k + nwin], s, t, w)):
                 assert bits_equal(a, b), (env, k)
         assert "k_tderiv_multi" not in plan.kernels(), plan.kernels()
+        # ... and the switch took: the general-radius path reports itself and nothing else,
+        # K3 + K4 stand in for the fused W kernel
+        if "OF3D_GENERAL" in env:
+            assert plan.kernels() == ["general"] and plan.geometry()["general"] == 1, plan.kernels()
+        if "OF3D_K34" in env:
+            assert {"k_prod_wy", "k_wx"} <= set(plan.kernels()), plan.kernels()
+            assert not any(k.startswith("k_prod_wyx") for k in plan.kernels()), plan.kernels()
     finally:
         plan.close()
 

@@ -18,7 +18,10 @@ FAMILY_ENV = ("OF3D_K34", "OF3D_K5C", "OF3D_K1C", "OF3D_K12", "OF3D_K5C_NW", "OF
               "OF3D_K12_ZC")
 
 
-def _run(img, s, t, w, ndim, mode, old, force=None, kernels=None):
+def _run(img, s, t, w, ndim, mode, old, force=None, kernels=None, geometry=None):
+    """One execution of a fresh plan under the kernel-family switches (old: every FAMILY_ENV
+    switch 0; force: switches set on top); kernels (a list) and geometry (a dict) receive
+    plan.kernels() and plan.geometry() after the execution: what actually ran."""
     import torch
 
     saved = {k: os.environ.get(k) for k in FAMILY_ENV}
@@ -50,6 +53,8 @@ def _run(img, s, t, w, ndim, mode, old, force=None, kernels=None):
             torch.cuda.synchronize(dev)
             if kernels is not None:
                 kernels.extend(plan.kernels())
+            if geometry is not None:
+                geometry.update(plan.geometry())
         finally:
             plan.close()
         res = [o.cpu().numpy() for o in outs[:3 if ndim == 3 else 2]] + [rel.cpu().numpy()]
@@ -85,16 +90,51 @@ def test_families_bit_identical(case, fp32):
         assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
+def _up(shape, m):
+    """shape with nx rounded up to a multiple of m."""
+    return shape[:-1] + ((shape[-1] + m - 1) // m * m,)
+
+
+def _k12_instance(rd, fp32):
+    """K12 instances (kt_grad3.hip): rd 3 and 6 (xyzSig 1, 2), rd 9 in fp32 only."""
+    return rd in (3, 6) or (rd == 9 and fp32)
+
+
 @pytest.mark.parametrize("case", range(3))
 @pytest.mark.parametrize("fp32", [False, True])
 def test_fused_gradients_k12_forced(case, fp32):
     """K12 (fused y/x/z gradient passes) forced on volumes below its size heuristic, against
-    K1c + K2c and the older kernels: every output bit-identical."""
+    K1c + K2c and the older kernels: every output bit-identical.  K12 stages rows by LDS DMA:
+    uint16 rows of 16-byte multiples, so nx is rounded up to a multiple of 8 (272, 144, 536), and
+    the plan must report the kernel (fp64 has no rd 9 instance: K1c + K2c there, also asserted)."""
     shape, (s, t, w), ndim = CASES[case]
+    shape = _up(shape, 8)
     rng = np.random.default_rng(400 + case)
     img = rng.integers(0, 4096, size=shape).astype(np.uint16)
     mode = _lib.OF3D_FP32 if fp32 else 0
-    new = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_K12": "1"})
+    used = []
+    new = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_K12": "1"}, kernels=used)
+    if _k12_instance(radii(s, t, w)[0], fp32):
+        assert "k_grad_xyz_c" in used and "k_grad_xy_c" not in used, used
+    else:
+        assert "k_grad_xyz_c" not in used and "k_grad_xy_c" in used, used
+    ref = _run(img, s, t, w, ndim, mode, old=True)
+    for a, b in zip(new, ref):
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+@pytest.mark.parametrize("case", range(3))
+@pytest.mark.parametrize("fp32", [False, True])
+def test_fused_gradients_k12_forced_misaligned_rows(case, fp32):
+    """OF3D_K12=1 on rows that are no 16-byte multiple (nx 266, 140, 530): the plan must fall
+    back to K1c + K2c, say so, and stay bit-identical to the older kernels."""
+    shape, (s, t, w), ndim = CASES[case]
+    assert shape[-1] % 8
+    img = np.random.default_rng(400 + case).integers(0, 4096, size=shape).astype(np.uint16)
+    mode = _lib.OF3D_FP32 if fp32 else 0
+    used = []
+    new = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_K12": "1"}, kernels=used)
+    assert "k_grad_xyz_c" not in used and "k_grad_xy_c" in used, used
     ref = _run(img, s, t, w, ndim, mode, old=True)
     for a, b in zip(new, ref):
         assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
@@ -122,12 +162,34 @@ def test_fused_gradients_k12_xyzsig1(zc, fp32):
 @pytest.mark.parametrize("fp32", [False, True])
 def test_wz_solve_eight_wave_blocks(case, fp32):
     """K5c with 8-wave, 128-plane blocks (OF3D_K5C_NW=8; the default for volumes with >= 128
-    output planes) forced on small volumes: bit-identical to the older kernels."""
+    output planes) forced on small volumes: bit-identical to the older kernels.  K5c stages
+    16-byte rows of the pass type, so in fp32 nx is rounded up to a multiple of 4 (268, 140,
+    532; fp64 keeps 266, 140, 530: nx % 2 == 0); the plan must report K5c in 8-wave blocks."""
     shape, (s, t, w), ndim = CASES[case]
+    if fp32:
+        shape = _up(shape, 4)
     img = np.random.default_rng(600 + case).integers(0, 4096, size=shape).astype(np.uint16)
     mode = _lib.OF3D_FP32 if fp32 else 0
-    new = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_K5C_NW": "8"})
+    used, geom = [], {}
+    new = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_K5C_NW": "8"}, kernels=used, geometry=geom)
+    assert "k_wz_solve_c" in used and geom["k5c"]["nw"] == 8, (used, geom)
     ref = _run(img, s, t, w, ndim, mode, old=True)
+    for a, b in zip(new, ref):
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+@pytest.mark.parametrize("case", [0, 2])
+def test_wz_solve_eight_wave_blocks_misaligned_rows_fp32(case):
+    """OF3D_K5C_NW=8 in fp32 on rows that are no 16-byte multiple (nx 266, 530): no K5c at all;
+    the plan must run the older W z + solve kernel, say so, and stay bit-identical."""
+    shape, (s, t, w), ndim = CASES[case]
+    assert shape[-1] % 4
+    img = np.random.default_rng(600 + case).integers(0, 4096, size=shape).astype(np.uint16)
+    used, geom = [], {}
+    new = _run(img, s, t, w, ndim, _lib.OF3D_FP32, old=False, force={"OF3D_K5C_NW": "8"}, kernels=used,
+               geometry=geom)
+    assert "k_wz_solve_c" not in used and "k_wz_solve" in used and geom["k5c"]["nw"] == 0, (used, geom)
+    ref = _run(img, s, t, w, ndim, _lib.OF3D_FP32, old=True)
     for a, b in zip(new, ref):
         assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
@@ -142,8 +204,12 @@ def test_wxy_plain_and_tiled_layouts(case, fp32):
     shape = shape[:-1] + (((shape[-1] + 31) // 32) * 32,)  # nx a multiple of 32: the tiled layout
     img = np.random.default_rng(660 + case).integers(0, 4096, size=shape).astype(np.uint16)
     mode = _lib.OF3D_FP32 if fp32 else 0
-    tiled = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_WXY_TILE": "1"})
-    plain = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_WXY_TILE": "0"})
+    used, geom, used0, geom0 = [], {}, [], {}
+    tiled = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_WXY_TILE": "1"}, kernels=used, geometry=geom)
+    assert geom["wxy_zt"] == shape[1] and "k_wz_solve_c" in used, (used, geom)  # z-tiled, all planes
+    assert any(k.startswith("k_prod_wyx") for k in used), used
+    plain = _run(img, s, t, w, ndim, mode, old=False, force={"OF3D_WXY_TILE": "0"}, kernels=used0, geometry=geom0)
+    assert geom0["wxy_zt"] == 0 and "k_wz_solve_c" in used0, (used0, geom0)
     ref = _run(img, s, t, w, ndim, mode, old=True)
     for a, b, c in zip(tiled, plain, ref):
         assert a.dtype == c.dtype and np.array_equal(a.view(np.uint8), c.view(np.uint8))

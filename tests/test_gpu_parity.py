@@ -158,6 +158,62 @@ def test_seeded_3d_fused_gradients(case, monkeypatch):
     test_seeded_3d_vs_oracle(case)
 
 
+# The two tests above go through the host entry point, which cannot say which kernels ran, and
+# most of their shapes cannot run K12 at all: it stages 16-byte rows (nx * itemsize % 16 == 0) of
+# uint8 / uint16 / float32 frames at xyzSig 1, 2 (fp64).  These shapes can (or, for the two input
+# dtypes without an instance, cannot on purpose); they run through a plan, which reports its kernels.
+# (shape, sigmas, dtype, K12 runs)
+SEEDED_3D_K12 = [
+    ((7, 16, 40, 72), (1, 1, 3), np.uint16, True),
+    ((13, 20, 64, 64), (2, 2, 5), np.uint16, True),
+    ((7, 5, 70, 144), (1, 1, 2), np.uint8, True),       # uint8: nx % 16 == 0
+    ((7, 6, 30, 40), (1, 1, 2), np.float32, True),
+    ((7, 6, 30, 40), (1, 1, 2), np.int32, False),       # no K12 (or K1c) instance: k_grad_xy + K2c
+    ((7, 6, 30, 40), (1, 1, 2), np.float64, False),
+    ((7, 4, 37, 600), (1, 1, 5), np.uint16, True),      # rw 15: several K12 column tiles
+    ((7, 2, 70, 1104), (1, 1, 7), np.uint16, True),
+    ((7, 16, 40, 70), (1, 1, 3), np.uint16, False),     # 140-byte rows: the fallback, on purpose
+]
+
+
+@pytest.mark.parametrize("case", range(len(SEEDED_3D_K12)))
+def test_seeded_3d_fused_gradients_ran(case, monkeypatch):
+    """OF3D_K12=1 through a plan: bit-identical to the oracle, and of3d_plan_kernels names
+    k_grad_xyz_c exactly where the shape and dtype allow it."""
+    import torch
+
+    from opticalflow3d_dev_amd import _lib, make_taps, radii
+
+    monkeypatch.setenv("OF3D_K12", "1")
+    shape, (s, t, w), dt, k12 = SEEDED_3D_K12[case]
+    img = _rand(shape, dt, 150 + case)
+    nt, nz, ny, nx = shape
+    rt = radii(s, t, w)[2]
+    c = nt // 2
+    win = np.ascontiguousarray(img[c - rt:c + rt + 1])
+    d_in = torch.from_numpy(win.view(np.uint8).reshape(2 * rt + 1, -1)).to("cuda")
+    n = nz * ny * nx
+    outs = [torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(3)]
+    d_rel = torch.empty(n, dtype=torch.float32, device="cuda")
+    plan = _lib.Plan(3, nz, ny, nx, make_taps(s, t, w), device=0)
+    try:
+        plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.DTYPE_CODES[img.dtype], 0, 0, nz,
+                     outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), d_rel.data_ptr())
+        torch.cuda.synchronize()
+        used = plan.kernels()
+    finally:
+        plan.close()
+    assert ("k_grad_xyz_c" in used) == k12, used
+    if not k12:
+        assert set(used) & {"k_grad_xy_c", "k_grad_xy"}, used
+    vx, vy, vz = (o.cpu().numpy().reshape(nz, ny, nx) for o in outs)
+    st = cpu_ref.structure_tensor3d(img, s, t, w, backend="scipy")
+    ox, oy, oz = cpu_ref.solve3d(st)
+    assert bits_equal(vx, ox) and bits_equal(vy, oy) and bits_equal(vz, oz)
+    lmin, lmax = cpu_ref.eig_fp64_3d(st)
+    assert_rel_close(d_rel.cpu().numpy().reshape(nz, ny, nx), lmin, lmax, REL_TOL_REF)
+
+
 @pytest.fixture
 def general_path(monkeypatch):
     """OF3D_GENERAL=1: every plan runs the general-radius kernels (k_corr_gen passes); the
