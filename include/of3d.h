@@ -253,6 +253,60 @@ int of3d_flow_stats(const void* vx, const void* vy, const void* vz, const void* 
                     int64_t n, double thresh, double xyscale, double zscale, double tscale, double* out_vx,
                     double* out_vy, double* out_vz, double* magnitude, double* theta, double* phi, void* stream);
 
+/* Exact order statistics of a device array without leaving the device (radix select on the
+ * order-preserving integer image of the float bits, 11-bit digits: 3 passes over float32, 6
+ * over float64): the element of 0-based rank `lo` (a) and of rank `hi` (b) of the n values
+ * (float32, or float64 with is_f64), lo <= hi <= n-1, combined as numpy's 'linear'
+ * percentile does in the array's dtype: a + (b-a)*gamma for gamma < 0.5, else
+ * b - (b-a)*(1-gamma); a when lo == hi (by the same expression, so an infinite a gives NaN as
+ * numpy's does); NaN when the array holds a NaN.  -0.0 and +0.0 are one value.  `out`: one device element of the array's dtype.  Everything is enqueued on
+ * `stream`; nothing is copied to the host and nothing synchronises, so the value can feed the
+ * next kernel (of3d_flow_summary's d_thresh).  `workspace`: device memory of
+ * of3d_quantile_workspace_bytes(is_f64) bytes (independent of n), 8-byte aligned.
+ * The reference takes np.percentile(rel, relPer) on the host (example_analysis_script.ipynb
+ * cell 4). */
+size_t of3d_quantile_workspace_bytes(int is_f64);
+int of3d_quantile(const void* d_a, int is_f64, int64_t n, int64_t lo, int64_t hi, double gamma, void* d_out,
+                  void* workspace, void* stream);
+
+/* Frame summary on resident outputs: of3d_flow_stats' per-voxel arithmetic (mask = rel >
+ * *d_thresh, a threshold in rel's dtype on the device; v*mask, exact zeros -> NaN,
+ * (v*scale)/tscale; magnitude; theta = atan2(vy, vx); phi = atan(vz / sqrt(vx^2+vy^2)), 3D
+ * only) reduced over n_roi <= 16 boxes of the (nz, ny, nx) volume instead of stored: what the
+ * reference's figure scripts compute from the saved TIFFs (plot_figure4_timeTraces.m:82-126,
+ * plot_figure3_ROIfigures.m:114-193).  rois: host int64[n_roi][6] = z0 z1 y0 y1 x0 x1,
+ * half-open, inside the volume and not empty.  A voxel is valid when its magnitude is not NaN.
+ * nbins: host int[6], edges: host double*[6] (entry q: nbins[q] + 1 strictly ascending edges;
+ * ignored where nbins[q] == 0) for the quantities 0 vx, 1 vy, 2 vz, 3 magnitude, 4 theta,
+ * 5 phi; at most 256 bins each, 0 = no histogram; np.histogram(values, bins=edges) semantics
+ * over the valid voxels (last bin closed, values outside and NaN dropped; counts, not
+ * magnitude-weighted).  2D: vz == NULL, nz == 1, nbins[2] == nbins[5] == 0.
+ *
+ * Result (device, of3d_flow_summary_result_bytes(n_roi, nbins) bytes, 8-byte words):
+ *   word 0        the threshold as float64
+ *   word 1        n_roi (uint64)
+ *   words 2..7    nbins[0..5] (uint64)
+ *   then per box, 10 + sum(nbins) words:
+ *     0  n_valid (int64)      1  n_voxels (int64)
+ *     2..9  float64 sums over the valid voxels: magnitude, vx, vy, vz (0 in 2D), sin(theta),
+ *           cos(theta), magnitude*sin(theta), magnitude*cos(theta)  (sin = vy/h, cos = vx/h,
+ *           h = sqrt(vx^2+vy^2))
+ *     10..  uint64 histogram counts, quantity after quantity (nbins[q] words each)
+ * Deterministic: no floating-point atomics; the workgroups of a box are a function of the
+ * box's size alone, each sums in a fixed order into its own workspace slot, and a second
+ * kernel adds the slots in index order, so equal inputs give equal bits on every run and a
+ * box's words do not depend on the other boxes.  `workspace`: device memory of
+ * of3d_flow_summary_workspace_bytes() bytes.  Enqueued on `stream`; no host synchronisation. */
+#define OF3D_SUMMARY_QUANTITIES 6
+#define OF3D_SUMMARY_MAX_BINS 256
+#define OF3D_SUMMARY_MAX_ROI 16
+size_t of3d_flow_summary_result_bytes(int n_roi, const int* nbins);
+size_t of3d_flow_summary_workspace_bytes(void);
+int of3d_flow_summary(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32,
+                      int rel_f64, int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale,
+                      double zscale, double tscale, const int64_t* rois, int n_roi, const int* nbins,
+                      const double* const* edges, void* d_result, void* workspace, void* stream);
+
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order
  * x2 y2 z2 xy xz yz (calc_flow.py:352-354's matrix (x2 xy xz / xy y2 yz /

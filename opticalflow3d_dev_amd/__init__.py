@@ -6,8 +6,11 @@ Drop-in for the hot path of ScientistRachel/OpticalFlow3D_dev
 ``libof3d.so`` (C-ABI: include/of3d.h).
 """
 
+from .analysis import (SummarySpec, flow_statistics, flow_summary, percentile_threshold,  # noqa: F401
+                       percentile_threshold_device)
 from .calc_flow import calc_flow, calc_flow2D, calc_flow2D_fp32, calc_flow3D, calc_flow3D_fp32, process_flow  # noqa: F401
 from .taps import make_taps, radii  # noqa: F401
 
 __all__ = ["calc_flow", "calc_flow2D", "calc_flow3D", "process_flow", "calc_flow2D_fp32", "calc_flow3D_fp32",
-           "make_taps", "radii"]
+           "make_taps", "radii", "SummarySpec", "flow_statistics", "flow_summary", "percentile_threshold",
+           "percentile_threshold_device"]

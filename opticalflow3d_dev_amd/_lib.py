@@ -41,6 +41,8 @@ EXPORTED = (
     "of3d_plan_set_overlap", "of3d_cache_clear", "of3d_plan_set_rows",
     "of3d_plan_kernels", "of3d_build_info", "of3d_plan_execute_next", "of3d_plan_execute_ahead",
     "of3d_rel3d", "of3d_plan_geometry",
+    "of3d_quantile", "of3d_quantile_workspace_bytes", "of3d_flow_summary", "of3d_flow_summary_result_bytes",
+    "of3d_flow_summary_workspace_bytes",
 )
 
 CSRC = os.path.join(_HERE, "csrc")
@@ -193,6 +195,18 @@ def load():
         d = ctypes.c_double
         lib.of3d_flow_stats.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int, i64, d, d, d, d, P, P, P, P, P, P, P]
         lib.of3d_flow_stats.restype = ctypes.c_int
+        lib.of3d_quantile_workspace_bytes.argtypes = [ctypes.c_int]
+        lib.of3d_quantile_workspace_bytes.restype = ctypes.c_size_t
+        lib.of3d_quantile.argtypes = [P, ctypes.c_int, i64, i64, i64, d, P, P, P]
+        lib.of3d_quantile.restype = ctypes.c_int
+        lib.of3d_flow_summary_result_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.of3d_flow_summary_result_bytes.restype = ctypes.c_size_t
+        lib.of3d_flow_summary_workspace_bytes.argtypes = []
+        lib.of3d_flow_summary_workspace_bytes.restype = ctypes.c_size_t
+        lib.of3d_flow_summary.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int, i64, i64, i64, P, d, d, d,
+                                          ctypes.POINTER(i64), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(D), P, P, P]
+        lib.of3d_flow_summary.restype = ctypes.c_int
         lib.of3d_rel3d.argtypes = [P, i64, P, ctypes.c_int, P]
         lib.of3d_rel3d.restype = ctypes.c_int
         lib.of3d_copy_async.argtypes = [P, P, ctypes.c_size_t, ctypes.c_int, P]

@@ -14,10 +14,36 @@ statistics selected on the GPU, the rest in one fused HIP pass
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import numpy as np
 
 from . import _lib
+
+
+def _linear_ranks(n, percentile, dt):
+    """numpy's 'linear' percentile of n values of dtype dt as two 0-based ranks and a weight:
+    (lo, hi, gamma) with lo <= hi <= n-1 and gamma of dtype dt, numpy's arithmetic in the array's
+    dtype (numpy/lib/_function_base_impl.py: percentile -> _quantile, method 'linear': virtual
+    index (n-1)*q, gamma); the value is _lerp(a, b, gamma) (see _lerp) of the order statistics."""
+    q = np.asanyarray(np.true_divide(percentile, dt.type(100)))
+    vi = (n - 1) * q
+    if vi >= n - 1:
+        lo = hi = n - 1
+    elif vi < 0:
+        lo = hi = 0
+    else:
+        lo = int(np.floor(vi))
+        hi = lo + 1
+    gamma = np.asanyarray(vi - lo, dtype=dt)
+    return lo, hi, gamma
+
+
+def _lerp(a, b, gamma, dt):
+    """numpy's _lerp of two order statistics in the array's dtype."""
+    diff = np.subtract(b, a)
+    res = np.add(a, diff * gamma) if gamma < 0.5 else np.subtract(b, diff * (1 - gamma))
+    return dt.type(res)
 
 
 def percentile_threshold(rel, percentile):
@@ -36,23 +62,10 @@ def percentile_threshold(rel, percentile):
     dt = np.dtype(str(flat.dtype).replace("torch.", ""))
     if bool(torch.isnan(flat).any()):
         return dt.type(np.nan)
-    # numpy's arithmetic, in the array's dtype (numpy/lib/_function_base_impl.py: percentile ->
-    # _quantile, method 'linear': virtual index (n-1)*q, gamma, _lerp)
-    q = np.asanyarray(np.true_divide(percentile, dt.type(100)))
-    vi = (n - 1) * q
-    if vi >= n - 1:
-        lo = hi = n - 1
-    elif vi < 0:
-        lo = hi = 0
-    else:
-        lo = int(np.floor(vi))
-        hi = lo + 1
-    gamma = np.asanyarray(vi - lo, dtype=dt)
+    lo, hi, gamma = _linear_ranks(n, percentile, dt)
     a = dt.type(flat.kthvalue(lo + 1).values.item())
     b = dt.type(flat.kthvalue(hi + 1).values.item()) if hi != lo else a
-    diff = np.subtract(b, a)
-    res = np.add(a, diff * gamma) if gamma < 0.5 else np.subtract(b, diff * (1 - gamma))
-    return dt.type(res)
+    return _lerp(a, b, gamma, dt)
 
 
 def flow_statistics(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, device=None):
@@ -90,3 +103,237 @@ def flow_statistics(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0,
         out = {k: v.cpu().numpy() for k, v in out.items()}
     out["threshold"] = thresh
     return out
+
+
+# ---------------------------------------------------------------------------
+# Device-side frame summaries (csrc/kt_summary.hip): what the reference's figure
+# scripts reduce the saved TIFFs to (plot_figure4_timeTraces.m:82-126,
+# plot_figure3_ROIfigures.m:114-193, plot_FigureS2_dt.m:199-222, notebook cells 4-6)
+# — a reliability percentile, then per ROI the valid count, the mean magnitude, the
+# (magnitude-weighted) circular mean of theta and histograms — computed on the
+# resident fields.  Histograms are plain counts: the magnitude-weighted phi
+# distribution of figure 4 needs floating-point accumulation per bin and is not
+# provided.
+# ---------------------------------------------------------------------------
+QUANTITIES = ("vx", "vy", "vz", "magnitude", "theta", "phi")
+SUMS = ("sum_magnitude", "sum_vx", "sum_vy", "sum_vz", "sum_sin", "sum_cos", "sum_mag_sin", "sum_mag_cos")
+MAX_ROI, MAX_BINS = 16, 256
+_HEAD, _ROI_HEAD = 8, 10  # result words before the boxes / before a box's histograms (include/of3d.h)
+
+
+def _np_dtype(t):
+    return np.dtype(str(t.dtype).replace("torch.", ""))
+
+
+def percentile_threshold_device(rel, percentile, out=None):
+    """``np.percentile(rel, percentile)`` of a CUDA tensor as a 1-element tensor of rel's dtype
+    on rel's device: of3d_quantile (radix select) on the current stream, no host
+    synchronisation — the value is ready for the next kernel on that stream."""
+    import torch
+
+    if not rel.is_cuda or rel.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rel must be a float32 or float64 CUDA tensor")
+    flat = rel.contiguous().reshape(-1)
+    n = flat.numel()
+    if n == 0:
+        raise ValueError("percentile of an empty array")
+    lo, hi, gamma = _linear_ranks(n, percentile, _np_dtype(flat))
+    if out is None:
+        out = torch.empty(1, dtype=flat.dtype, device=flat.device)
+    elif out.dtype != flat.dtype or out.device != flat.device or out.numel() != 1:
+        raise ValueError("out must be one element of rel's dtype on rel's device")
+    lib = _lib.load()
+    f64 = int(flat.dtype == torch.float64)
+    ws = torch.empty(lib.of3d_quantile_workspace_bytes(f64), dtype=torch.uint8, device=flat.device)
+    _lib.check(lib.of3d_quantile(flat.data_ptr(), f64, n, lo, hi, float(gamma), out.data_ptr(), ws.data_ptr(),
+                                 torch.cuda.current_stream(flat.device).cuda_stream))
+    return out
+
+
+@dataclasses.dataclass
+class SummarySpec:
+    """What flow_summary / FlowStream(summary=) / process_flow(summary=) reduce a frame to.
+
+    rois: boxes (z0, z1, y0, y1, x0, x1), half-open, or (y0, y1, x0, x1) in 2D; the whole
+    volume is always ROI 0 and these follow it (at most 15).  bins: quantity name (vx, vy,
+    vz, magnitude, theta, phi) -> ascending bin edges (at most 256 bins),
+    np.histogram(values, bins=edges) semantics.  Scales and percentile as flow_statistics."""
+    rois: list | None = None
+    bins: dict | None = None
+    rel_percentile: float = 90
+    xyscale: float = 1.0
+    zscale: float = 1.0
+    tscale: float = 1.0
+
+    def resolve(self, shape):
+        """Validated (boxes int64 (n_roi, 6), nbins [6], edges [6 arrays or None]) for a volume
+        of `shape` ((nz, ny, nx) or (ny, nx)); ValueError on a bad box or bad edges."""
+        shape = tuple(int(v) for v in shape)
+        if len(shape) not in (2, 3) or min(shape) < 1:
+            raise ValueError(f"summary: volume shape {shape} is not 2D or 3D")
+        ndim = len(shape)
+        dims = shape if ndim == 3 else (1,) + shape
+        if not (0 <= float(self.rel_percentile) <= 100):
+            raise ValueError(f"summary: rel_percentile {self.rel_percentile} outside [0, 100]")
+        boxes = [(0, dims[0], 0, dims[1], 0, dims[2])]
+        for i, r in enumerate(self.rois or ()):
+            r = tuple(r)
+            if len(r) != 2 * ndim:
+                raise ValueError(f"summary: ROI {i + 1} {r} needs {2 * ndim} bounds for a {ndim}D volume")
+            if any(int(v) != v for v in r):
+                raise ValueError(f"summary: ROI {i + 1} {r} has non-integer bounds")
+            r = tuple(int(v) for v in r)
+            r = r if ndim == 3 else (0, 1) + r
+            for a in range(3):
+                if not (0 <= r[2 * a] < r[2 * a + 1] <= dims[a]):
+                    raise ValueError(f"summary: ROI {i + 1} {r} is empty or outside the volume {dims} "
+                                     f"(axis {'zyx'[a]}: need 0 <= {r[2 * a]} < {r[2 * a + 1]} <= {dims[a]})")
+            boxes.append(r)
+        if len(boxes) > MAX_ROI:
+            raise ValueError(f"summary: at most {MAX_ROI - 1} ROIs beside the whole volume, got {len(boxes) - 1}")
+        nbins, edges = [0] * len(QUANTITIES), [None] * len(QUANTITIES)
+        for name, e in (self.bins or {}).items():
+            if name not in QUANTITIES:
+                raise ValueError(f"summary: unknown histogram quantity {name!r} (one of {QUANTITIES})")
+            if ndim == 2 and name in ("vz", "phi"):
+                raise ValueError(f"summary: a {name} histogram needs a 3D volume")
+            e = np.ascontiguousarray(e, dtype=np.float64)
+            if e.ndim != 1 or e.size < 2 or e.size > MAX_BINS + 1:
+                raise ValueError(f"summary: {name} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
+            if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
+                raise ValueError(f"summary: {name} bin edges must be strictly ascending")
+            q = QUANTITIES.index(name)
+            nbins[q], edges[q] = e.size - 1, e
+        return np.array(boxes, dtype=np.int64), nbins, edges
+
+
+class _SummaryCall:
+    """One resolved spec bound to a device: sizes, workspaces and the kernel launches."""
+
+    def __init__(self, spec, shape, rel_dtype, device):
+        import torch
+
+        self.spec, self.shape = spec, tuple(int(v) for v in shape)
+        self.boxes, self.nbins, self.edges = spec.resolve(shape)
+        self.dims = self.shape if len(self.shape) == 3 else (1,) + self.shape
+        lib = self.lib = _lib.load()
+        self.nb_arr = (ctypes.c_int * 6)(*self.nbins)
+        D = ctypes.POINTER(ctypes.c_double)
+        self.edge_arr = (D * 6)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
+        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        self.result_bytes = lib.of3d_flow_summary_result_bytes(len(self.boxes), self.nb_arr)
+        self.rel_f64 = int(rel_dtype == torch.float64)
+        self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
+        self.qws = torch.empty(lib.of3d_quantile_workspace_bytes(self.rel_f64), dtype=torch.uint8, device=device)
+        self.thresh = torch.empty(1, dtype=rel_dtype, device=device)
+        self.n = int(np.prod(self.dims))
+        self.ranks = _linear_ranks(self.n, spec.rel_percentile, np.dtype(str(rel_dtype).replace("torch.", "")))
+
+    def new_result(self, device):
+        import torch
+
+        return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
+
+    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream):
+        """Quantile + summary kernels on `stream` (device pointers; vz 0/None for 2D)."""
+        lo, hi, gamma = self.ranks
+        lib, s = self.lib, self.spec
+        _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), self.thresh.data_ptr(),
+                                     self.qws.data_ptr(), stream or None))
+        _lib.check(lib.of3d_flow_summary(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
+                                         self.thresh.data_ptr(), float(s.xyscale), float(s.zscale), float(s.tscale),
+                                         self.roi_arr, len(self.boxes), self.nb_arr, self.edge_arr, result_ptr,
+                                         self.ws.data_ptr(), stream or None))
+
+    def decode(self, words):
+        """The result words (host int64 array) as flow_summary's dict."""
+        words = np.ascontiguousarray(words, dtype=np.int64)
+        n_roi, ntot = len(self.boxes), sum(self.nbins)
+        body = words[_HEAD:_HEAD + n_roi * (_ROI_HEAD + ntot)].reshape(n_roi, _ROI_HEAD + ntot)
+        rel_dt = np.dtype(np.float64 if self.rel_f64 else np.float32)
+        out = {"threshold": rel_dt.type(words[:1].view(np.float64)[0]), "rois": self.boxes.copy(),
+               "n_valid": body[:, 0].copy(), "n_voxels": body[:, 1].copy()}
+        sums = np.ascontiguousarray(body[:, 2:_ROI_HEAD]).view(np.float64)
+        for i, k in enumerate(SUMS):
+            out[k] = sums[:, i].copy()
+        nv = out["n_valid"].astype(np.float64)
+        nv[nv == 0] = np.nan  # empty box: NaN means, no division warnings
+        out["mean_magnitude"] = out["sum_magnitude"] / nv
+        for k in ("vx", "vy", "vz"):
+            out["mean_" + k] = out["sum_" + k] / nv
+        out["theta_mean"] = np.arctan2(out["sum_sin"] / nv, out["sum_cos"] / nv)
+        out["theta_mean_weighted"] = np.arctan2(out["sum_mag_sin"] / nv, out["sum_mag_cos"] / nv)
+        out["hist"], out["edges"] = {}, {}
+        off = _ROI_HEAD
+        for q, name in enumerate(QUANTITIES):
+            if self.nbins[q]:
+                out["hist"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.uint64)
+                out["edges"][name] = self.edges[q].copy()
+                off += self.nbins[q]
+        return out
+
+
+def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None,
+                 device=None):
+    """One frame reduced on the device to a few kilobytes (one small device->host copy).
+
+    Inputs as flow_statistics (numpy arrays or torch tensors, vz None for 2D).  The masking is
+    flow_statistics' (rel > the rel_percentile-th percentile; zeros -> NaN; physical units); a
+    voxel is valid when its magnitude is not NaN.  Returns a dict of numpy values: threshold,
+    rois (n_roi, 6; ROI 0 is the whole volume, `rois` follow), per ROI n_valid, n_voxels and
+    the raw sums sum_magnitude, sum_vx, sum_vy, sum_vz, sum_sin, sum_cos, sum_mag_sin,
+    sum_mag_cos (sin/cos of theta = atan2(vy, vx)), the derived mean_magnitude, mean_vx/vy/vz,
+    theta_mean = atan2(sum_sin/n, sum_cos/n), theta_mean_weighted (NaN where n_valid == 0), and
+    hist[name] (n_roi, nbins) uint64 with edges[name] for every quantity in `bins`.
+    Bit-reproducible: the same inputs give the same bits on every run."""
+    import torch
+
+    host = isinstance(vx, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    to = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host else a.contiguous()
+    tx, ty, tr = to(vx), to(vy), to(rel)
+    tz = to(vz) if vz is not None else None
+    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
+    if tx.dim() != (3 if tz is not None else 2):
+        raise ValueError("flow_summary needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+    spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale)
+    call = _SummaryCall(spec, tuple(tx.shape), tr.dtype, tx.device)
+    res = call.new_result(tx.device)
+    call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
+                 tx.dtype == torch.float32, res.data_ptr(), torch.cuda.current_stream(tx.device).cuda_stream)
+    return call.decode(res.cpu().numpy())
+
+
+CSV_COLUMNS = ("frame", "roi", "z0", "z1", "y0", "y1", "x0", "x1", "threshold", "n_valid", "n_voxels",
+               "mean_magnitude", "mean_vx", "mean_vy", "mean_vz", "theta_mean", "theta_mean_weighted") + SUMS
+
+
+def write_summaries(prefix, frames, summaries):
+    """<prefix>_summary.csv (one row per frame and ROI; floats as repr, so they read back
+    exactly) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
+    (frames, n_roi, nbins)) from flow_summary dicts of consecutive frames."""
+    with open(prefix + "_summary.csv", "w", newline="") as f:
+        f.write(",".join(CSV_COLUMNS) + "\n")
+        for frame, s in zip(frames, summaries):
+            for r in range(len(s["rois"])):
+                row = [int(frame), r] + [int(v) for v in s["rois"][r]] + [repr(float(s["threshold"]))]
+                row += [int(s["n_valid"][r]), int(s["n_voxels"][r])]
+                row += [repr(float(s[k][r])) for k in CSV_COLUMNS[11:]]
+                f.write(",".join(str(v) for v in row) + "\n")
+    arrays = {"frames": np.asarray(list(frames), dtype=np.int64)}
+    if summaries:
+        for name, e in summaries[0]["edges"].items():
+            arrays["edges_" + name] = e
+            arrays["counts_" + name] = np.stack([s["hist"][name] for s in summaries])
+    np.savez(prefix + "_summary_hist.npz", **arrays)
+
+
+def read_summary_csv(path):
+    """The rows of a <prefix>_summary.csv as a dict of numpy columns (int64 / float64)."""
+    with open(path) as f:
+        cols = f.readline().strip().split(",")
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    ints = set(CSV_COLUMNS[:8]) | {"n_valid", "n_voxels"}
+    return {c: np.array([int(r[i]) if c in ints else float(r[i]) for r in rows],
+                        dtype=np.int64 if c in ints else np.float64) for i, c in enumerate(cols)}

@@ -186,7 +186,7 @@ def _dist_context():
 
 
 def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSig=3, tSig=1, wSig=4,
-                 precision="fp64", matlab_output=False, parallel="auto"):
+                 precision="fp64", matlab_output=False, parallel="auto", summary=None, save_fields=True):
     """Parse a TIFF time lapse, run the flow per output frame, write TIFFs.
 
     Mirrors calc_flow.py:362-625: same checks and messages, the same
@@ -197,6 +197,15 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     matlab_output=True writes what the reference's MATLAB twin writes
     (M/TIFFwrite.m: LZW BigTIFF, float64; rel kept fp64 as pageeig does,
     M/calc_flow3D.m:235-236).
+
+    summary=analysis.SummarySpec: every saved frame is also reduced on the device (reliability
+    percentile, per-ROI valid counts, mean magnitude, circular means of theta, histograms:
+    analysis.flow_summary) and ``<imNameSave>_summary.csv`` (one row per frame and ROI) and
+    ``<imNameSave>_summary_hist.npz`` (edges and (frames, n_roi, nbins) counts per quantity)
+    are written; save_fields=False then downloads and writes no field TIFFs at all.  The
+    stdout lines are the same in every mode.  Single process, device-ring path only: with
+    several ranks, or a window that differs from the temporal taps, a summary raises
+    ValueError.
 
     Several GPUs (one process per GPU, torch.distributed initialised, e.g. by
     ``shard.init_distributed()`` under torchrun): the reference's own parallel axis
@@ -260,6 +269,12 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     NtSlice = math.ceil(NtChunk / 2) - 1
 
     rank, world = _dist_context()
+    if not save_fields and summary is None:
+        raise ValueError("save_fields=False needs a summary")
+    if summary is not None and world > 1:
+        raise ValueError("summary: sharded summaries (several ranks) are not supported")
+    if summary is not None and NtChunk != 2 * math.ceil(3 * tSig) + 1:
+        raise ValueError("summary: needs the device-ring path (6*tSig+1 == 2*ceil(3*tSig)+1)")
     savedir = imDir / ('OpticalFlow3D' if spatialDimensions == 3 else 'OpticalFlow2D')
     savedir.mkdir(exist_ok=True)
     imNameSave = imName.replace('.*', '')
@@ -333,7 +348,7 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
         h0, h1 = frame_blocks(nOut, rank, world) if nOut > 0 else (0, 0)
         if h1 > h0 and NtChunk == 2 * rt + 1:
             _process_stream(load_frame, (h0, h1), NtChunk, NtSlice, spatialDimensions, xyzSig, tSig, wSig, prefix,
-                            names, precision, writer)
+                            names, precision, writer, summary=summary, save_fields=save_fields)
         else:  # window and temporal taps disagree (non-integer 6*tSig+1): one upload per window
             for hh in range(h0, h1):
                 loopStart = datetime.now()
@@ -380,12 +395,14 @@ class _Shape:
 
 
 def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig, wSig, prefix, names,
-                    precision="fp64", write_fn=None):
+                    precision="fp64", write_fn=None, summary=None, save_fields=True):
     """process_flow's loop on a device-resident frame ring (stream.py): one
     frame read + upload per output frame; compute, download and TIFF writing
     of consecutive frames overlap.  Files and stdout lines are the reference's
     (both lines of a frame are printed once its files are written).
-    out_range = (h0, h1): the windows starting at frames h0 .. h1 - 1 (a rank's block)."""
+    out_range = (h0, h1): the windows starting at frames h0 .. h1 - 1 (a rank's block).
+    summary (a SummarySpec): each frame's device-side summary is collected and written as
+    <prefix>_summary.csv / _summary_hist.npz at the end; save_fields=False: no TIFFs."""
     from concurrent.futures import ThreadPoolExecutor
 
     from .stream import FlowStream, Writer
@@ -397,12 +414,17 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
         _check_args(_Shape((NtChunk,) + first.shape), ndim + 1, tSig, MSG_NDIM_3D if ndim == 3 else MSG_NDIM_2D)
     dt = first.dtype.newbyteorder('=') if first.dtype.byteorder not in ('=', '|') else first.dtype
     fs = FlowStream(ndim, first.shape, dt, xyzSig, tSig, wSig, precision=precision,
-                    rel_fp64=write_fn is not None and ndim == 3)
+                    rel_fp64=write_fn is not None and ndim == 3, summary=summary, fields=save_fields)
+    frames, summaries = [], []
 
     def finish(frame, start, start_str, pending):
         print(start_str + ' - Processing frame ' + str(frame) + '...')
         try:
-            _write_frame(prefix, names, frame, pending.result(), pool, write_fn)
+            if summary is not None:
+                frames.append(frame)
+                summaries.append(pending.summary())
+            if save_fields:
+                _write_frame(prefix, names, frame, pending.result(), pool, write_fn)
         finally:
             pending.release()
         print(_now() + ' - Frame ' + str(frame) + ' saved.  Duration: ' + str(datetime.now() - start))
@@ -425,6 +447,10 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
         writer.close()
         pool.shutdown()
         fs.close()
+    if summary is not None:
+        from .analysis import write_summaries
+
+        write_summaries(prefix, frames, summaries)
 
 
 def _process_slab(load_part, axis, vol, nOut, NtChunk, NtSlice, xyzSig, tSig, wSig, prefix, names, precision,

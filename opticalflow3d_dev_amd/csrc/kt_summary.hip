@@ -1,0 +1,540 @@
+// kt_summary.hip — device-side frame summaries (no reference kernel counterpart: the reference
+// reduces its saved TIFFs on the host, example_analysis_script.ipynb cells 4-6 and the figure
+// scripts): an exact order-statistic select (of3d_quantile) and the masked ROI sums and
+// histograms of one frame (of3d_flow_summary).  Both are stream-ordered end to end: nothing
+// returns to the host, the threshold stays in device memory between the two.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "../../include/of3d.h"
+#include "kernels.hpp"
+
+namespace {
+
+using u64 = unsigned long long;
+
+#define SUM_HIP(call)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+
+// ---------------------------------------------------------------------------
+// Radix select.  key(v): the order-preserving unsigned image of the float bits (sign bit set:
+// all bits flipped, else the sign bit set); -0.0 takes +0.0's key.  11-bit digits from the top:
+// float32 11 + 11 + 10 bits (3 passes), float64 5 x 11 + 9 bits (6 passes).  Both ranks are
+// narrowed at once: each carries its own key prefix and remaining rank; while the prefixes
+// agree one histogram serves both.
+// ---------------------------------------------------------------------------
+constexpr int kDigit = 11, kBins = 1 << kDigit;
+constexpr int kSelThreads = 256;
+constexpr int kMaxPasses = 6;
+
+// workspace: state, then one histogram pair per pass (zeroed once per call)
+struct SelState {
+    u64 prefix[2];
+    u64 rank[2];
+    u64 n_nan;
+    u64 pad[3];
+};
+constexpr size_t kSelHistWords = (size_t)kMaxPasses * 2 * kBins;
+constexpr size_t kSelBytes = sizeof(SelState) + kSelHistWords * sizeof(u64);
+
+template <typename T>
+struct KeyOf;
+template <>
+struct KeyOf<float> {
+    static constexpr int bits = 32, passes = 3;
+    static __device__ __forceinline__ u64 key(float v) {
+        unsigned u = __float_as_uint(v);
+        if ((u << 1) == 0) u = 0;  // -0.0 -> +0.0
+        return (u & 0x80000000u) ? (unsigned)~u : (u | 0x80000000u);
+    }
+    static __device__ __forceinline__ float value(u64 k) {
+        const unsigned u = (unsigned)k;
+        return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+    }
+};
+template <>
+struct KeyOf<double> {
+    static constexpr int bits = 64, passes = 6;
+    static __device__ __forceinline__ u64 key(double v) {
+        u64 u = (u64)__double_as_longlong(v);
+        if ((u << 1) == 0) u = 0;
+        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    }
+    static __device__ __forceinline__ double value(u64 k) {
+        return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+    }
+};
+
+// digit p of a `bits`-wide key: [shift, shift + width)
+__host__ __device__ constexpr int digit_shift(int bits, int p) {
+    return bits - (p + 1) * kDigit > 0 ? bits - (p + 1) * kDigit : 0;
+}
+__host__ __device__ constexpr int digit_width(int bits, int p) {
+    return bits - (p + 1) * kDigit >= 0 ? kDigit : bits - p * kDigit;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSelThreads) void k_sel_hist(const T* __restrict__ a, size_t n, int pass,
+                                                          SelState* __restrict__ st, u64* __restrict__ hist) {
+    __shared__ unsigned h[2][kBins];
+    __shared__ unsigned nan_s;
+    for (int i = threadIdx.x; i < 2 * kBins; i += kSelThreads) (&h[0][0])[i] = 0;
+    if (threadIdx.x == 0) nan_s = 0;
+    __syncthreads();
+    constexpr int bits = KeyOf<T>::bits;
+    const int shift = digit_shift(bits, pass), width = digit_width(bits, pass);
+    const unsigned mask = (1u << width) - 1;
+    const int up = shift + width;  // the bits above the digit are the prefix (none in pass 0)
+    const u64 p0 = pass ? st->prefix[0] >> up : 0, p1 = pass ? st->prefix[1] >> up : 0;
+    const bool two = p0 != p1;
+    unsigned nans = 0;
+    auto count = [&](T v) {
+        const u64 k = KeyOf<T>::key(v);
+        const u64 top = pass ? k >> up : 0;
+        const unsigned d = (unsigned)(k >> shift) & mask;
+        if (top == p0) atomicAdd(&h[0][d], 1u);
+        if (two && top == p1) atomicAdd(&h[1][d], 1u);
+        nans += v != v;
+    };
+    // 16-byte loads over the aligned middle of the array, element loads for its head and tail
+    constexpr int V = 16 / (int)sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    const size_t mis = ((uintptr_t)a % 16) / sizeof(T);
+    const size_t head = mis ? (V - mis < n ? V - mis : n) : 0;
+    const size_t nvec = (n - head) / V;
+    const vec_t* av = reinterpret_cast<const vec_t*>(a + head);
+    const size_t stride = (size_t)gridDim.x * kSelThreads, first = (size_t)blockIdx.x * kSelThreads + threadIdx.x;
+    for (size_t i = first; i < nvec; i += stride) {
+        const vec_t v = av[i];
+#pragma unroll
+        for (int j = 0; j < V; ++j) count(v[j]);
+    }
+    const size_t rest = n - head - nvec * V;  // < V
+    if (first < head) count(a[first]);
+    if (first >= head && first < head + rest) count(a[head + nvec * V + (first - head)]);
+    if (pass == 0 && nans) atomicAdd(&nan_s, nans);
+    __syncthreads();
+    u64* g = hist + (size_t)pass * 2 * kBins;
+    for (int i = threadIdx.x; i < 2 * kBins; i += kSelThreads) {
+        const unsigned c = (&h[0][0])[i];
+        if (c) atomicAdd(&g[i], (u64)c);
+    }
+    if (pass == 0 && threadIdx.x == 0 && nan_s) atomicAdd(&st->n_nan, (u64)nan_s);
+}
+
+// One workgroup: the bin holding each rank, the narrowed prefix and the rank within the bin;
+// after the last pass the prefixes are the two order statistics' keys -> the interpolation.
+template <typename T>
+__global__ __launch_bounds__(kSelThreads) void k_sel_pick(int pass, SelState* __restrict__ st,
+                                                          const u64* __restrict__ hist, double gamma,
+                                                          T* __restrict__ out) {
+    constexpr int per = kBins / kSelThreads;
+    constexpr int bits = KeyOf<T>::bits;
+    __shared__ u64 part[kSelThreads];
+    __shared__ u64 res[2][2];
+    const int shift = digit_shift(bits, pass), width = digit_width(bits, pass);
+    const int up = shift + width;
+    const bool two = pass && (st->prefix[0] >> up) != (st->prefix[1] >> up);
+    const u64* g = hist + (size_t)pass * 2 * kBins;
+    for (int r = 0; r < 2; ++r) {
+        const u64* hr = g + ((r && two) ? kBins : 0);
+        const u64 rank = st->rank[r];
+        u64 c[per], s = 0;
+        for (int j = 0; j < per; ++j) {
+            c[j] = hr[threadIdx.x * per + j];
+            s += c[j];
+        }
+        part[threadIdx.x] = s;
+        __syncthreads();
+        for (int off = 1; off < kSelThreads; off <<= 1) {  // inclusive scan of the threads' counts
+            const u64 v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+            __syncthreads();
+            part[threadIdx.x] += v;
+            __syncthreads();
+        }
+        u64 before = part[threadIdx.x] - s;
+        for (int j = 0; j < per; ++j) {
+            if (rank >= before && rank < before + c[j]) {
+                res[r][0] = (u64)(threadIdx.x * per + j);
+                res[r][1] = rank - before;
+            }
+            before += c[j];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        u64 pf[2];
+        for (int r = 0; r < 2; ++r) {
+            pf[r] = st->prefix[r] | (res[r][0] << shift);
+            st->prefix[r] = pf[r];
+            st->rank[r] = res[r][1];
+        }
+        if (pass == KeyOf<T>::passes - 1) {
+            // numpy's _lerp in the array's dtype (method 'linear')
+            const T a = KeyOf<T>::value(pf[0]), b = KeyOf<T>::value(pf[1]);
+            const T g1 = (T)gamma;
+            // lo == hi: b == a and the same expression gives a — or NaN for an infinite a, as numpy's
+            const T diff = b - a;
+            T v = g1 < (T)0.5 ? a + diff * g1 : b - diff * ((T)1 - g1);
+            if (st->n_nan) v = (T)__builtin_nan("");
+            *out = v;
+        }
+    }
+}
+
+__global__ void k_sel_init(SelState* st, u64 lo, u64 hi) {
+    st->prefix[0] = st->prefix[1] = 0;
+    st->rank[0] = lo;
+    st->rank[1] = hi;
+}
+
+template <typename T>
+int quantile_launch(const void* a, int64_t n, int64_t lo, int64_t hi, double gamma, void* out, void* ws,
+                    hipStream_t s) {
+    SelState* st = (SelState*)ws;
+    u64* hist = (u64*)((char*)ws + sizeof(SelState));
+    SUM_HIP(hipMemsetAsync(ws, 0, kSelBytes, s));
+    hipLaunchKernelGGL(k_sel_init, dim3(1), dim3(1), 0, s, st, (u64)lo, (u64)hi);
+    // 16 elements per thread and pass at least; at most 2048 workgroups
+    const int64_t want = (n + (int64_t)kSelThreads * 16 - 1) / ((int64_t)kSelThreads * 16);
+    const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
+    for (int p = 0; p < KeyOf<T>::passes; ++p) {
+        hipLaunchKernelGGL(k_sel_hist<T>, dim3(blocks), dim3(kSelThreads), 0, s, (const T*)a, (size_t)n, p, st, hist);
+        hipLaunchKernelGGL(k_sel_pick<T>, dim3(1), dim3(kSelThreads), 0, s, p, st, (const u64*)hist, gamma,
+                           (T*)out);
+    }
+    SUM_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Frame summary.  Grid (kSumMaxBlocks, n_roi); workgroup b of a box walks rows
+// [b*R/nb, (b+1)*R/nb) of the box's R = dz*dy rows, nb = a function of the box size alone.
+// Per voxel k_flow_stats' arithmetic (of3d_dev.hpp); sums in registers, a fixed shuffle tree
+// over the lanes, the waves' partials added in wave order, one workspace slot per workgroup;
+// k_sum_final adds a box's slots in index order.  Counts and histograms: LDS integer atomics,
+// then 64-bit integer atomics into the (zeroed) result.  No floating-point atomics: the same
+// inputs give the same bits on every run, and a box's row does not depend on the other boxes.
+// ---------------------------------------------------------------------------
+constexpr int kSumThreads = 512, kSumWaves = kSumThreads / 64;
+constexpr int kSumMaxBlocks = 1024;        // workgroups (workspace slots) per box at most
+constexpr int64_t kSumVoxPerBlock = 8192;  // a workgroup's share of a box at least
+constexpr int kNSum = 8;                   // mag x y z sin cos mag*sin mag*cos
+constexpr int kNQ = OF3D_SUMMARY_QUANTITIES;
+constexpr int kMaxBins = OF3D_SUMMARY_MAX_BINS, kMaxRoi = OF3D_SUMMARY_MAX_ROI;
+constexpr int kHead = 8, kRoiHead = 2 + kNSum;  // result words before the boxes / before a box's histograms
+constexpr size_t kSumSlotBytes = (size_t)kMaxRoi * kSumMaxBlocks * kNSum * sizeof(double);
+constexpr size_t kEdgeWords = (size_t)kNQ * (kMaxBins + 1);
+constexpr size_t kSumWsBytes = kSumSlotBytes + kEdgeWords * sizeof(double);
+constexpr int kEdgeChunk = 384;  // edges carried by one k_put_edges launch (kernel arguments)
+
+struct SumParams {
+    int nz, ny, nx, n_roi;
+    int box[kMaxRoi][6];  // z0 z1 y0 y1 x0 x1
+    int nb[kMaxRoi];      // workgroups of the box
+    int nbins[kNQ];
+    int eoff[kNQ];  // first edge of the quantity in the workspace's edge array
+    int hoff[kNQ];  // first bin of the quantity in a box's histogram words
+    int roi_words;  // result words per box
+    double sxy, sz, st;
+};
+
+struct EdgeChunk {
+    double e[kEdgeChunk];
+};
+
+// the edges travel as kernel arguments: stream-ordered, no host copy to wait for
+__global__ void k_put_edges(double* __restrict__ dst, EdgeChunk c, int n) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
+}
+
+// np.histogram(v, bins=e): e[i] <= v < e[i+1], the last bin closed; -1: dropped (outside, NaN)
+__device__ __forceinline__ int find_bin(const double* e, int nb, double v) {
+    if (!(v >= e[0] && v <= e[nb])) return -1;
+    int lo = 0, hi = nb;  // e[lo] <= v, and v < e[hi] or hi == nb
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (v >= e[mid])
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+template <typename VT, typename RelT>
+__global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict__ vx, const VT* __restrict__ vy,
+                                                           const VT* __restrict__ vz, const RelT* __restrict__ rel,
+                                                           const RelT* __restrict__ thr_p, SumParams P,
+                                                           const double* __restrict__ edges_g,
+                                                           double* __restrict__ slots, u64* __restrict__ result) {
+    const int roi = blockIdx.y, nb = P.nb[roi];
+    if ((int)blockIdx.x >= nb) return;
+    __shared__ double edges[kEdgeWords];
+    __shared__ unsigned hist[kNQ * kMaxBins];
+    __shared__ unsigned nvalid_s;
+    __shared__ double wsum[kSumWaves][kNSum];
+    int ntot = 0, ne = 0;
+    for (int q = 0; q < kNQ; ++q) {
+        ntot += P.nbins[q];
+        ne += P.nbins[q] ? P.nbins[q] + 1 : 0;
+    }
+    for (int i = threadIdx.x; i < ne; i += kSumThreads) edges[i] = edges_g[i];
+    for (int i = threadIdx.x; i < ntot; i += kSumThreads) hist[i] = 0;
+    if (threadIdx.x == 0) nvalid_s = 0;
+    __syncthreads();
+
+    const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
+    const unsigned dy = P.box[roi][3] - y0, dx = P.box[roi][5] - x0;
+    const long long R = (long long)(P.box[roi][1] - z0) * dy;
+    const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
+    const long long count = (r1 - r0) * dx;  // this workgroup's voxels (< 2^31: checked on the host)
+    // this thread's voxel as (z, y, x) inside the box, advanced by kSumThreads voxels per step
+    // without divisions: x by step % dx with a carry into the row, the row by step / dx
+    const unsigned step_x = kSumThreads % dx, step_r = kSumThreads / dx;
+    const unsigned step_y = step_r % dy, step_z = step_r / dy;
+    unsigned x = threadIdx.x % dx;
+    const long long row = r0 + threadIdx.x / dx;
+    unsigned y = (unsigned)(row % dy), z = (unsigned)(row / dy);
+    const double thr = (double)*thr_p;
+    const double qnan = __builtin_nan("");
+    const bool is3 = vz != nullptr;
+    double acc[kNSum] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned nvalid = 0;
+
+    constexpr int U = 4;
+    for (long long e = threadIdx.x; e < count; e += (long long)U * kSumThreads) {
+        double fx[U], fy[U], fz[U], fr[U];
+        bool in[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            in[u] = e + (long long)u * kSumThreads < count;
+            fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
+            if (in[u]) {
+                const size_t i = ((size_t)(z0 + z) * P.ny + (y0 + y)) * P.nx + (x0 + x);
+                fr[u] = (double)rel[i];
+                fx[u] = (double)vx[i];
+                fy[u] = (double)vy[i];
+                if (is3) fz[u] = (double)vz[i];
+            }
+            x += step_x;
+            unsigned c = x >= dx;
+            x -= c ? dx : 0;
+            y += step_y + c;
+            c = y >= dy;
+            y -= c ? dy : 0;
+            z += step_z + c;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!in[u]) continue;
+            const double m = (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
+            auto fix = [&](double v, double scale) {
+                v = v * m;
+                if (v == 0.0) v = qnan;
+                return (v * scale) / P.st;
+            };
+            const double vxp = fix(fx[u], P.sxy), vyp = fix(fy[u], P.sxy);
+            const double vzp = is3 ? fix(fz[u], P.sz) : 0.0;
+            const double xy2 = vxp * vxp + vyp * vyp;
+            const double mag = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
+            if (mag != mag) continue;  // badRows = isnan(mag)
+            const double h = sqrt(xy2);
+            const double sn = vyp / h, cs = vxp / h;
+            ++nvalid;
+            acc[0] += mag;
+            acc[1] += vxp;
+            acc[2] += vyp;
+            acc[3] += vzp;
+            acc[4] += sn;
+            acc[5] += cs;
+            acc[6] += mag * sn;
+            acc[7] += mag * cs;
+            auto put = [&](int q, double v) {
+                const int b = find_bin(edges + P.eoff[q], P.nbins[q], v);
+                if (b >= 0) atomicAdd(&hist[P.hoff[q] + b], 1u);
+            };
+            if (P.nbins[0]) put(0, vxp);
+            if (P.nbins[1]) put(1, vyp);
+            if (P.nbins[2]) put(2, vzp);
+            if (P.nbins[3]) put(3, mag);
+            if (P.nbins[4]) put(4, atan2(vyp, vxp));
+            if (P.nbins[5]) put(5, atan(vzp / h));
+        }
+    }
+
+    // lanes: a fixed shuffle tree; waves: wave 0 adds the partials in wave order
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < kNSum; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) wsum[wave][q] = v;
+    }
+    if (nvalid) atomicAdd(&nvalid_s, nvalid);
+    __syncthreads();
+    if (threadIdx.x < kNSum) {
+        double v = wsum[0][threadIdx.x];
+        for (int w = 1; w < kSumWaves; ++w) v += wsum[w][threadIdx.x];
+        slots[((size_t)roi * kSumMaxBlocks + blockIdx.x) * kNSum + threadIdx.x] = v;
+    }
+    u64* rr = result + kHead + (size_t)roi * P.roi_words;
+    if (threadIdx.x == 0 && nvalid_s) atomicAdd(&rr[0], (u64)nvalid_s);
+    for (int i = threadIdx.x; i < ntot; i += kSumThreads)
+        if (hist[i]) atomicAdd(&rr[kRoiHead + i], (u64)hist[i]);
+}
+
+// One workgroup per box: its slots staged in LDS, then added in index order.
+template <typename RelT>
+__global__ __launch_bounds__(256) void k_sum_final(const double* __restrict__ slots, const RelT* __restrict__ thr_p,
+                                                   SumParams P, u64* __restrict__ result) {
+    __shared__ double s[kSumMaxBlocks * kNSum];
+    const int roi = blockIdx.x, nb = P.nb[roi];
+    for (int i = threadIdx.x; i < nb * kNSum; i += 256) s[i] = slots[(size_t)roi * kSumMaxBlocks * kNSum + i];
+    __syncthreads();
+    u64* rr = result + kHead + (size_t)roi * P.roi_words;
+    if (threadIdx.x < kNSum) {
+        double v = s[threadIdx.x];
+        for (int b = 1; b < nb; ++b) v += s[b * kNSum + threadIdx.x];
+        rr[2 + threadIdx.x] = (u64)__double_as_longlong(v);
+    }
+    if (threadIdx.x == 0) {
+        const int* bx = P.box[roi];
+        rr[1] = (u64)((long long)(bx[1] - bx[0]) * (bx[3] - bx[2]) * (bx[5] - bx[4]));
+        if (roi == 0) {
+            result[0] = (u64)__double_as_longlong((double)*thr_p);
+            result[1] = (u64)P.n_roi;
+            for (int q = 0; q < kNQ; ++q) result[2 + q] = (u64)P.nbins[q];
+        }
+    }
+}
+
+int roi_words(const int* nbins) {
+    int w = kRoiHead;
+    for (int q = 0; q < kNQ; ++q) w += nbins[q];
+    return w;
+}
+
+bool bins_ok(const int* nbins) {
+    if (!nbins) return false;
+    for (int q = 0; q < kNQ; ++q)
+        if (nbins[q] < 0 || nbins[q] > kMaxBins) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t of3d_quantile_workspace_bytes(int is_f64) {
+    (void)is_f64;
+    return kSelBytes;
+}
+
+int of3d_quantile(const void* a, int is_f64, int64_t n, int64_t lo, int64_t hi, double gamma, void* out,
+                  void* workspace, void* stream) {
+    if (!a || !out || !workspace) return of3dk::set_error("of3d: null argument");
+    if (n < 1) return of3dk::set_error("of3d: quantile of an empty array");
+    if (lo < 0 || lo > hi || hi > n - 1) return of3dk::set_error("of3d: quantile ranks must satisfy 0 <= lo <= hi <= n-1");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return of3dk::set_error("of3d: quantile gamma must lie in [0, 1]");
+    hipStream_t s = (hipStream_t)stream;
+    return is_f64 ? quantile_launch<double>(a, n, lo, hi, gamma, out, workspace, s)
+                  : quantile_launch<float>(a, n, lo, hi, gamma, out, workspace, s);
+}
+
+size_t of3d_flow_summary_result_bytes(int n_roi, const int* nbins) {
+    if (n_roi < 1 || n_roi > kMaxRoi || !bins_ok(nbins)) return 0;
+    return ((size_t)kHead + (size_t)n_roi * roi_words(nbins)) * 8;
+}
+
+size_t of3d_flow_summary_workspace_bytes(void) { return kSumWsBytes; }
+
+int of3d_flow_summary(const void* vx, const void* vy, const void* vz, const void* rel, int v_f32, int rel_f64,
+                      int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                      double tscale, const int64_t* rois, int n_roi, const int* nbins, const double* const* edges,
+                      void* d_result, void* workspace, void* stream) {
+    if (!vx || !vy || !rel || !d_thresh || !rois || !d_result || !workspace)
+        return of3dk::set_error("of3d: null argument");
+    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
+        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
+    if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (n_roi < 1 || n_roi > kMaxRoi) return of3dk::set_error("of3d: 1 to 16 ROI boxes");
+    if (!bins_ok(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
+    if (!vz && (nbins[2] || nbins[5])) return of3dk::set_error("of3d: vz and phi histograms need a 3D volume");
+    SumParams P;
+    memset(&P, 0, sizeof(P));
+    P.nz = (int)nz, P.ny = (int)ny, P.nx = (int)nx, P.n_roi = n_roi;
+    P.sxy = xyscale, P.sz = zscale, P.st = tscale;
+    const int64_t dims[3] = {nz, ny, nx};
+    int max_nb = 1;
+    for (int r = 0; r < n_roi; ++r) {
+        int64_t vox = 1;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
+            if (b0 < 0 || b0 >= b1 || b1 > dims[a])
+                return of3dk::set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
+            P.box[r][2 * a] = (int)b0, P.box[r][2 * a + 1] = (int)b1;
+            vox *= b1 - b0;
+        }
+        // a function of the box alone (never of the device): the summation order is fixed
+        const int64_t rows = (rois[r * 6 + 1] - rois[r * 6]) * (rois[r * 6 + 3] - rois[r * 6 + 2]);
+        int64_t nb = (vox + kSumVoxPerBlock - 1) / kSumVoxPerBlock;
+        nb = nb > kSumMaxBlocks ? kSumMaxBlocks : nb;
+        nb = nb > rows ? rows : nb;
+        // a workgroup's share: at most ceil(rows / nb) rows
+        if (((rows + nb - 1) / nb) * (rois[r * 6 + 5] - rois[r * 6 + 4]) >= ((int64_t)1 << 31) - 4 * kSumThreads)
+            return of3dk::set_error("of3d: ROI too large (2^31 voxels per workgroup)");
+        P.nb[r] = (int)nb;
+        max_nb = nb > max_nb ? (int)nb : max_nb;
+    }
+    int eo = 0, ho = 0;
+    double host_edges[kEdgeWords];
+    for (int q = 0; q < kNQ; ++q) {
+        P.nbins[q] = nbins[q], P.eoff[q] = eo, P.hoff[q] = ho;
+        if (!nbins[q]) continue;
+        if (!edges || !edges[q]) return of3dk::set_error("of3d: bins requested without edges");
+        for (int i = 0; i <= nbins[q]; ++i) {
+            const double e = edges[q][i];
+            if (!(e == e) || (i && !(e > edges[q][i - 1])))
+                return of3dk::set_error("of3d: bin edges must ascend strictly and hold no NaN");
+            host_edges[eo + i] = e;
+        }
+        eo += nbins[q] + 1, ho += nbins[q];
+    }
+    P.roi_words = roi_words(nbins);
+    hipStream_t s = (hipStream_t)stream;
+    double* slots = (double*)workspace;
+    double* d_edges = (double*)((char*)workspace + kSumSlotBytes);
+    SUM_HIP(hipMemsetAsync(d_result, 0, of3d_flow_summary_result_bytes(n_roi, nbins), s));
+    for (int o = 0; o < eo; o += kEdgeChunk) {
+        EdgeChunk c;
+        const int cnt = eo - o < kEdgeChunk ? eo - o : kEdgeChunk;
+        memcpy(c.e, host_edges + o, sizeof(double) * cnt);
+        hipLaunchKernelGGL(k_put_edges, dim3(1), dim3(kEdgeChunk), 0, s, d_edges + o, c, cnt);
+    }
+    auto launch = [&](auto vt, auto rt) {
+        using VT = decltype(vt);
+        using RT = decltype(rt);
+        hipLaunchKernelGGL((k_sum_boxes<VT, RT>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s, (const VT*)vx,
+                           (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, P,
+                           (const double*)d_edges, slots, (u64*)d_result);
+        hipLaunchKernelGGL(k_sum_final<RT>, dim3(n_roi), dim3(256), 0, s, (const double*)slots, (const RT*)d_thresh,
+                           P, (u64*)d_result);
+    };
+    if (v_f32)
+        rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
+    else
+        rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
+    SUM_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -1544,6 +1544,9 @@ __global__ __launch_bounds__(256) void k_copy_bytes(const unsigned char* __restr
 // ---------------------------------------------------------------------------
 // C-ABI
 // ---------------------------------------------------------------------------
+// of3d_last_error's message, set from the other translation units (kt_summary.hip)
+int of3dk::set_error(const char* msg) { return fail(msg); }
+
 extern "C" {
 
 int of3d_version(void) { return OF3D_VERSION; }

@@ -49,11 +49,21 @@ class FlowStream:
     2*rt+1 resident frames; the oldest is then retired) and returns a Pending whose
     .result() gives host arrays (vx, vy, [vz,] rel); .release() hands the buffer set
     back (at most `depth` frames in flight).  With lookahead, push one frame more than
-    the window before submit() to pipeline the next window's temporal derivative."""
+    the window before submit() to pipeline the next window's temporal derivative.
+    summary=SummarySpec: the frame is also reduced on the device (.summary() gives
+    analysis.flow_summary's dict); fields=False: only that, no field downloads."""
 
     def __init__(self, ndim, vol_shape, dtype, xyzSig, tSig, wSig, device=None, depth=3, d2h="dma",
-                 d2h_blocks=64, precision="fp64", rel_fp64=False, zslab=None, lookahead=None, k0_batch=None):
-        """zslab=(rank, world, group[, axis]): this process holds one slab of every frame (3D
+                 d2h_blocks=64, precision="fp64", rel_fp64=False, zslab=None, lookahead=None, k0_batch=None,
+                 summary=None, fields=True):
+        """summary=analysis.SummarySpec: submit() enqueues the percentile select and the summary
+        kernels (csrc/kt_summary.hip) on the compute stream right after the plan's kernels, on the
+        device outputs of that buffer set, and the copy of the few-kilobyte result to a pinned
+        slot of the set; Pending.summary() returns analysis.flow_summary's dict.  fields=False
+        (needs a summary): the fields are never downloaded, their pinned host buffers are not
+        allocated and Pending.result() raises.  Whole-volume streams only (no zslab).
+
+        zslab=(rank, world, group[, axis]): this process holds one slab of every frame (3D
         only) — axis 0 (default): output planes shard.zslab_bounds(nz, rank, world); axis 1:
         rows zslab_bounds(ny, rank, world) of every plane.  push() then takes the rank's own
         part ((z1 - z0, ny, nx) or (nz, y1 - y0, nx)) and fetches the frame's rd + rw halo
@@ -77,6 +87,11 @@ class FlowStream:
 
         self.torch = torch
         self.ndim = ndim
+        if summary is not None and zslab is not None:
+            raise ValueError("FlowStream: summaries of slab streams are not supported (whole volumes only)")
+        if not fields and summary is None:
+            raise ValueError("FlowStream: fields=False needs a summary")
+        self.fields = bool(fields)
         self.device = _lib.device_index() if device is None else device
         self.dev = torch.device("cuda", self.device)
         dt = np.dtype(dtype)
@@ -198,7 +213,15 @@ class FlowStream:
                                             pin_memory=pin) for _ in range(nout - 1)] + \
                                [torch.empty(n, dtype=rel_t, device=None if pin else self.dev, pin_memory=pin)]
         self.dout = [mk(False) for _ in range(depth)]
-        self.hout = [mk(True) for _ in range(depth)]
+        self.hout = [mk(True) if self.fields else None for _ in range(depth)]
+        self.summary = None
+        if summary is not None:
+            from .analysis import _SummaryCall
+
+            self.summary = _SummaryCall(summary, self.shape, rel_t, self.dev)
+            self.dsum = [self.summary.new_result(self.dev) for _ in range(depth)]
+            self.hsum = [torch.empty(self.summary.result_bytes // 8, dtype=torch.int64, pin_memory=True)
+                         for _ in range(depth)]
         # row slabs without row ranges: the plan writes all rows of its sub-volume here; the own
         # rows are copied out
         self.dfull = mk(False, max(self.nblock, 1)) if self.axis == 1 and not self.rows_direct else None
@@ -325,12 +348,24 @@ class FlowStream:
             with torch.cuda.stream(self.comp):
                 for d, f in zip(dout, full):
                     d[:self.nvox].view(self.shape).copy_(self._rows(f)[:, self.y0 - self.yi0:self.y1 - self.yi0])
+        pending = Pending(self, b)
+        if self.summary is not None:
+            # on the compute stream: behind this frame's kernels and ahead of every later frame's,
+            # so a later submit() that reuses this set's device outputs (after its release()) is
+            # ordered behind these reads by the stream itself
+            self.summary.enqueue(dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(),
+                                 self.precision == "fp32", self.dsum[b].data_ptr(), self.comp.cuda_stream)
+            with torch.cuda.stream(self.comp):
+                self.hsum[b].copy_(self.dsum[b], non_blocking=True)
+                pending.sum_event = torch.cuda.Event()
+                pending.sum_event.record(self.comp)
         cev = torch.cuda.Event()
         cev.record(self.comp)
         for s in self.order[:self.nwin + self.L]:  # the window and (lookahead) the next frame
             self.slot_evt[s] = cev
         self.free.append(self.order.pop(0))  # the window's oldest frame is done with (after cev)
-        pending = Pending(self, b)
+        if not self.fields:
+            return pending
         if self.d2h_mode == "dma":
             self.dl_q.put((cev, hout, dout, pending))
             return pending
@@ -385,9 +420,19 @@ class Pending:
         self.event = None               # D2H on a stream: completion event
         self.done = threading.Event()   # D2H by the download thread
         self.error = None
+        self.sum_event = None           # summary kernels + the copy of their result
+
+    def summary(self):
+        """analysis.flow_summary's dict of this frame (streams created with summary=)."""
+        if self.sum_event is None:
+            raise RuntimeError("FlowStream was created without a summary")
+        self.sum_event.synchronize()
+        return self.fs.summary.decode(self.fs.hsum[self.b].numpy().copy())
 
     def result(self):
         """Host arrays: views of pinned buffers, valid until release()."""
+        if not self.fs.fields:
+            raise RuntimeError("FlowStream(fields=False) downloads no fields: use summary()")
         if self.event is not None:
             self.event.synchronize()
         else:
