@@ -307,6 +307,46 @@ int of3d_flow_summary(const void* d_vx, const void* d_vy, const void* d_vz, cons
                       double zscale, double tscale, const int64_t* rois, int n_roi, const int* nbins,
                       const double* const* edges, void* d_result, void* workspace, void* stream);
 
+/* Area opening of the reliability mask on the device: MATLAB's
+ *   relMask = rel > relThresh;  relMask = bwareaopen(relMask, minSize);
+ * of the reference's figure scripts (plot_figure4_timeTraces.m:75-79, plot_figure4_Movies.m:93-94,
+ * plot_figure5.m:87-88, plot_figure5_Movie.m:88-89; plot_figure3_ROIfigures.m:96 and
+ * plot_figure3_ChannelCompare.m:140 with 10^5), applied to each cropped ROI as
+ * plot_figure4_timeTraces.m:72-79 does.  d_rel: (nz, ny, nx) float32 (float64 with rel_f64),
+ * 2D = nz 1; d_thresh: one device element of rel's dtype (of3d_quantile's output); rois as
+ * of3d_flow_summary's; min_size >= 1; connectivity 6, 18 or 26 for nz > 1, 4 or 8 for nz == 1
+ * (bwareaopen's defaults are 26 and 8).  For every box r independently:
+ *   1. M_r = (rel > *d_thresh) restricted to the box (a NaN on either side gives false);
+ *   2. the connected components of M_r inside the box (neighbours outside it connect nothing);
+ *   3. keep_r = the union of the components with at least min_size voxels.
+ * d_keep: one uint16 per voxel of the whole volume; bit r is set where the voxel lies in box r
+ * and in keep_r, every other bit is 0 (boxes may overlap, a voxel's bits may differ).
+ * d_counts: int64[n_roi][4] = n_mask (voxels of M_r), n_components, n_components_kept, n_kept
+ * (voxels of keep_r).  min_size 1 keeps every mask voxel.
+ * Union-find over box-local uint32 labels, one launch per phase and box (initial labels with
+ * the x-runs of a wave pre-merged, unions with the backward neighbours by find + atomicMin,
+ * path compression, component sizes by integer atomics, the keep bits): every component is
+ * rooted at its smallest linear index, so all outputs are integers fixed by the input alone —
+ * equal bits on every run and exactly a host labelling's result.  A box needs fewer than
+ * 2^32 - 1 voxels.  `workspace`: device memory of of3d_mask_open_workspace_bytes(rois, n_roi)
+ * bytes (labels and sizes of the largest box, 8 bytes per voxel; 0 for invalid boxes), shared
+ * by the boxes.  Enqueued on `stream`; no host synchronisation, no workgroup waits for another. */
+size_t of3d_mask_open_workspace_bytes(const int64_t* rois, int n_roi);
+int of3d_mask_open(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64_t nx, const void* d_thresh,
+                   const int64_t* rois, int n_roi, int64_t min_size, int connectivity, uint16_t* d_keep,
+                   int64_t* d_counts, void* workspace, void* stream);
+
+/* of3d_flow_summary with the mask factor of a voxel in box r taken from bit r of d_keep
+ * (of3d_mask_open's output) instead of rel > *d_thresh: the figure scripts' statistics over the
+ * opened mask.  Word 0 of the result is still *d_thresh; the result layout, the workgroup
+ * partition, the summation order and the histograms are of3d_flow_summary's, so a d_keep from
+ * min_size 1 gives of3d_flow_summary's bits. */
+int of3d_flow_summary_masked(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32,
+                             int rel_f64, int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale,
+                             double zscale, double tscale, const int64_t* rois, int n_roi, const int* nbins,
+                             const double* const* edges, void* d_result, void* workspace, void* stream,
+                             const uint16_t* d_keep);
+
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order
  * x2 y2 z2 xy xz yz (calc_flow.py:352-354's matrix (x2 xy xz / xy y2 yz /

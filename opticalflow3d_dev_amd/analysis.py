@@ -113,12 +113,16 @@ def flow_statistics(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0,
 # (magnitude-weighted) circular mean of theta and histograms — computed on the
 # resident fields.  Histograms are plain counts: the magnitude-weighted phi
 # distribution of figure 4 needs floating-point accumulation per bin and is not
-# provided.
+# provided.  The scripts' clean-up of the mask first, bwareaopen(rel > thresh, minSize)
+# (plot_figure4_timeTraces.m:75-79, plot_figure5.m:87-88), is min_size / connectivity
+# (csrc/kt_ccl.hip: of3d_mask_open, then of3d_flow_summary_masked).
 # ---------------------------------------------------------------------------
 QUANTITIES = ("vx", "vy", "vz", "magnitude", "theta", "phi")
 SUMS = ("sum_magnitude", "sum_vx", "sum_vy", "sum_vz", "sum_sin", "sum_cos", "sum_mag_sin", "sum_mag_cos")
 MAX_ROI, MAX_BINS = 16, 256
 _HEAD, _ROI_HEAD = 8, 10  # result words before the boxes / before a box's histograms (include/of3d.h)
+CONNECTIVITIES = {2: (4, 8), 3: (6, 18, 26)}  # bwareaopen's, the default last
+OPEN_COUNTS = ("n_mask", "n_components", "n_components_kept", "n_kept")  # of3d_mask_open's d_counts
 
 
 def _np_dtype(t):
@@ -157,21 +161,41 @@ class SummarySpec:
     rois: boxes (z0, z1, y0, y1, x0, x1), half-open, or (y0, y1, x0, x1) in 2D; the whole
     volume is always ROI 0 and these follow it (at most 15).  bins: quantity name (vx, vy,
     vz, magnitude, theta, phi) -> ascending bin edges (at most 256 bins),
-    np.histogram(values, bins=edges) semantics.  Scales and percentile as flow_statistics."""
+    np.histogram(values, bins=edges) semantics.  Scales and percentile as flow_statistics.
+    min_size >= 1: the mask of every ROI is opened first, MATLAB's bwareaopen(rel > thresh,
+    min_size, connectivity) on the cropped mask (components of fewer than min_size voxels are
+    dropped; of3d_mask_open), and the summaries carry n_mask, n_components, n_components_kept
+    and n_kept; 0: no opening.  connectivity: 6, 18 or 26 in 3D (default 26), 4 or 8 in 2D
+    (default 8)."""
     rois: list | None = None
     bins: dict | None = None
     rel_percentile: float = 90
     xyscale: float = 1.0
     zscale: float = 1.0
     tscale: float = 1.0
+    min_size: int = 0
+    connectivity: int | None = None
+
+    def opening(self, ndim):
+        """Validated (min_size, connectivity) for an ndim-D volume; ValueError on a bad value."""
+        m = self.min_size
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 0:
+            raise ValueError(f"summary: min_size {m!r} is not a non-negative integer")
+        allowed = CONNECTIVITIES[ndim]
+        c = allowed[-1] if self.connectivity is None else self.connectivity
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c not in allowed:
+            raise ValueError(f"summary: connectivity {c!r} is not one of {allowed} for a {ndim}D volume")
+        return int(m), int(c)
 
     def resolve(self, shape):
         """Validated (boxes int64 (n_roi, 6), nbins [6], edges [6 arrays or None]) for a volume
-        of `shape` ((nz, ny, nx) or (ny, nx)); ValueError on a bad box or bad edges."""
+        of `shape` ((nz, ny, nx) or (ny, nx)); ValueError on a bad box, bad edges or a bad
+        min_size / connectivity."""
         shape = tuple(int(v) for v in shape)
         if len(shape) not in (2, 3) or min(shape) < 1:
             raise ValueError(f"summary: volume shape {shape} is not 2D or 3D")
         ndim = len(shape)
+        self.opening(ndim)
         dims = shape if ndim == 3 else (1,) + shape
         if not (0 <= float(self.rel_percentile) <= 100):
             raise ValueError(f"summary: rel_percentile {self.rel_percentile} outside [0, 100]")
@@ -207,6 +231,29 @@ class SummarySpec:
         return np.array(boxes, dtype=np.int64), nbins, edges
 
 
+class _OpenCall:
+    """of3d_mask_open bound to boxes and a device: the keep volume and the label / size
+    workspace, allocated once."""
+
+    def __init__(self, boxes, dims, rel_f64, min_size, connectivity, device):
+        import torch
+
+        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
+        self.min_size, self.connectivity = int(min_size), int(connectivity)
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
+        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        nbytes = self.lib.of3d_mask_open_workspace_bytes(self.roi_arr, len(self.boxes))
+        if nbytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.keep = torch.empty(self.dims, dtype=torch.uint16, device=device)
+
+    def enqueue(self, rel, thresh_ptr, counts_ptr, stream):
+        _lib.check(self.lib.of3d_mask_open(rel, self.rel_f64, *self.dims, thresh_ptr, self.roi_arr, len(self.boxes),
+                                           self.min_size, self.connectivity, self.keep.data_ptr(), counts_ptr,
+                                           self.ws.data_ptr(), stream or None))
+
+
 class _SummaryCall:
     """One resolved spec bound to a device: sizes, workspaces and the kernel launches."""
 
@@ -215,14 +262,19 @@ class _SummaryCall:
 
         self.spec, self.shape = spec, tuple(int(v) for v in shape)
         self.boxes, self.nbins, self.edges = spec.resolve(shape)
+        self.min_size, self.connectivity = spec.opening(len(self.shape))
         self.dims = self.shape if len(self.shape) == 3 else (1,) + self.shape
         lib = self.lib = _lib.load()
         self.nb_arr = (ctypes.c_int * 6)(*self.nbins)
         D = ctypes.POINTER(ctypes.c_double)
         self.edge_arr = (D * 6)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
         self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-        self.result_bytes = lib.of3d_flow_summary_result_bytes(len(self.boxes), self.nb_arr)
+        # the summary words, then (min_size >= 1) of3d_mask_open's 4 counts per box: one download
+        self.summary_bytes = lib.of3d_flow_summary_result_bytes(len(self.boxes), self.nb_arr)
+        self.result_bytes = self.summary_bytes + (32 * len(self.boxes) if self.min_size else 0)
         self.rel_f64 = int(rel_dtype == torch.float64)
+        self.open = _OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
+                              device) if self.min_size else None
         self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
         self.qws = torch.empty(lib.of3d_quantile_workspace_bytes(self.rel_f64), dtype=torch.uint8, device=device)
         self.thresh = torch.empty(1, dtype=rel_dtype, device=device)
@@ -240,10 +292,14 @@ class _SummaryCall:
         lib, s = self.lib, self.spec
         _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), self.thresh.data_ptr(),
                                      self.qws.data_ptr(), stream or None))
-        _lib.check(lib.of3d_flow_summary(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
-                                         self.thresh.data_ptr(), float(s.xyscale), float(s.zscale), float(s.tscale),
-                                         self.roi_arr, len(self.boxes), self.nb_arr, self.edge_arr, result_ptr,
-                                         self.ws.data_ptr(), stream or None))
+        args = (vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims, self.thresh.data_ptr(),
+                float(s.xyscale), float(s.zscale), float(s.tscale), self.roi_arr, len(self.boxes), self.nb_arr,
+                self.edge_arr, result_ptr, self.ws.data_ptr(), stream or None)
+        if self.open is None:
+            _lib.check(lib.of3d_flow_summary(*args))
+            return
+        self.open.enqueue(rel, self.thresh.data_ptr(), result_ptr + self.summary_bytes, stream)
+        _lib.check(lib.of3d_flow_summary_masked(*args, self.open.keep.data_ptr()))
 
     def decode(self, words):
         """The result words (host int64 array) as flow_summary's dict."""
@@ -270,11 +326,67 @@ class _SummaryCall:
                 out["hist"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.uint64)
                 out["edges"][name] = self.edges[q].copy()
                 off += self.nbins[q]
+        if self.min_size:
+            counts = words[self.summary_bytes // 8:self.summary_bytes // 8 + 4 * n_roi].reshape(n_roi, 4)
+            for i, k in enumerate(OPEN_COUNTS):
+                out[k] = counts[:, i].copy()
         return out
 
 
+def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connectivity=None, rois=None, device=None):
+    """The opened reliability mask of one frame, per ROI: MATLAB's
+    ``bwareaopen(rel > relThresh, min_size, connectivity)`` of the reference's figure scripts
+    (plot_figure5.m:87-88 feeds it to regionprops3) on the device (of3d_mask_open).
+
+    rel: numpy array or torch tensor, (nz, ny, nx) or (ny, nx), float32 or float64.  The
+    threshold is the rel_percentile-th percentile of rel (selected on the device) unless
+    `threshold` (a Python float, used as one element of rel's dtype) is given.  min_size >= 1;
+    connectivity 6 / 18 / 26 in 3D (default 26), 4 / 8 in 2D (default 8).  ROI 0 is the whole
+    volume, `rois` follow (SummarySpec's boxes); each box's mask is cropped first, then opened.
+    Returns a dict: keep (uint16, rel's shape; bit r set where the voxel lies in box r and in a
+    component of at least min_size voxels of that box's mask; a torch tensor, numpy for numpy
+    input), mask (r -> that bit plane as bool), rois, threshold and per ROI n_mask,
+    n_components, n_components_kept, n_kept (int64)."""
+    import torch
+
+    host = isinstance(rel, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    tr = torch.as_tensor(np.ascontiguousarray(rel)).to(dev) if host else rel.contiguous()
+    if tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rel must be float32 or float64")
+    if tr.dim() not in (2, 3):
+        raise ValueError("reliability_mask needs a (nz, ny, nx) or (ny, nx) field")
+    spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
+    boxes = spec.resolve(tuple(tr.shape))[0]
+    min_size, connectivity = spec.opening(tr.dim())
+    if min_size < 1:
+        raise ValueError("summary: reliability_mask needs min_size >= 1")
+    dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
+    call = _OpenCall(boxes, dims, tr.dtype == torch.float64, min_size, connectivity, tr.device)
+    with torch.cuda.device(tr.device):
+        if threshold is None:
+            thresh = percentile_threshold_device(tr, rel_percentile)
+        else:
+            thresh = torch.tensor([float(threshold)], dtype=tr.dtype).to(tr.device)
+        counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tr.device)
+        call.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(),
+                     torch.cuda.current_stream(tr.device).cuda_stream)
+        keep = call.keep.view(tr.shape)
+        counts = counts.cpu().numpy()
+        out = {"keep": keep.cpu().numpy() if host else keep, "rois": boxes.copy(),
+               "threshold": _np_dtype(tr).type(thresh.cpu().numpy()[0])}
+    k = out["keep"]
+    if host:
+        out["mask"] = lambda r: ((k >> np.uint16(r)) & np.uint16(1)).astype(bool)
+    else:
+        out["mask"] = lambda r: ((k.view(torch.int16) >> r) & 1).bool()  # uint16 has no shifts in torch
+    for i, name in enumerate(OPEN_COUNTS):
+        out[name] = counts[:, i].copy()
+    return out
+
+
 def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None,
-                 device=None):
+                 device=None, min_size=0, connectivity=None):
     """One frame reduced on the device to a few kilobytes (one small device->host copy).
 
     Inputs as flow_statistics (numpy arrays or torch tensors, vz None for 2D).  The masking is
@@ -285,6 +397,9 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     sum_mag_cos (sin/cos of theta = atan2(vy, vx)), the derived mean_magnitude, mean_vx/vy/vz,
     theta_mean = atan2(sum_sin/n, sum_cos/n), theta_mean_weighted (NaN where n_valid == 0), and
     hist[name] (n_roi, nbins) uint64 with edges[name] for every quantity in `bins`.
+    min_size >= 1 (with connectivity, see SummarySpec): every ROI's mask is opened first
+    (reliability_mask), n_valid then counts the kept voxels with a non-NaN magnitude, and the
+    dict also holds n_mask, n_components, n_components_kept and n_kept (int64 per ROI).
     Bit-reproducible: the same inputs give the same bits on every run."""
     import torch
 
@@ -297,7 +412,7 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
         raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
     if tx.dim() != (3 if tz is not None else 2):
         raise ValueError("flow_summary needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
-    spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale)
+    spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale, min_size, connectivity)
     call = _SummaryCall(spec, tuple(tx.shape), tr.dtype, tx.device)
     res = call.new_result(tx.device)
     call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
@@ -309,17 +424,24 @@ CSV_COLUMNS = ("frame", "roi", "z0", "z1", "y0", "y1", "x0", "x1", "threshold", 
                "mean_magnitude", "mean_vx", "mean_vy", "mean_vz", "theta_mean", "theta_mean_weighted") + SUMS
 
 
+CSV_OPEN_COLUMNS = OPEN_COUNTS  # appended when the summaries carry the opening's counts (min_size >= 1)
+
+
 def write_summaries(prefix, frames, summaries):
     """<prefix>_summary.csv (one row per frame and ROI; floats as repr, so they read back
-    exactly) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
+    exactly; the columns CSV_COLUMNS, then CSV_OPEN_COLUMNS when the summaries were made with
+    min_size >= 1) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
     (frames, n_roi, nbins)) from flow_summary dicts of consecutive frames."""
+    opened = bool(summaries) and all(k in summaries[0] for k in CSV_OPEN_COLUMNS)
     with open(prefix + "_summary.csv", "w", newline="") as f:
-        f.write(",".join(CSV_COLUMNS) + "\n")
+        f.write(",".join(CSV_COLUMNS + (CSV_OPEN_COLUMNS if opened else ())) + "\n")
         for frame, s in zip(frames, summaries):
             for r in range(len(s["rois"])):
                 row = [int(frame), r] + [int(v) for v in s["rois"][r]] + [repr(float(s["threshold"]))]
                 row += [int(s["n_valid"][r]), int(s["n_voxels"][r])]
                 row += [repr(float(s[k][r])) for k in CSV_COLUMNS[11:]]
+                if opened:
+                    row += [int(s[k][r]) for k in CSV_OPEN_COLUMNS]
                 f.write(",".join(str(v) for v in row) + "\n")
     arrays = {"frames": np.asarray(list(frames), dtype=np.int64)}
     if summaries:
@@ -334,6 +456,6 @@ def read_summary_csv(path):
     with open(path) as f:
         cols = f.readline().strip().split(",")
         rows = [line.strip().split(",") for line in f if line.strip()]
-    ints = set(CSV_COLUMNS[:8]) | {"n_valid", "n_voxels"}
+    ints = set(CSV_COLUMNS[:8]) | {"n_valid", "n_voxels"} | set(CSV_OPEN_COLUMNS)
     return {c: np.array([int(r[i]) if c in ints else float(r[i]) for r in rows],
                         dtype=np.int64 if c in ints else np.float64) for i, c in enumerate(cols)}

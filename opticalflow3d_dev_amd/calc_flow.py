@@ -202,7 +202,9 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     percentile, per-ROI valid counts, mean magnitude, circular means of theta, histograms:
     analysis.flow_summary) and ``<imNameSave>_summary.csv`` (one row per frame and ROI) and
     ``<imNameSave>_summary_hist.npz`` (edges and (frames, n_roi, nbins) counts per quantity)
-    are written; save_fields=False then downloads and writes no field TIFFs at all.  The
+    are written; save_fields=False then downloads and writes no field TIFFs at all.  A spec
+    with min_size >= 1 opens every ROI's reliability mask first (bwareaopen, as the figure
+    scripts do) and appends the columns n_mask, n_components, n_components_kept, n_kept.  The
     stdout lines are the same in every mode.  Single process, device-ring path only: with
     several ranks, or a window that differs from the temporal taps, a summary raises
     ValueError.

@@ -269,10 +269,12 @@ __device__ __forceinline__ int find_bin(const double* e, int nb, double v) {
     return lo;
 }
 
-template <typename VT, typename RelT>
+// Masked: the mask factor of a voxel is bit `roi` of keep (of3d_mask_open) instead of rel > thr
+template <typename VT, typename RelT, bool Masked>
 __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict__ vx, const VT* __restrict__ vy,
                                                            const VT* __restrict__ vz, const RelT* __restrict__ rel,
-                                                           const RelT* __restrict__ thr_p, SumParams P,
+                                                           const RelT* __restrict__ thr_p,
+                                                           const uint16_t* __restrict__ keep, SumParams P,
                                                            const double* __restrict__ edges_g,
                                                            double* __restrict__ slots, u64* __restrict__ result) {
     const int roi = blockIdx.y, nb = P.nb[roi];
@@ -319,7 +321,10 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
             fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
             if (in[u]) {
                 const size_t i = ((size_t)(z0 + z) * P.ny + (y0 + y)) * P.nx + (x0 + x);
-                fr[u] = (double)rel[i];
+                if constexpr (Masked)
+                    fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
+                else
+                    fr[u] = (double)rel[i];
                 fx[u] = (double)vx[i];
                 fy[u] = (double)vy[i];
                 if (is3) fz[u] = (double)vz[i];
@@ -335,7 +340,7 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!in[u]) continue;
-            const double m = (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
+            const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
             auto fix = [&](double v, double scale) {
                 v = v * m;
                 if (v == 0.0) v = qnan;
@@ -457,11 +462,12 @@ size_t of3d_flow_summary_result_bytes(int n_roi, const int* nbins) {
 
 size_t of3d_flow_summary_workspace_bytes(void) { return kSumWsBytes; }
 
-int of3d_flow_summary(const void* vx, const void* vy, const void* vz, const void* rel, int v_f32, int rel_f64,
-                      int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
-                      double tscale, const int64_t* rois, int n_roi, const int* nbins, const double* const* edges,
-                      void* d_result, void* workspace, void* stream) {
-    if (!vx || !vy || !rel || !d_thresh || !rois || !d_result || !workspace)
+static int summary_launch(const void* vx, const void* vy, const void* vz, const void* rel, int v_f32, int rel_f64,
+                          int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                          double tscale, const int64_t* rois, int n_roi, const int* nbins,
+                          const double* const* edges, void* d_result, void* workspace, void* stream,
+                          const uint16_t* keep, bool masked) {
+    if (!vx || !vy || !rel || !d_thresh || !rois || !d_result || !workspace || (masked && !keep))
         return of3dk::set_error("of3d: null argument");
     if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
         return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
@@ -523,9 +529,14 @@ int of3d_flow_summary(const void* vx, const void* vy, const void* vz, const void
     auto launch = [&](auto vt, auto rt) {
         using VT = decltype(vt);
         using RT = decltype(rt);
-        hipLaunchKernelGGL((k_sum_boxes<VT, RT>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s, (const VT*)vx,
-                           (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, P,
-                           (const double*)d_edges, slots, (u64*)d_result);
+        if (masked)
+            hipLaunchKernelGGL((k_sum_boxes<VT, RT, true>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
+                               (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, keep,
+                               P, (const double*)d_edges, slots, (u64*)d_result);
+        else
+            hipLaunchKernelGGL((k_sum_boxes<VT, RT, false>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
+                               (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, keep,
+                               P, (const double*)d_edges, slots, (u64*)d_result);
         hipLaunchKernelGGL(k_sum_final<RT>, dim3(n_roi), dim3(256), 0, s, (const double*)slots, (const RT*)d_thresh,
                            P, (u64*)d_result);
     };
@@ -535,6 +546,23 @@ int of3d_flow_summary(const void* vx, const void* vy, const void* vz, const void
         rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
     SUM_HIP(hipGetLastError());
     return 0;
+}
+
+int of3d_flow_summary(const void* vx, const void* vy, const void* vz, const void* rel, int v_f32, int rel_f64,
+                      int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                      double tscale, const int64_t* rois, int n_roi, const int* nbins, const double* const* edges,
+                      void* d_result, void* workspace, void* stream) {
+    return summary_launch(vx, vy, vz, rel, v_f32, rel_f64, nz, ny, nx, d_thresh, xyscale, zscale, tscale, rois, n_roi,
+                          nbins, edges, d_result, workspace, stream, nullptr, false);
+}
+
+int of3d_flow_summary_masked(const void* vx, const void* vy, const void* vz, const void* rel, int v_f32, int rel_f64,
+                             int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                             double tscale, const int64_t* rois, int n_roi, const int* nbins,
+                             const double* const* edges, void* d_result, void* workspace, void* stream,
+                             const uint16_t* d_keep) {
+    return summary_launch(vx, vy, vz, rel, v_f32, rel_f64, nz, ny, nx, d_thresh, xyscale, zscale, tscale, rois, n_roi,
+                          nbins, edges, d_result, workspace, stream, d_keep, true);
 }
 
 }  // extern "C"

@@ -61,7 +61,10 @@ class FlowStream:
         device outputs of that buffer set, and the copy of the few-kilobyte result to a pinned
         slot of the set; Pending.summary() returns analysis.flow_summary's dict.  fields=False
         (needs a summary): the fields are never downloaded, their pinned host buffers are not
-        allocated and Pending.result() raises.  Whole-volume streams only (no zslab).
+        allocated and Pending.result() raises.  Whole-volume streams only (no zslab).  A spec
+        with min_size >= 1 adds the mask opening (csrc/kt_ccl.hip) between the select and the
+        summary; its keep volume, labels and sizes are allocated once here, and its counts ride
+        in the same result words.
 
         zslab=(rank, world, group[, axis]): this process holds one slab of every frame (3D
         only) — axis 0 (default): output planes shard.zslab_bounds(nz, rank, world); axis 1:
