@@ -347,6 +347,69 @@ int of3d_flow_summary_masked(const void* d_vx, const void* d_vy, const void* d_v
                              const double* const* edges, void* d_result, void* workspace, void* stream,
                              const uint16_t* d_keep);
 
+/* The body-axis frame of the reliability mask and the flow projected onto it, on the device:
+ * what the reference's plot_figure5.m:87-88,132-149,200 and plot_figure5_Movie.m:88-89,128-143 do
+ * with regionprops3(relMask, 'EigenVectors', 'EigenValues') and a projection of every physical
+ * velocity vector onto the first eigenvectors (the embryo's anterior-posterior and dorso-ventral
+ * axes).  Fields, d_rel, dtypes, dims, d_thresh, scales and rois as of3d_flow_summary's.  For
+ * every box r independently:
+ *   1. the mask M_r: bit r of d_keep (of3d_mask_open's output) when d_keep is given, else
+ *      rel > *d_thresh inside the box (a NaN gives false; d_rel / d_thresh may be NULL with
+ *      d_keep).  A NaN magnitude plays no part here: regionprops3 sees only the mask.
+ *   2. ten unsigned 64-bit sums over M_r of the box-local integer coordinates (x - x0, y - y0,
+ *      z - z0): n, Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz.  Integer arithmetic and integer
+ *      atomics only: exact and independent of the order.
+ *   3. centroid = box origin + S_a / n, in volume coordinates (x, y, z); the population
+ *      covariance C_ab = (n S_ab - S_a S_b) / n^2, the numerator exact in 128-bit integers,
+ *      converted to float64 as hi * 2^64 + lo, then divided by (double)n * (double)n; with
+ *      axes_physical C becomes S C S, S = diag(xyscale, xyscale, zscale).
+ *   4. eigenvalues (descending, as regionprops3 lists them; one that rounding left negative is
+ *      0) and unit eigenvectors of C by a cyclic Jacobi iteration in float64 (12 sweeps, no
+ *      data-dependent loop); equal eigenvalues keep the x, y, z order.  Sign: the component of
+ *      largest magnitude of each vector is positive, a tie goes to the first of x, y, z.  A 2D
+ *      volume (nz == 1) gives eigenvalue 3 = 0 and vector 3 = (0, 0, 1).  n == 0: NaN.
+ *   5. the axes used: the box's eigenvectors e1 e2 e3, or axes_given (host, 9 finite doubles
+ *      e1 e2 e3, each x y z, the same for every box; they travel as kernel arguments) — a
+ *      movie keeps one frame's axes so that no sign flips between frames.  Steps 2-4 are
+ *      reported either way.
+ *   6. with fields (d_vx != NULL): of3d_flow_summary's per-voxel arithmetic (mask factor,
+ *      v * mask, zeros -> NaN, (v*scale)/tscale; valid <=> magnitude not NaN), then
+ *      p_k = (vx*e_k.x + vy*e_k.y) + vz*e_k.z (2D: vx*e_k.x + vy*e_k.y), plain multiplies and
+ *      adds in that order (no FMA); n_valid, the three sums of p_k and up to three histograms
+ *      (nbins3: host int[3], edges3: host double*[3]; np.histogram semantics, at most 256 bins;
+ *      nbins3[2] == 0 in 2D).  d_vx == NULL (then d_vy == d_vz == NULL, nbins3 all 0): steps
+ *      1-5 only.
+ * Not reproduced of regionprops3: any constant it adds to the second moments for a voxel's own
+ * extent (a multiple of the identity: the eigenvectors are the same, the eigenvalues shift by
+ * it), and the scripts' pairing vy*vecs(1,k) + vx*vecs(2,k): here the x component of an axis
+ * multiplies vx; the axes are returned, so any other pairing can be formed from them.
+ *
+ * Result (device, of3d_mask_axes_result_bytes(n_roi, nbins3) bytes, 8-byte words), per box
+ * 44 + sum(nbins3) words:
+ *    0..9    uint64 n, Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz
+ *   10..12   float64 centroid x y z
+ *   13..18   float64 covariance xx yy zz xy xz yz
+ *   19..21   float64 eigenvalues, descending
+ *   22..30   float64 eigenvectors e1 e2 e3, each x y z
+ *   31..39   float64 the axes used for the projection, e1 e2 e3
+ *   40       n_valid (int64)
+ *   41..43   float64 sums of p_1, p_2, p_3 over the valid voxels (p_3: vz term omitted in 2D)
+ *   44..     uint64 histogram counts, axis after axis (nbins3[k] words each)
+ * Deterministic as of3d_flow_summary is (the same workgroup partition, summation order and
+ * slots; no floating-point atomics), and a box's words do not depend on the other boxes.
+ * of3d_mask_axes_workspace_bytes: host arithmetic only; 0 for an invalid box and for a box whose
+ * sums could overflow: voxels * (L - 1)^2 < 2^63 is required, L the box's longest edge.
+ * Enqueued on `stream`; no host synchronisation, no workgroup waits for another. */
+#define OF3D_AXES_QUANTITIES 3
+#define OF3D_AXES_ROI_WORDS 44
+size_t of3d_mask_axes_workspace_bytes(const int64_t* rois, int n_roi);
+size_t of3d_mask_axes_result_bytes(int n_roi, const int* nbins3);
+int of3d_mask_axes(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32, int rel_f64,
+                   int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                   double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const double* axes_given,
+                   int axes_physical, const int* nbins3, const double* const* edges3, void* d_result,
+                   void* workspace, void* stream);
+
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order
  * x2 y2 z2 xy xz yz (calc_flow.py:352-354's matrix (x2 xy xz / xy y2 yz /

@@ -123,6 +123,11 @@ MAX_ROI, MAX_BINS = 16, 256
 _HEAD, _ROI_HEAD = 8, 10  # result words before the boxes / before a box's histograms (include/of3d.h)
 CONNECTIVITIES = {2: (4, 8), 3: (6, 18, 26)}  # bwareaopen's, the default last
 OPEN_COUNTS = ("n_mask", "n_components", "n_components_kept", "n_kept")  # of3d_mask_open's d_counts
+# of3d_mask_axes (csrc/kt_axes.hip): the mask's principal axes (regionprops3's EigenVectors /
+# EigenValues, plot_figure5.m:132-149, plot_figure5_Movie.m:128-143) and the flow projected on them
+AXIS_NAMES = ("axis1", "axis2", "axis3")
+MOMENTS = ("n", "x", "y", "z", "xx", "yy", "zz", "xy", "xz", "yz")  # the integer sums of a box's result
+_AX_HEAD = 44  # a box's result words before its histograms (include/of3d.h)
 
 
 def _np_dtype(t):
@@ -166,7 +171,14 @@ class SummarySpec:
     min_size, connectivity) on the cropped mask (components of fewer than min_size voxels are
     dropped; of3d_mask_open), and the summaries carry n_mask, n_components, n_components_kept
     and n_kept; 0: no opening.  connectivity: 6, 18 or 26 in 3D (default 26), 4 or 8 in 2D
-    (default 8)."""
+    (default 8).
+    axes: "mask" — the principal axes of every ROI's (opened) mask, regionprops3's EigenVectors /
+    EigenValues (of3d_mask_axes), and the flow projected onto them — or a 3x3 array (rows e1 e2
+    e3, each x y z) to project on instead, e.g. an earlier frame's axis_vectors, so that no
+    sign flips along a movie; the mask's own axes are reported either way.  axes_physical: the
+    covariance in physical units (xyscale, xyscale, zscale) before the decomposition.
+    axis_bins: "axis1" / "axis2" / "axis3" -> ascending bin edges of the projections'
+    histograms (at most 256 bins; axis3 in 3D only).  None: nothing of this is computed."""
     rois: list | None = None
     bins: dict | None = None
     rel_percentile: float = 90
@@ -175,6 +187,45 @@ class SummarySpec:
     tscale: float = 1.0
     min_size: int = 0
     connectivity: int | None = None
+    axes: object = None
+    axes_physical: bool = False
+    axis_bins: dict | None = None
+
+    def axes_request(self, ndim):
+        """None without axes, else validated (given, nbins3, edges3): given = None for "mask" or
+        the 9 float64 values of the 3x3 array; ValueError on a bad value."""
+        if self.axes is None:
+            if self.axis_bins:
+                raise ValueError("summary: axis_bins needs axes")
+            return None
+        given = None
+        if isinstance(self.axes, str):
+            if self.axes != "mask":
+                raise ValueError(f"summary: axes {self.axes!r} is not 'mask' or a 3x3 array")
+        else:
+            try:
+                given = np.ascontiguousarray(self.axes, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"summary: axes {self.axes!r} is not 'mask' or a 3x3 array") from None
+            if given.shape != (3, 3):
+                raise ValueError(f"summary: axes must be a 3x3 array, got shape {given.shape}")
+            if not np.all(np.isfinite(given)):
+                raise ValueError("summary: axes must be finite")
+            given = given.reshape(9).copy()
+        nbins, edges = [0] * 3, [None] * 3
+        for name, e in (self.axis_bins or {}).items():
+            if name not in AXIS_NAMES:
+                raise ValueError(f"summary: unknown axis histogram {name!r} (one of {AXIS_NAMES})")
+            if ndim == 2 and name == "axis3":
+                raise ValueError("summary: an axis3 histogram needs a 3D volume")
+            e = np.ascontiguousarray(e, dtype=np.float64)
+            if e.ndim != 1 or e.size < 2 or e.size > MAX_BINS + 1:
+                raise ValueError(f"summary: {name} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
+            if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
+                raise ValueError(f"summary: {name} bin edges must be strictly ascending")
+            k = AXIS_NAMES.index(name)
+            nbins[k], edges[k] = e.size - 1, e
+        return given, nbins, edges
 
     def opening(self, ndim):
         """Validated (min_size, connectivity) for an ndim-D volume; ValueError on a bad value."""
@@ -254,6 +305,65 @@ class _OpenCall:
                                            self.ws.data_ptr(), stream or None))
 
 
+class _AxesCall:
+    """of3d_mask_axes bound to boxes and a device: sizes, the workspace and the decoding."""
+
+    def __init__(self, boxes, dims, rel_f64, request, physical, scales, device):
+        import torch
+
+        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
+        self.given, self.nbins, self.edges = request
+        self.physical, self.scales = int(bool(physical)), tuple(float(v) for v in scales)
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
+        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        D = ctypes.POINTER(ctypes.c_double)
+        self.nb_arr = (ctypes.c_int * 3)(*self.nbins)
+        self.edge_arr = (D * 3)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
+        self.given_arr = self.given.ctypes.data_as(D) if self.given is not None else None
+        nbytes = self.lib.of3d_mask_axes_workspace_bytes(self.roi_arr, len(self.boxes))
+        if nbytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.result_bytes = self.lib.of3d_mask_axes_result_bytes(len(self.boxes), self.nb_arr)
+
+    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+        """Moments, axes and (vx given) projection kernels on `stream` (device pointers)."""
+        _lib.check(self.lib.of3d_mask_axes(vx or None, vy or None, vz or None, rel, int(v_f32), self.rel_f64,
+                                           *self.dims, thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
+                                           keep_ptr or None, self.given_arr, self.physical, self.nb_arr,
+                                           self.edge_arr, result_ptr, self.ws.data_ptr(), stream or None))
+
+    def decode(self, words, out, projected=True):
+        """The block's words (host int64) added to the dict `out` (flow_summary's keys)."""
+        n_roi, ntot = len(self.boxes), sum(self.nbins)
+        body = np.ascontiguousarray(words[:n_roi * (_AX_HEAD + ntot)], dtype=np.int64).reshape(n_roi, _AX_HEAD + ntot)
+        f = lambda a, b: np.ascontiguousarray(body[:, a:b]).view(np.float64)
+        out["moments"] = np.ascontiguousarray(body[:, :10]).view(np.uint64)
+        out["n_axes_mask"] = body[:, 0].copy()
+        out["centroid"] = f(10, 13)
+        c = f(13, 19)
+        out["covariance"] = c[:, [0, 3, 4, 3, 1, 5, 4, 5, 2]].reshape(n_roi, 3, 3)
+        out["axis_values"] = f(19, 22)
+        out["axis_vectors"] = f(22, 31).reshape(n_roi, 3, 3)
+        out["axes_used"] = f(31, 40).reshape(n_roi, 3, 3)
+        if not projected:
+            return out
+        out["n_axes_valid"] = body[:, 40].copy()
+        sums = f(41, 44)
+        nv = out["n_axes_valid"].astype(np.float64)
+        nv[nv == 0] = np.nan
+        for k, name in enumerate(AXIS_NAMES):
+            out["sum_" + name] = sums[:, k].copy()
+            out["mean_" + name] = sums[:, k] / nv
+        off = _AX_HEAD
+        for k, name in enumerate(AXIS_NAMES):
+            if self.nbins[k]:
+                out["hist"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[k]]).view(np.uint64)
+                out["edges"][name] = self.edges[k].copy()
+                off += self.nbins[k]
+        return out
+
+
 class _SummaryCall:
     """One resolved spec bound to a device: sizes, workspaces and the kernel launches."""
 
@@ -273,6 +383,13 @@ class _SummaryCall:
         self.summary_bytes = lib.of3d_flow_summary_result_bytes(len(self.boxes), self.nb_arr)
         self.result_bytes = self.summary_bytes + (32 * len(self.boxes) if self.min_size else 0)
         self.rel_f64 = int(rel_dtype == torch.float64)
+        # then (axes) of3d_mask_axes' block
+        request = spec.axes_request(len(self.shape))
+        self.axes, self.axes_off = None, self.result_bytes
+        if request is not None:
+            self.axes = _AxesCall(self.boxes, self.dims, self.rel_f64, request, spec.axes_physical,
+                                  (spec.xyscale, spec.zscale, spec.tscale), device)
+            self.result_bytes += self.axes.result_bytes
         self.open = _OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
                               device) if self.min_size else None
         self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
@@ -297,9 +414,13 @@ class _SummaryCall:
                 self.edge_arr, result_ptr, self.ws.data_ptr(), stream or None)
         if self.open is None:
             _lib.check(lib.of3d_flow_summary(*args))
-            return
-        self.open.enqueue(rel, self.thresh.data_ptr(), result_ptr + self.summary_bytes, stream)
-        _lib.check(lib.of3d_flow_summary_masked(*args, self.open.keep.data_ptr()))
+        else:
+            self.open.enqueue(rel, self.thresh.data_ptr(), result_ptr + self.summary_bytes, stream)
+            _lib.check(lib.of3d_flow_summary_masked(*args, self.open.keep.data_ptr()))
+        if self.axes is not None:
+            self.axes.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+                              self.open.keep.data_ptr() if self.open is not None else None,
+                              result_ptr + self.axes_off, stream)
 
     def decode(self, words):
         """The result words (host int64 array) as flow_summary's dict."""
@@ -330,13 +451,16 @@ class _SummaryCall:
             counts = words[self.summary_bytes // 8:self.summary_bytes // 8 + 4 * n_roi].reshape(n_roi, 4)
             for i, k in enumerate(OPEN_COUNTS):
                 out[k] = counts[:, i].copy()
+        if self.axes is not None:
+            self.axes.decode(words[self.axes_off // 8:], out)
         return out
 
 
 def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connectivity=None, rois=None, device=None):
     """The opened reliability mask of one frame, per ROI: MATLAB's
     ``bwareaopen(rel > relThresh, min_size, connectivity)`` of the reference's figure scripts
-    (plot_figure5.m:87-88 feeds it to regionprops3) on the device (of3d_mask_open).
+    (plot_figure5.m:87-88; principal_axes gives the regionprops3 step that follows it there) on
+    the device (of3d_mask_open).
 
     rel: numpy array or torch tensor, (nz, ny, nx) or (ny, nx), float32 or float64.  The
     threshold is the rel_percentile-th percentile of rel (selected on the device) unless
@@ -385,8 +509,62 @@ def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connect
     return out
 
 
+def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectivity=None, rois=None, physical=False,
+                   xyscale=1.0, zscale=1.0, device=None):
+    """The principal axes of one frame's reliability mask, per ROI: what the reference's
+    plot_figure5.m:132-149 takes from ``regionprops3(relMask, 'EigenVectors', 'EigenValues')``,
+    on the device (of3d_mask_axes); the mask-only part of flow_summary(axes="mask").
+
+    rel, rel_percentile, threshold, connectivity and rois as reliability_mask; min_size >= 1
+    opens the mask first, 0 (the default) takes rel > threshold as it is.  physical: the
+    covariance in physical units, diag(xyscale, xyscale, zscale) on both sides.  Returns a dict of
+    numpy values per ROI: rois, threshold, n_axes_mask (the mask's voxels), moments (uint64
+    (n_roi, 10): n and the sums of x y z xx yy zz xy xz yz over box-local coordinates), centroid
+    (x, y, z in volume coordinates), covariance (3, 3; population, exact numerators),
+    axis_values (descending), axis_vectors (row k: e_k as x y z; largest component positive) and,
+    with min_size >= 1, the opening's counts.  An empty mask gives NaN."""
+    import torch
+
+    host = isinstance(rel, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    tr = torch.as_tensor(np.ascontiguousarray(rel)).to(dev) if host else rel.contiguous()
+    if tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rel must be float32 or float64")
+    if tr.dim() not in (2, 3):
+        raise ValueError("principal_axes needs a (nz, ny, nx) or (ny, nx) field")
+    spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity,
+                       axes="mask", axes_physical=physical)
+    boxes = spec.resolve(tuple(tr.shape))[0]
+    min_size, connectivity = spec.opening(tr.dim())
+    dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
+    rel_f64 = tr.dtype == torch.float64
+    call = _AxesCall(boxes, dims, rel_f64, spec.axes_request(tr.dim()), physical, (xyscale, zscale, 1.0), tr.device)
+    opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tr.device) if min_size else None
+    with torch.cuda.device(tr.device):
+        stream = torch.cuda.current_stream(tr.device).cuda_stream
+        if threshold is None:
+            thresh = percentile_threshold_device(tr, rel_percentile)
+        else:
+            thresh = torch.tensor([float(threshold)], dtype=tr.dtype).to(tr.device)
+        res = torch.empty(call.result_bytes // 8 + 4 * len(boxes), dtype=torch.int64, device=tr.device)
+        counts_ptr = res.data_ptr() + call.result_bytes
+        if opening is not None:
+            opening.enqueue(tr.data_ptr(), thresh.data_ptr(), counts_ptr, stream)
+        call.enqueue(None, None, None, tr.data_ptr(), 0, thresh.data_ptr(),
+                     opening.keep.data_ptr() if opening is not None else None, res.data_ptr(), stream)
+        words = res.cpu().numpy()
+        out = {"rois": boxes.copy(), "threshold": _np_dtype(tr).type(thresh.cpu().numpy()[0])}
+    call.decode(words, out, projected=False)
+    del out["axes_used"]
+    if opening is not None:
+        counts = words[call.result_bytes // 8:].reshape(len(boxes), 4)
+        for i, name in enumerate(OPEN_COUNTS):
+            out[name] = counts[:, i].copy()
+    return out
+
+
 def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None,
-                 device=None, min_size=0, connectivity=None):
+                 device=None, min_size=0, connectivity=None, axes=None, axes_physical=False, axis_bins=None):
     """One frame reduced on the device to a few kilobytes (one small device->host copy).
 
     Inputs as flow_statistics (numpy arrays or torch tensors, vz None for 2D).  The masking is
@@ -400,6 +578,10 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     min_size >= 1 (with connectivity, see SummarySpec): every ROI's mask is opened first
     (reliability_mask), n_valid then counts the kept voxels with a non-NaN magnitude, and the
     dict also holds n_mask, n_components, n_components_kept and n_kept (int64 per ROI).
+    axes ("mask" or a 3x3 array), axes_physical, axis_bins (see SummarySpec): per ROI also the
+    mask's integer moments (moments, n_axes_mask), centroid, covariance (3, 3), axis_values,
+    axis_vectors (row k: e_k as x y z), axes_used (those, or the given array), and the flow
+    projected on axes_used: n_axes_valid, sum_axis1..3, mean_axis1..3, hist["axis1"]...
     Bit-reproducible: the same inputs give the same bits on every run."""
     import torch
 
@@ -412,7 +594,8 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
         raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
     if tx.dim() != (3 if tz is not None else 2):
         raise ValueError("flow_summary needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
-    spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale, min_size, connectivity)
+    spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale, min_size, connectivity, axes,
+                       axes_physical, axis_bins)
     call = _SummaryCall(spec, tuple(tx.shape), tr.dtype, tx.device)
     res = call.new_result(tx.device)
     call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
@@ -427,14 +610,36 @@ CSV_COLUMNS = ("frame", "roi", "z0", "z1", "y0", "y1", "x0", "x1", "threshold", 
 CSV_OPEN_COLUMNS = OPEN_COUNTS  # appended when the summaries carry the opening's counts (min_size >= 1)
 
 
+# appended when the summaries carry the axes block (SummarySpec.axes): the integer columns, then
+# the float64 ones (vectors as x y z)
+CSV_AXES_INT_COLUMNS = ("n_axes_mask",) + tuple("mom_" + m for m in MOMENTS[1:]) + ("n_axes_valid",)
+CSV_AXES_COLUMNS = CSV_AXES_INT_COLUMNS + (
+    ("centroid_x", "centroid_y", "centroid_z", "cov_xx", "cov_yy", "cov_zz", "cov_xy", "cov_xz", "cov_yz",
+     "axis_value1", "axis_value2", "axis_value3")
+    + tuple(f"{a}_{c}" for a in AXIS_NAMES for c in "xyz") + tuple(f"used{k}_{c}" for k in "123" for c in "xyz")
+    + tuple("sum_" + a for a in AXIS_NAMES) + tuple("mean_" + a for a in AXIS_NAMES))
+
+
+def _axes_row(s, r):
+    """The CSV_AXES_COLUMNS values of ROI r of a summary dict."""
+    c = s["covariance"][r]
+    ints = [int(s["n_axes_mask"][r])] + [int(v) for v in s["moments"][r][1:]] + [int(s["n_axes_valid"][r])]
+    floats = list(s["centroid"][r]) + [c[0, 0], c[1, 1], c[2, 2], c[0, 1], c[0, 2], c[1, 2]]
+    floats += list(s["axis_values"][r]) + list(s["axis_vectors"][r].ravel()) + list(s["axes_used"][r].ravel())
+    floats += [s["sum_" + a][r] for a in AXIS_NAMES] + [s["mean_" + a][r] for a in AXIS_NAMES]
+    return ints + [repr(float(v)) for v in floats]
+
+
 def write_summaries(prefix, frames, summaries):
     """<prefix>_summary.csv (one row per frame and ROI; floats as repr, so they read back
     exactly; the columns CSV_COLUMNS, then CSV_OPEN_COLUMNS when the summaries were made with
-    min_size >= 1) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
+    min_size >= 1, then CSV_AXES_COLUMNS when they were made with axes) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
     (frames, n_roi, nbins)) from flow_summary dicts of consecutive frames."""
     opened = bool(summaries) and all(k in summaries[0] for k in CSV_OPEN_COLUMNS)
+    with_axes = bool(summaries) and "axes_used" in summaries[0]
     with open(prefix + "_summary.csv", "w", newline="") as f:
-        f.write(",".join(CSV_COLUMNS + (CSV_OPEN_COLUMNS if opened else ())) + "\n")
+        f.write(",".join(CSV_COLUMNS + (CSV_OPEN_COLUMNS if opened else ())
+                         + (CSV_AXES_COLUMNS if with_axes else ())) + "\n")
         for frame, s in zip(frames, summaries):
             for r in range(len(s["rois"])):
                 row = [int(frame), r] + [int(v) for v in s["rois"][r]] + [repr(float(s["threshold"]))]
@@ -442,6 +647,8 @@ def write_summaries(prefix, frames, summaries):
                 row += [repr(float(s[k][r])) for k in CSV_COLUMNS[11:]]
                 if opened:
                     row += [int(s[k][r]) for k in CSV_OPEN_COLUMNS]
+                if with_axes:
+                    row += _axes_row(s, r)
                 f.write(",".join(str(v) for v in row) + "\n")
     arrays = {"frames": np.asarray(list(frames), dtype=np.int64)}
     if summaries:
@@ -456,6 +663,6 @@ def read_summary_csv(path):
     with open(path) as f:
         cols = f.readline().strip().split(",")
         rows = [line.strip().split(",") for line in f if line.strip()]
-    ints = set(CSV_COLUMNS[:8]) | {"n_valid", "n_voxels"} | set(CSV_OPEN_COLUMNS)
+    ints = set(CSV_COLUMNS[:8]) | {"n_valid", "n_voxels"} | set(CSV_OPEN_COLUMNS) | set(CSV_AXES_INT_COLUMNS)
     return {c: np.array([int(r[i]) if c in ints else float(r[i]) for r in rows],
                         dtype=np.int64 if c in ints else np.float64) for i, c in enumerate(cols)}

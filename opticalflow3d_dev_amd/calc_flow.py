@@ -204,7 +204,9 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     ``<imNameSave>_summary_hist.npz`` (edges and (frames, n_roi, nbins) counts per quantity)
     are written; save_fields=False then downloads and writes no field TIFFs at all.  A spec
     with min_size >= 1 opens every ROI's reliability mask first (bwareaopen, as the figure
-    scripts do) and appends the columns n_mask, n_components, n_components_kept, n_kept.  The
+    scripts do) and appends the columns n_mask, n_components, n_components_kept, n_kept.  A
+    spec with axes adds the mask's moments, centroid, covariance and principal axes and the flow
+    projected onto them (analysis.CSV_AXES_COLUMNS; counts_axis* / edges_axis* in the npz).  The
     stdout lines are the same in every mode.  Single process, device-ring path only: with
     several ranks, or a window that differs from the temporal taps, a summary raises
     ValueError.

@@ -11,6 +11,7 @@
 
 #include "../../include/of3d.h"
 #include "kernels.hpp"
+#include "summary_dev.hpp"
 
 namespace {
 
@@ -223,9 +224,7 @@ int quantile_launch(const void* a, int64_t n, int64_t lo, int64_t hi, double gam
 // then 64-bit integer atomics into the (zeroed) result.  No floating-point atomics: the same
 // inputs give the same bits on every run, and a box's row does not depend on the other boxes.
 // ---------------------------------------------------------------------------
-constexpr int kSumThreads = 512, kSumWaves = kSumThreads / 64;
-constexpr int kSumMaxBlocks = 1024;        // workgroups (workspace slots) per box at most
-constexpr int64_t kSumVoxPerBlock = 8192;  // a workgroup's share of a box at least
+using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::kSumVoxPerBlock;  // summary_dev.hpp
 constexpr int kNSum = 8;                   // mag x y z sin cos mag*sin mag*cos
 constexpr int kNQ = OF3D_SUMMARY_QUANTITIES;
 constexpr int kMaxBins = OF3D_SUMMARY_MAX_BINS, kMaxRoi = OF3D_SUMMARY_MAX_ROI;
@@ -255,19 +254,7 @@ __global__ void k_put_edges(double* __restrict__ dst, EdgeChunk c, int n) {
     if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
 }
 
-// np.histogram(v, bins=e): e[i] <= v < e[i+1], the last bin closed; -1: dropped (outside, NaN)
-__device__ __forceinline__ int find_bin(const double* e, int nb, double v) {
-    if (!(v >= e[0] && v <= e[nb])) return -1;
-    int lo = 0, hi = nb;  // e[lo] <= v, and v < e[hi] or hi == nb
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (v >= e[mid])
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
+using of3dk::find_bin;  // summary_dev.hpp, shared with kt_axes.hip
 
 // Masked: the mask factor of a voxel is bit `roi` of keep (of3d_mask_open) instead of rel > thr
 template <typename VT, typename RelT, bool Masked>
@@ -299,14 +286,8 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
     const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
     const long long count = (r1 - r0) * dx;  // this workgroup's voxels (< 2^31: checked on the host)
     // this thread's voxel as (z, y, x) inside the box, advanced by kSumThreads voxels per step
-    // without divisions: x by step % dx with a carry into the row, the row by step / dx
-    const unsigned step_x = kSumThreads % dx, step_r = kSumThreads / dx;
-    const unsigned step_y = step_r % dy, step_z = step_r / dy;
-    unsigned x = threadIdx.x % dx;
-    const long long row = r0 + threadIdx.x / dx;
-    unsigned y = (unsigned)(row % dy), z = (unsigned)(row / dy);
+    of3dk::BoxWalk w(dy, dx, r0, threadIdx.x, kSumThreads);
     const double thr = (double)*thr_p;
-    const double qnan = __builtin_nan("");
     const bool is3 = vz != nullptr;
     double acc[kNSum] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned nvalid = 0;
@@ -320,7 +301,7 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
             in[u] = e + (long long)u * kSumThreads < count;
             fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
             if (in[u]) {
-                const size_t i = ((size_t)(z0 + z) * P.ny + (y0 + y)) * P.nx + (x0 + x);
+                const size_t i = ((size_t)(z0 + w.z) * P.ny + (y0 + w.y)) * P.nx + (x0 + w.x);
                 if constexpr (Masked)
                     fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
                 else
@@ -329,25 +310,15 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
                 fy[u] = (double)vy[i];
                 if (is3) fz[u] = (double)vz[i];
             }
-            x += step_x;
-            unsigned c = x >= dx;
-            x -= c ? dx : 0;
-            y += step_y + c;
-            c = y >= dy;
-            y -= c ? dy : 0;
-            z += step_z + c;
+            w.advance();
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!in[u]) continue;
             const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
-            auto fix = [&](double v, double scale) {
-                v = v * m;
-                if (v == 0.0) v = qnan;
-                return (v * scale) / P.st;
-            };
-            const double vxp = fix(fx[u], P.sxy), vyp = fix(fy[u], P.sxy);
-            const double vzp = is3 ? fix(fz[u], P.sz) : 0.0;
+            const double vxp = of3dk::masked_velocity(fx[u], m, P.sxy, P.st);
+            const double vyp = of3dk::masked_velocity(fy[u], m, P.sxy, P.st);
+            const double vzp = is3 ? of3dk::masked_velocity(fz[u], m, P.sz, P.st) : 0.0;
             const double xy2 = vxp * vxp + vyp * vyp;
             const double mag = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
             if (mag != mag) continue;  // badRows = isnan(mag)
@@ -492,9 +463,7 @@ static int summary_launch(const void* vx, const void* vy, const void* vz, const 
         }
         // a function of the box alone (never of the device): the summation order is fixed
         const int64_t rows = (rois[r * 6 + 1] - rois[r * 6]) * (rois[r * 6 + 3] - rois[r * 6 + 2]);
-        int64_t nb = (vox + kSumVoxPerBlock - 1) / kSumVoxPerBlock;
-        nb = nb > kSumMaxBlocks ? kSumMaxBlocks : nb;
-        nb = nb > rows ? rows : nb;
+        const int64_t nb = of3dk::sum_workgroups(vox, rows);
         // a workgroup's share: at most ceil(rows / nb) rows
         if (((rows + nb - 1) / nb) * (rois[r * 6 + 5] - rois[r * 6 + 4]) >= ((int64_t)1 << 31) - 4 * kSumThreads)
             return of3dk::set_error("of3d: ROI too large (2^31 voxels per workgroup)");
