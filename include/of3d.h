@@ -279,8 +279,8 @@ int of3d_quantile(const void* d_a, int is_f64, int64_t n, int64_t lo, int64_t hi
  * nbins: host int[6], edges: host double*[6] (entry q: nbins[q] + 1 strictly ascending edges;
  * ignored where nbins[q] == 0) for the quantities 0 vx, 1 vy, 2 vz, 3 magnitude, 4 theta,
  * 5 phi; at most 256 bins each, 0 = no histogram; np.histogram(values, bins=edges) semantics
- * over the valid voxels (last bin closed, values outside and NaN dropped; counts, not
- * magnitude-weighted).  2D: vz == NULL, nz == 1, nbins[2] == nbins[5] == 0.
+ * over the valid voxels (last bin closed, values outside and NaN dropped; counts —
+ * of3d_flow_whist gives the magnitude-weighted ones).  2D: vz == NULL, nz == 1, nbins[2] == nbins[5] == 0.
  *
  * Result (device, of3d_flow_summary_result_bytes(n_roi, nbins) bytes, 8-byte words):
  *   word 0        the threshold as float64
@@ -409,6 +409,42 @@ int of3d_mask_axes(const void* d_vx, const void* d_vy, const void* d_vz, const v
                    double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const double* axes_given,
                    int axes_physical, const int* nbins3, const double* const* edges3, void* d_result,
                    void* workspace, void* stream);
+
+/* Magnitude-weighted histograms of the frame summary: per box and quantity
+ *   np.histogram(values, bins=edges, weights=magnitude)[0]
+ * over the valid voxels — the reference's distPhiW (plot_figure4_timeTraces.m:128-138:
+ * accumarray(discretize(-phi, phiBins), mag) over ~badRows; its division by the valid count is
+ * left to the caller, n_valid is returned).  Fields, d_rel, dtypes, dims, d_thresh, scales, rois,
+ * validity (magnitude not NaN), nbins, edges and the bin rule are of3d_flow_summary's; the weight
+ * is always the physical magnitude.  d_keep NULL: the mask factor is rel > *d_thresh; else bit r
+ * of d_keep for box r, as of3d_flow_summary_masked (d_rel and d_thresh may then be NULL).  At
+ * least one quantity must have bins; 2D: vz == NULL, nz == 1, nbins[2] == nbins[5] == 0.
+ *
+ * Result (device, of3d_flow_whist_result_bytes(n_roi, nbins) bytes, 8-byte words, zeroed on the
+ * stream first), per box 1 + sum(nbins) words:
+ *   0    n_valid (int64; of3d_flow_summary's for the same mask)
+ *   1..  float64 bin sums, requested quantity after quantity in the order vx, vy, vz, magnitude,
+ *        theta, phi (nbins[q] words each)
+ * A pass over the fields per requested quantity (grid: workgroups x boxes x quantities), beside
+ * of3d_flow_summary's and with its workgroup partition.  Deterministic under the same contract:
+ * no floating-point atomic in LDS or global memory.  Every wave keeps a bin array of its own in
+ * LDS; per voxel step it visits the distinct bins among its 64 lanes in the order of their first
+ * lane, adds the weights of the lanes holding the bin (+0.0 in the others, exact as weights are
+ * >= 0) by a fixed shuffle tree and one lane adds that to the wave's array; the workgroup adds
+ * its waves' arrays in wave order into its own workspace slot, and a second kernel adds a bin's
+ * slots in workgroup order.  Each bin's summation order is fixed by the box, the thread, wave and
+ * slot indices and the data, so equal inputs give equal bits on every run, and a box's words
+ * depend neither on the other boxes nor on which other quantities are requested.
+ * `workspace`: device memory of of3d_flow_whist_workspace_bytes(rois, n_roi, nbins) bytes — the
+ * edges, then one slot of sum(nbins) float64 per workgroup of every box; host arithmetic only,
+ * 0 (and of3d_last_error's text) for an invalid box or no bins.  Enqueued on `stream`; no host
+ * copy, no host synchronisation, no workgroup waits for another. */
+size_t of3d_flow_whist_result_bytes(int n_roi, const int* nbins);
+size_t of3d_flow_whist_workspace_bytes(const int64_t* rois, int n_roi, const int* nbins);
+int of3d_flow_whist(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32, int rel_f64,
+                    int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                    double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const int* nbins,
+                    const double* const* edges, void* d_result, void* workspace, void* stream);
 
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order

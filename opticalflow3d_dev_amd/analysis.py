@@ -111,11 +111,13 @@ def flow_statistics(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0,
 # plot_figure3_ROIfigures.m:114-193, plot_FigureS2_dt.m:199-222, notebook cells 4-6)
 # — a reliability percentile, then per ROI the valid count, the mean magnitude, the
 # (magnitude-weighted) circular mean of theta and histograms — computed on the
-# resident fields.  Histograms are plain counts: the magnitude-weighted phi
-# distribution of figure 4 needs floating-point accumulation per bin and is not
-# provided.  The scripts' clean-up of the mask first, bwareaopen(rel > thresh, minSize)
-# (plot_figure4_timeTraces.m:75-79, plot_figure5.m:87-88), is min_size / connectivity
-# (csrc/kt_ccl.hip: of3d_mask_open, then of3d_flow_summary_masked).
+# resident fields.  `bins` gives plain counts; the magnitude-weighted phi distribution
+# of figure 4 (plot_figure4_timeTraces.m:128-138, distPhiW) is `weighted_bins`: float64
+# sums of the magnitude per bin, by a deterministic pass of its own (csrc/kt_whist.hip:
+# of3d_flow_whist; no floating-point atomics).  The scripts' clean-up of the mask first,
+# bwareaopen(rel > thresh, minSize) (plot_figure4_timeTraces.m:75-79, plot_figure5.m:87-88),
+# is min_size / connectivity (csrc/kt_ccl.hip: of3d_mask_open, then
+# of3d_flow_summary_masked).
 # ---------------------------------------------------------------------------
 QUANTITIES = ("vx", "vy", "vz", "magnitude", "theta", "phi")
 SUMS = ("sum_magnitude", "sum_vx", "sum_vy", "sum_vz", "sum_sin", "sum_cos", "sum_mag_sin", "sum_mag_cos")
@@ -178,7 +180,10 @@ class SummarySpec:
     sign flips along a movie; the mask's own axes are reported either way.  axes_physical: the
     covariance in physical units (xyscale, xyscale, zscale) before the decomposition.
     axis_bins: "axis1" / "axis2" / "axis3" -> ascending bin edges of the projections'
-    histograms (at most 256 bins; axis3 in 3D only).  None: nothing of this is computed."""
+    histograms (at most 256 bins; axis3 in 3D only).  None: nothing of this is computed.
+    weighted_bins: quantity name -> ascending bin edges, as `bins`, for magnitude-weighted
+    histograms, np.histogram(values, bins=edges, weights=magnitude) (of3d_flow_whist); the same
+    quantity may appear in both."""
     rois: list | None = None
     bins: dict | None = None
     rel_percentile: float = 90
@@ -190,6 +195,31 @@ class SummarySpec:
     axes: object = None
     axes_physical: bool = False
     axis_bins: dict | None = None
+    weighted_bins: dict | None = None
+
+    @staticmethod
+    def _quantity_bins(bins, ndim, kind=""):
+        """Validated (nbins [6], edges [6 arrays or None]) of a `bins` / `weighted_bins` dict
+        (kind: "" / "weighted ", for the messages)."""
+        nbins, edges = [0] * len(QUANTITIES), [None] * len(QUANTITIES)
+        for name, e in (bins or {}).items():
+            if name not in QUANTITIES:
+                raise ValueError(f"summary: unknown {kind}histogram quantity {name!r} (one of {QUANTITIES})")
+            if ndim == 2 and name in ("vz", "phi"):
+                raise ValueError(f"summary: a {kind}{name} histogram needs a 3D volume")
+            e = np.ascontiguousarray(e, dtype=np.float64)
+            if e.ndim != 1 or e.size < 2 or e.size > MAX_BINS + 1:
+                raise ValueError(f"summary: {kind}{name} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
+            if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
+                raise ValueError(f"summary: {kind}{name} bin edges must be strictly ascending")
+            q = QUANTITIES.index(name)
+            nbins[q], edges[q] = e.size - 1, e
+        return nbins, edges
+
+    def weighted(self, ndim):
+        """Validated (nbins [6], edges [6 arrays or None]) of weighted_bins for an ndim-D volume
+        (all 0 / None without any); ValueError on a bad name or bad edges."""
+        return self._quantity_bins(self.weighted_bins, ndim, "weighted ")
 
     def axes_request(self, ndim):
         """None without axes, else validated (given, nbins3, edges3): given = None for "mask" or
@@ -266,19 +296,8 @@ class SummarySpec:
             boxes.append(r)
         if len(boxes) > MAX_ROI:
             raise ValueError(f"summary: at most {MAX_ROI - 1} ROIs beside the whole volume, got {len(boxes) - 1}")
-        nbins, edges = [0] * len(QUANTITIES), [None] * len(QUANTITIES)
-        for name, e in (self.bins or {}).items():
-            if name not in QUANTITIES:
-                raise ValueError(f"summary: unknown histogram quantity {name!r} (one of {QUANTITIES})")
-            if ndim == 2 and name in ("vz", "phi"):
-                raise ValueError(f"summary: a {name} histogram needs a 3D volume")
-            e = np.ascontiguousarray(e, dtype=np.float64)
-            if e.ndim != 1 or e.size < 2 or e.size > MAX_BINS + 1:
-                raise ValueError(f"summary: {name} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
-            if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
-                raise ValueError(f"summary: {name} bin edges must be strictly ascending")
-            q = QUANTITIES.index(name)
-            nbins[q], edges[q] = e.size - 1, e
+        nbins, edges = self._quantity_bins(self.bins, ndim)
+        self.weighted(ndim)
         return np.array(boxes, dtype=np.int64), nbins, edges
 
 
@@ -364,6 +383,48 @@ class _AxesCall:
         return out
 
 
+class _WhistCall:
+    """of3d_flow_whist bound to boxes and a device: sizes, the workspace and the decoding."""
+
+    def __init__(self, boxes, dims, rel_f64, nbins, edges, scales, device):
+        import torch
+
+        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
+        self.nbins, self.edges = list(nbins), list(edges)
+        self.scales = tuple(float(v) for v in scales)
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
+        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        D = ctypes.POINTER(ctypes.c_double)
+        self.nb_arr = (ctypes.c_int * 6)(*self.nbins)
+        self.edge_arr = (D * 6)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
+        nbytes = self.lib.of3d_flow_whist_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr)
+        if nbytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.result_bytes = self.lib.of3d_flow_whist_result_bytes(len(self.boxes), self.nb_arr)
+
+    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+        """The accumulation and final kernels on `stream` (device pointers)."""
+        _lib.check(self.lib.of3d_flow_whist(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
+                                            thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
+                                            keep_ptr or None, self.nb_arr, self.edge_arr, result_ptr,
+                                            self.ws.data_ptr(), stream or None))
+
+    def decode(self, words, out):
+        """The block's words (host int64) added to the dict `out` (flow_summary's keys)."""
+        n_roi, ntot = len(self.boxes), sum(self.nbins)
+        body = np.ascontiguousarray(words[:n_roi * (1 + ntot)], dtype=np.int64).reshape(n_roi, 1 + ntot)
+        assert np.array_equal(body[:, 0], out["n_valid"]), (body[:, 0], out["n_valid"])
+        out["hist_weighted"], out["edges_weighted"] = {}, {}
+        off = 1
+        for q, name in enumerate(QUANTITIES):
+            if self.nbins[q]:
+                out["hist_weighted"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.float64)
+                out["edges_weighted"][name] = self.edges[q].copy()
+                off += self.nbins[q]
+        return out
+
+
 class _SummaryCall:
     """One resolved spec bound to a device: sizes, workspaces and the kernel launches."""
 
@@ -390,7 +451,14 @@ class _SummaryCall:
             self.axes = _AxesCall(self.boxes, self.dims, self.rel_f64, request, spec.axes_physical,
                                   (spec.xyscale, spec.zscale, spec.tscale), device)
             self.result_bytes += self.axes.result_bytes
-        self.open = _OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
+        # then (weighted_bins) of3d_flow_whist's block
+        wnbins, wedges = spec.weighted(len(self.shape))
+        self.whist, self.whist_off = None, self.result_bytes
+        if any(wnbins):
+            self.whist = _WhistCall(self.boxes, self.dims, self.rel_f64, wnbins, wedges,
+                                    (spec.xyscale, spec.zscale, spec.tscale), device)
+            self.result_bytes += self.whist.result_bytes
+        self.open =_OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
                               device) if self.min_size else None
         self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
         self.qws = torch.empty(lib.of3d_quantile_workspace_bytes(self.rel_f64), dtype=torch.uint8, device=device)
@@ -421,6 +489,10 @@ class _SummaryCall:
             self.axes.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
                               self.open.keep.data_ptr() if self.open is not None else None,
                               result_ptr + self.axes_off, stream)
+        if self.whist is not None:
+            self.whist.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+                               self.open.keep.data_ptr() if self.open is not None else None,
+                               result_ptr + self.whist_off, stream)
 
     def decode(self, words):
         """The result words (host int64 array) as flow_summary's dict."""
@@ -453,6 +525,8 @@ class _SummaryCall:
                 out[k] = counts[:, i].copy()
         if self.axes is not None:
             self.axes.decode(words[self.axes_off // 8:], out)
+        if self.whist is not None:
+            self.whist.decode(words[self.whist_off // 8:], out)
         return out
 
 
@@ -564,7 +638,8 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
 
 
 def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None,
-                 device=None, min_size=0, connectivity=None, axes=None, axes_physical=False, axis_bins=None):
+                 device=None, min_size=0, connectivity=None, axes=None, axes_physical=False, axis_bins=None,
+                 weighted_bins=None):
     """One frame reduced on the device to a few kilobytes (one small device->host copy).
 
     Inputs as flow_statistics (numpy arrays or torch tensors, vz None for 2D).  The masking is
@@ -582,6 +657,13 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     mask's integer moments (moments, n_axes_mask), centroid, covariance (3, 3), axis_values,
     axis_vectors (row k: e_k as x y z), axes_used (those, or the given array), and the flow
     projected on axes_used: n_axes_valid, sum_axis1..3, mean_axis1..3, hist["axis1"]...
+    weighted_bins (quantity -> edges, as bins): hist_weighted[name] (n_roi, nbins) float64 =
+    np.histogram(values, bins=edges, weights=magnitude)[0] over the valid voxels (the same mask,
+    opened when min_size >= 1), with edges_weighted[name].  Figure 4's magnitude-weighted phi
+    trace (plot_figure4_timeTraces.m:128-138, distPhiW) is hist_weighted["phi"] / n_valid[:, None].
+    The script bins -phi into phiBins: pass weighted_bins={"phi": -phiBins[::-1]} and reverse
+    the bins (hist_weighted["phi"][:, ::-1]); the bins are then right-closed where discretize's
+    are left-closed, which differs only for a value exactly on an edge.
     Bit-reproducible: the same inputs give the same bits on every run."""
     import torch
 
@@ -595,7 +677,7 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     if tx.dim() != (3 if tz is not None else 2):
         raise ValueError("flow_summary needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
     spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale, min_size, connectivity, axes,
-                       axes_physical, axis_bins)
+                       axes_physical, axis_bins, weighted_bins)
     call = _SummaryCall(spec, tuple(tx.shape), tr.dtype, tx.device)
     res = call.new_result(tx.device)
     call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
@@ -634,7 +716,8 @@ def write_summaries(prefix, frames, summaries):
     """<prefix>_summary.csv (one row per frame and ROI; floats as repr, so they read back
     exactly; the columns CSV_COLUMNS, then CSV_OPEN_COLUMNS when the summaries were made with
     min_size >= 1, then CSV_AXES_COLUMNS when they were made with axes) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
-    (frames, n_roi, nbins)) from flow_summary dicts of consecutive frames."""
+    (frames, n_roi, nbins), and with weighted_bins wedges_<name>, weights_<name> float64 of that
+    shape) from flow_summary dicts of consecutive frames."""
     opened = bool(summaries) and all(k in summaries[0] for k in CSV_OPEN_COLUMNS)
     with_axes = bool(summaries) and "axes_used" in summaries[0]
     with open(prefix + "_summary.csv", "w", newline="") as f:
@@ -655,6 +738,9 @@ def write_summaries(prefix, frames, summaries):
         for name, e in summaries[0]["edges"].items():
             arrays["edges_" + name] = e
             arrays["counts_" + name] = np.stack([s["hist"][name] for s in summaries])
+        for name, e in summaries[0].get("edges_weighted", {}).items():
+            arrays["wedges_" + name] = e
+            arrays["weights_" + name] = np.stack([s["hist_weighted"][name] for s in summaries])
     np.savez(prefix + "_summary_hist.npz", **arrays)
 
 

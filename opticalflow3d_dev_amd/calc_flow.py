@@ -206,7 +206,9 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     with min_size >= 1 opens every ROI's reliability mask first (bwareaopen, as the figure
     scripts do) and appends the columns n_mask, n_components, n_components_kept, n_kept.  A
     spec with axes adds the mask's moments, centroid, covariance and principal axes and the flow
-    projected onto them (analysis.CSV_AXES_COLUMNS; counts_axis* / edges_axis* in the npz).  The
+    projected onto them (analysis.CSV_AXES_COLUMNS; counts_axis* / edges_axis* in the npz).  A
+    spec with weighted_bins adds the magnitude-weighted histograms to the npz (wedges_<name>,
+    weights_<name> float64 of shape (frames, n_roi, nbins)); the CSV is unchanged.  The
     stdout lines are the same in every mode.  Single process, device-ring path only: with
     several ranks, or a window that differs from the temporal taps, a summary raises
     ValueError.

@@ -1,0 +1,334 @@
+// kt_whist.hip — magnitude-weighted histograms of the frame summary (of3d_flow_whist): per box
+// and requested quantity np.histogram(values, bins=edges, weights=magnitude) over the valid
+// voxels, the reference's distPhiW (plot_figure4_timeTraces.m:128-138: accumarray of the
+// magnitudes over the discretized -phi).  A pass of its own over the fields, beside k_sum_boxes
+// (kt_summary.hip) as k_proj_boxes (kt_axes.hip) is: the per-voxel arithmetic, the bin search,
+// the walk and the workgroup partition are summary_dev.hpp's.
+//   k_whist_boxes  one quantity per blockIdx.z; per wave a private LDS bin array, filled by a
+//                  wave-uniform loop over the distinct bins among the lanes (no atomics)
+//   k_whist_final  a thread per (box, quantity, bin): the workgroups' slots in index order
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "../../include/of3d.h"
+#include "kernels.hpp"
+#include "summary_dev.hpp"
+
+namespace {
+
+using u64 = unsigned long long;
+
+#define WH_HIP(call)                                                                           \
+    do {                                                                                       \
+        hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+
+using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks;
+constexpr int kNQ = OF3D_SUMMARY_QUANTITIES;
+constexpr int kMaxBins = OF3D_SUMMARY_MAX_BINS, kMaxRoi = OF3D_SUMMARY_MAX_ROI;
+constexpr size_t kEdgeWordsMax = (size_t)kNQ * (kMaxBins + 1);
+constexpr int kEdgeChunk = 384;  // edges carried by one k_put_whist_edges launch (kernel arguments)
+
+// Requested quantities are numbered k = 0.. in QUANTITIES order; everything per quantity is
+// indexed by k.  Workspace: the edges (eo words), then the slots [roi][k][workgroup][bin].
+struct WhParams {
+    int nz, ny, nx, n_roi;
+    int box[kMaxRoi][6];      // z0 z1 y0 y1 x0 x1
+    int nb[kMaxRoi];          // workgroups of the box (of3dk::sum_workgroups)
+    long long soff[kMaxRoi];  // first slot word of the box: sum over earlier boxes of nb * ntot
+    int nq;                   // requested quantities
+    int q[kNQ];               // the quantity (0 vx .. 5 phi)
+    int nbins[kNQ];
+    int eoff[kNQ];  // first edge in the workspace's edge array
+    int hoff[kNQ];  // first bin among a box's bins
+    int ntot;       // bins of a box, all quantities
+    double sxy, sz, st;
+};
+
+struct EdgeChunk {
+    double e[kEdgeChunk];
+};
+
+// the edges travel as kernel arguments: stream-ordered, no host copy to wait for
+__global__ void k_put_whist_edges(double* __restrict__ dst, EdgeChunk c, int n) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
+}
+
+__device__ __forceinline__ double readlane_f64(double v, int src) {
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((u64)b >> 32), src);
+    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
+}
+
+// One voxel step of a wave: every lane holds a bin (-1: nothing to add) and a weight >= +0.0
+// (0.0 with bin -1).  All 64 lanes call this together and run the same number of iterations:
+// the loop condition is a ballot, so the shuffles inside see every lane.  Per distinct bin, in
+// the order of its first lane: the weights of the lanes holding it (0.0 in the others, exact
+// since weights are >= 0) added by the fixed shuffle tree of k_sum_boxes, then one plain
+// read-modify-write of the wave's own array by lane 0.  A bin held by a single lane skips the
+// tree: x + 0.0 == x bit for bit, so the tree would return that lane's weight unchanged.
+__device__ __forceinline__ void wave_add(double* __restrict__ mine, int bin, double wgt, int lane) {
+    u64 pending = __ballot(bin >= 0);
+    while (pending) {
+        const int leader = __ffsll(pending) - 1;
+        const int b = __builtin_amdgcn_readlane(bin, leader);
+        const bool match = bin == b;
+        const u64 mm = __ballot(match);
+        double v;
+        if (mm & (mm - 1)) {
+            v = match ? wgt : 0.0;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        } else {
+            v = readlane_f64(wgt, leader);
+        }
+        if (lane == 0) mine[b] += v;
+        pending &= ~mm;
+    }
+}
+
+// Grid (max workgroups of a box, n_roi, requested quantities).  Masked: the mask factor of a
+// voxel is bit `roi` of keep (of3d_mask_open) instead of rel > thr.  The voxel loop and
+// everything around wave_add is wave-uniform: invalid, out-of-range and tail lanes carry bin -1
+// and weight 0.0 instead of leaving the loop.
+template <typename VT, typename RelT, bool Masked>
+__global__ __launch_bounds__(kSumThreads) void k_whist_boxes(const VT* __restrict__ vx, const VT* __restrict__ vy,
+                                                             const VT* __restrict__ vz, const RelT* __restrict__ rel,
+                                                             const RelT* __restrict__ thr_p,
+                                                             const uint16_t* __restrict__ keep, WhParams P,
+                                                             const double* __restrict__ edges_g,
+                                                             double* __restrict__ slots, u64* __restrict__ result) {
+    const int roi = blockIdx.y, nb = P.nb[roi], k = blockIdx.z;
+    if ((int)blockIdx.x >= nb) return;
+    __shared__ double edges[kMaxBins + 1];
+    __shared__ double whist[kSumWaves][kMaxBins];
+    __shared__ unsigned nvalid_s;
+    const int q = P.q[k], nbins = P.nbins[k];
+    for (int i = threadIdx.x; i <= nbins; i += kSumThreads) edges[i] = edges_g[P.eoff[k] + i];
+    for (int i = threadIdx.x; i < kSumWaves * kMaxBins; i += kSumThreads) (&whist[0][0])[i] = 0.0;
+    if (threadIdx.x == 0) nvalid_s = 0;
+    __syncthreads();
+
+    const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
+    const unsigned dy = P.box[roi][3] - y0, dx = P.box[roi][5] - x0;
+    const long long R = (long long)(P.box[roi][1] - z0) * dy;
+    const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
+    const long long count = (r1 - r0) * dx;  // this workgroup's voxels (< 2^31: checked on the host)
+    of3dk::BoxWalk w(dy, dx, r0, threadIdx.x, kSumThreads);
+    const double thr = Masked ? 0.0 : (double)*thr_p;
+    const bool is3 = vz != nullptr;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* mine = whist[wave];
+    unsigned nvalid = 0;
+
+    constexpr int U = 4;
+    for (long long e0 = 0; e0 < count; e0 += (long long)U * kSumThreads) {  // the same trips in every lane
+        double fx[U], fy[U], fz[U], fr[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            fx[u] = fy[u] = fz[u] = fr[u] = 0.0;  // past the end: mask factor 0, not valid
+            if (e0 + threadIdx.x + (long long)u * kSumThreads < count) {
+                const size_t i = ((size_t)(z0 + w.z) * P.ny + (y0 + w.y)) * P.nx + (x0 + w.x);
+                if constexpr (Masked)
+                    fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
+                else
+                    fr[u] = (double)rel[i];
+                fx[u] = (double)vx[i];
+                fy[u] = (double)vy[i];
+                if (is3) fz[u] = (double)vz[i];
+            }
+            w.advance();
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
+            const double vxp = of3dk::masked_velocity(fx[u], m, P.sxy, P.st);
+            const double vyp = of3dk::masked_velocity(fy[u], m, P.sxy, P.st);
+            const double vzp = is3 ? of3dk::masked_velocity(fz[u], m, P.sz, P.st) : 0.0;
+            const double xy2 = vxp * vxp + vyp * vyp;
+            const double mag = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
+            const bool valid = mag == mag;  // badRows = isnan(mag)
+            nvalid += valid;
+            if (!__ballot(valid)) continue;  // wave-uniform: no lane of this wave has anything to add
+            const double v = of3dk::quantity_value(q, vxp, vyp, vzp, mag, sqrt(xy2));
+            const int bin = valid ? of3dk::find_bin(edges, nbins, v) : -1;
+            wave_add(mine, bin, bin >= 0 ? mag : 0.0, lane);
+        }
+    }
+
+    if (k == 0 && nvalid) atomicAdd(&nvalid_s, nvalid);
+    __syncthreads();
+    // the waves' arrays in wave order, into this workgroup's own slot
+    double* slot = slots + P.soff[roi] + ((long long)nb * P.hoff[k] + (long long)blockIdx.x * nbins);
+    for (int i = threadIdx.x; i < nbins; i += kSumThreads) {
+        double v = whist[0][i];
+        for (int j = 1; j < kSumWaves; ++j) v += whist[j][i];
+        slot[i] = v;
+    }
+    if (threadIdx.x == 0 && nvalid_s) atomicAdd(&result[(size_t)roi * (1 + P.ntot)], (u64)nvalid_s);
+}
+
+// Grid (ceil(ntot / 256), n_roi): thread i of a box owns bin i of its bins and adds that bin's
+// slots in workgroup-index order.
+__global__ __launch_bounds__(256) void k_whist_final(const double* __restrict__ slots, WhParams P,
+                                                     u64* __restrict__ result) {
+    const int roi = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.ntot) return;
+    int k = 0;
+    while (k + 1 < P.nq && i >= P.hoff[k + 1]) ++k;
+    const int nb = P.nb[roi], nbins = P.nbins[k];
+    const double* s = slots + P.soff[roi] + ((long long)nb * P.hoff[k] + (i - P.hoff[k]));
+    double v = s[0];
+    for (int b = 1; b < nb; ++b) v += s[(size_t)b * nbins];
+    result[(size_t)roi * (1 + P.ntot) + 1 + i] = (u64)__double_as_longlong(v);
+}
+
+bool bins_ok(const int* nbins) {
+    if (!nbins) return false;
+    for (int q = 0; q < kNQ; ++q)
+        if (nbins[q] < 0 || nbins[q] > kMaxBins) return false;
+    return true;
+}
+
+int total_bins(const int* nbins) {
+    int n = 0;
+    for (int q = 0; q < kNQ; ++q) n += nbins[q];
+    return n;
+}
+
+// The boxes as of3d_flow_summary validates them (dims NULL: against 2^31 alone) and their
+// workgroups; slot_words: the sum over the boxes of workgroups * ntot.
+int plan_boxes(const int64_t* rois, int n_roi, const int64_t* dims, int ntot, int* nb_out, long long* soff_out,
+               size_t* slot_words) {
+    if (!rois) return of3dk::set_error("of3d: null argument");
+    if (n_roi < 1 || n_roi > kMaxRoi) return of3dk::set_error("of3d: 1 to 16 ROI boxes");
+    size_t words = 0;
+    for (int r = 0; r < n_roi; ++r) {
+        int64_t ext[3];
+        for (int a = 0; a < 3; ++a) {
+            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
+            if (b0 < 0 || b0 >= b1 || b1 > (dims ? dims[a] : (int64_t)INT32_MAX))
+                return of3dk::set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
+            ext[a] = b1 - b0;
+        }
+        // a function of the box alone (never of the device): the summation order is fixed
+        const int64_t rows = ext[0] * ext[1];  // < 2^62
+        const int64_t big = INT64_MAX / 2;     // stands for any larger voxel count: the cap decides
+        const int64_t nb = of3dk::sum_workgroups(ext[2] > big / rows ? big : rows * ext[2], rows);
+        // a workgroup's share, at most ceil(rows / nb) rows of ext[2] voxels, must stay below lim
+        const int64_t lim = ((int64_t)1 << 31) - 4 * kSumThreads;
+        if ((rows + nb - 1) / nb >= (lim + ext[2] - 1) / ext[2])
+            return of3dk::set_error("of3d: ROI too large (2^31 voxels per workgroup)");
+        if (nb_out) nb_out[r] = (int)nb;
+        if (soff_out) soff_out[r] = (long long)words;
+        words += (size_t)nb * ntot;
+    }
+    *slot_words = words;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t of3d_flow_whist_result_bytes(int n_roi, const int* nbins) {
+    if (n_roi < 1 || n_roi > kMaxRoi || !bins_ok(nbins)) return 0;
+    return (size_t)n_roi * (1 + total_bins(nbins)) * 8;
+}
+
+size_t of3d_flow_whist_workspace_bytes(const int64_t* rois, int n_roi, const int* nbins) {
+    if (!bins_ok(nbins)) {
+        of3dk::set_error("of3d: 0 to 256 bins per quantity");
+        return 0;
+    }
+    const int ntot = total_bins(nbins);
+    if (!ntot) {
+        of3dk::set_error("of3d: a weighted histogram needs bins for at least one quantity");
+        return 0;
+    }
+    size_t slot_words = 0, edge_words = 0;
+    if (plan_boxes(rois, n_roi, nullptr, ntot, nullptr, nullptr, &slot_words) != 0) return 0;
+    for (int q = 0; q < kNQ; ++q) edge_words += nbins[q] ? nbins[q] + 1 : 0;
+    return (edge_words + slot_words) * sizeof(double);
+}
+
+int of3d_flow_whist(const void* vx, const void* vy, const void* vz, const void* rel, int v_f32, int rel_f64,
+                    int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                    double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const int* nbins,
+                    const double* const* edges, void* d_result, void* workspace, void* stream) {
+    if (!vx || !vy || !rois || !d_result || !workspace || (!d_keep && (!rel || !d_thresh)))
+        return of3dk::set_error("of3d: null argument");
+    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
+        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
+    if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (!bins_ok(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
+    if (!vz && (nbins[2] || nbins[5])) return of3dk::set_error("of3d: vz and phi histograms need a 3D volume");
+    WhParams P;
+    memset(&P, 0, sizeof(P));
+    P.nz = (int)nz, P.ny = (int)ny, P.nx = (int)nx, P.n_roi = n_roi;
+    P.sxy = xyscale, P.sz = zscale, P.st = tscale;
+    P.ntot = total_bins(nbins);
+    if (!P.ntot) return of3dk::set_error("of3d: a weighted histogram needs bins for at least one quantity");
+    const int64_t dims[3] = {nz, ny, nx};
+    size_t slot_words = 0;
+    if (plan_boxes(rois, n_roi, dims, P.ntot, P.nb, P.soff, &slot_words) != 0) return -1;
+    int max_nb = 1;
+    for (int r = 0; r < n_roi; ++r) {
+        for (int a = 0; a < 6; ++a) P.box[r][a] = (int)rois[r * 6 + a];
+        max_nb = P.nb[r] > max_nb ? P.nb[r] : max_nb;
+    }
+    int eo = 0, ho = 0;
+    double host_edges[kEdgeWordsMax];
+    for (int q = 0; q < kNQ; ++q) {
+        if (!nbins[q]) continue;
+        if (!edges || !edges[q]) return of3dk::set_error("of3d: bins requested without edges");
+        for (int i = 0; i <= nbins[q]; ++i) {
+            const double e = edges[q][i];
+            if (!(e == e) || (i && !(e > edges[q][i - 1])))
+                return of3dk::set_error("of3d: bin edges must ascend strictly and hold no NaN");
+            host_edges[eo + i] = e;
+        }
+        const int k = P.nq++;
+        P.q[k] = q, P.nbins[k] = nbins[q], P.eoff[k] = eo, P.hoff[k] = ho;
+        eo += nbins[q] + 1, ho += nbins[q];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* d_edges = (double*)workspace;
+    double* slots = d_edges + eo;
+    u64* res = (u64*)d_result;
+    WH_HIP(hipMemsetAsync(d_result, 0, of3d_flow_whist_result_bytes(n_roi, nbins), s));
+    for (int o = 0; o < eo; o += kEdgeChunk) {
+        EdgeChunk c;
+        const int cnt = eo - o < kEdgeChunk ? eo - o : kEdgeChunk;
+        memcpy(c.e, host_edges + o, sizeof(double) * cnt);
+        hipLaunchKernelGGL(k_put_whist_edges, dim3(1), dim3(kEdgeChunk), 0, s, d_edges + o, c, cnt);
+    }
+    const dim3 grid(max_nb, n_roi, P.nq);
+    auto launch = [&](auto vt, auto rt) {
+        using VT = decltype(vt);
+        using RT = decltype(rt);
+        if (d_keep)
+            hipLaunchKernelGGL((k_whist_boxes<VT, RT, true>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
+                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P,
+                               (const double*)d_edges, slots, res);
+        else
+            hipLaunchKernelGGL((k_whist_boxes<VT, RT, false>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
+                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P,
+                               (const double*)d_edges, slots, res);
+    };
+    if (v_f32)
+        rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
+    else
+        rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
+    hipLaunchKernelGGL(k_whist_final, dim3((P.ntot + 255) / 256, n_roi), dim3(256), 0, s, (const double*)slots, P, res);
+    WH_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

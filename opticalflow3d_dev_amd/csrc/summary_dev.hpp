@@ -1,15 +1,15 @@
 #pragma once
 // summary_dev.hpp — the per-voxel device helpers shared by the frame summary (kt_summary.hip:
-// k_sum_boxes) and the projected flow (kt_axes.hip: k_proj_boxes): one statement of the
-// masking arithmetic, the histogram bin search and the walk over a box, so the two passes
-// cannot drift apart.
+// k_sum_boxes), the projected flow (kt_axes.hip: k_proj_boxes) and the magnitude-weighted
+// histograms (kt_whist.hip: k_whist_boxes): one statement of the masking arithmetic, the
+// histogram bin search and the walk over a box, so the passes cannot drift apart.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 namespace of3dk {
 
-// The workgroup partition of a box's reduction (k_sum_boxes, k_proj_boxes): workgroup b of nb
+// The workgroup partition of a box's reduction (k_sum_boxes, k_proj_boxes, k_whist_boxes): workgroup b of nb
 // walks rows [b*R/nb, (b+1)*R/nb) of the box's R = dz*dy rows.  nb is a function of the box
 // alone (never of the device), so the summation order is fixed.
 constexpr int kSumThreads = 512, kSumWaves = kSumThreads / 64;
@@ -41,6 +41,20 @@ __device__ __forceinline__ double masked_velocity(double v, double m, double sca
     v = v * m;
     if (v == 0.0) v = __builtin_nan("");
     return (v * scale) / tscale;
+}
+
+// Quantity q of a valid voxel in of3d_flow_summary's order (0 vx, 1 vy, 2 vz, 3 magnitude,
+// 4 theta, 5 phi), from the physical velocities, the magnitude and h = sqrt(vx^2 + vy^2): the
+// values k_sum_boxes bins (kt_whist.hip bins the same ones, one quantity per workgroup)
+__device__ __forceinline__ double quantity_value(int q, double vxp, double vyp, double vzp, double mag, double h) {
+    switch (q) {
+        case 0: return vxp;
+        case 1: return vyp;
+        case 2: return vzp;
+        case 3: return mag;
+        case 4: return atan2(vyp, vxp);
+        default: return atan(vzp / h);
+    }
 }
 
 // A thread's voxel as (z, y, x) inside a box of dy rows of dx voxels per plane, advanced by
