@@ -59,7 +59,11 @@ enum of3d_dtype {
  * traffic; accuracy max|dv| <= 1e-4 max|v| against the fp64 result. */
 enum of3d_mode { OF3D_FP64_EXACT = 0, OF3D_REL_F64 = 0x100, OF3D_FP32 = 0x200 };
 
-/* Filter taps (calc_flow.py:230-267).  Each vector has 2r+1 entries. */
+/* Filter taps (calc_flow.py:230-267).  Each vector has 2r+1 entries.
+ * The reference's taps have rs <= rd (rs = ceil(3*sig/4)), and the tiled gradient kernels
+ * stage an rd halo only.  Taps with rs > rd are accepted and run the general-radius path
+ * (of3d_plan_kernels reports "general"): same arithmetic, no tuned kernels; a plane range's
+ * input halo (of3d_plan_input_range) is then rw + max(rd, rs). */
 typedef struct of3d_taps {
     const double* gauss;  /* fderiv == fx, radius rd = ceil(3*sig)       (:233,:253) */
     const double* deriv;  /* fderiv*gderiv, radius rd, antisymmetric     (:239)      */
@@ -229,7 +233,12 @@ const char* of3d_stage_name(int i);
  * full length): the W-xy hand-off layout (wxy_zt: 0 plain planes, else z-tiled), the K34 shape
  * the autotune kept (staged columns, tile rows s, outputs per block, threads, candidates), the K5c
  * block (planes per z-group, waves), and of the LAST execution the K12 march length and grid and
- * the batched-K0 windows.  Diagnostics for tests and benchmarks (no reference counterpart). */
+ * the batched-K0 windows.  "runtime_radius": the template instances the runtime-radius kernels'
+ * getters pick for the plan's radii (k1_nj: k_grad_xy rows per thread; k3_tj, k4_tj: k_prod_wy /
+ * k_wx; k5 {r, nj}: k_wz_solve planes per thread and window rows per thread; k5_dma {nb, nj2}:
+ * k_wz_solve_dma window buffers, 0 where the register-staged k_wz_solve runs, and row groups
+ * per wave; general: the general-radius path runs instead, the others are 0).
+ * Diagnostics for tests and benchmarks (no reference counterpart). */
 int of3d_plan_geometry(const of3d_plan* plan, char* buf, size_t n);
 
 /* Copy `bytes` from src to dst on `stream` with a kernel of at most

@@ -361,8 +361,9 @@ class Plan:
         return [k for k in buf.value.decode().split(",") if k]
 
     def geometry(self):
-        """of3d_plan_geometry: the plan's kernel shapes (W-xy layout, K34, K5c) and the last
-        execution's K12 march / batched-K0 windows, as a dict."""
+        """of3d_plan_geometry: the plan's kernel shapes (W-xy layout, K34, K5c, the runtime-radius
+        kernels' instances under "runtime_radius") and the last execution's K12 march /
+        batched-K0 windows, as a dict."""
         n = check(self.lib.of3d_plan_geometry(self.handle, None, 0))
         buf = ctypes.create_string_buffer(n + 1)
         check(self.lib.of3d_plan_geometry(self.handle, buf, n + 1))

@@ -6,10 +6,11 @@ namespace of3dk {
 
 template <typename T, typename F>
 const void* k1_kernel(int rd) {
-    const int nj = (K1_TY + 2 * rd + 3) / 4;
-    if (nj <= 8) return (const void*)k_grad_xy<T, F, 8>;
-    if (nj <= 12) return (const void*)k_grad_xy<T, F, 12>;
-    return (const void*)k_grad_xy<T, F, 16>;
+    switch (k1_nj(rd)) {
+        case 8: return (const void*)k_grad_xy<T, F, 8>;
+        case 12: return (const void*)k_grad_xy<T, F, 12>;
+        default: return (const void*)k_grad_xy<T, F, 16>;
+    }
 }
 
 template <typename F>

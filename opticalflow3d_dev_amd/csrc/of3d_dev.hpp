@@ -2763,4 +2763,42 @@ int k5_dma_nb(int rw) {
     return 3 * buf <= lim ? 3 : (2 * buf <= lim ? 2 : 0);
 }
 
+// Rungs of the runtime-radius kernels: the template instance each getter (kt_*_legacy.hip)
+// picks for a radius.  The getters and of3d_plan_geometry's "runtime_radius" both call these,
+// so the report cannot drift from the launch.
+// k_grad_xy<T, F, NJ>: NJ rows per thread of the (K1_TY + 2 rd)-row staged strip, 4 waves
+constexpr int k1_nj(int rd) {
+    const int nj = (K1_TY + 2 * rd + 3) / 4;
+    return nj <= 8 ? 8 : (nj <= 12 ? 12 : 16);
+}
+// k_prod_wy<F, NP, TJ>: <= 24 for rw <= 48
+constexpr int k3_tj(int rw) {
+    const int tj = (2 * rw + 3) / 4;
+    return tj <= 8 ? 8 : (tj <= 12 ? 12 : 24);
+}
+// k_wx<F, NF, TJ>: <= 3 for rw <= 48
+constexpr int k4_tj(int rw) {
+    const int tj = (2 * k4_halo(rw) + 31) / 32;
+    return tj <= 1 ? 1 : (tj == 2 ? 2 : 3);
+}
+// k_wz_solve<F, RelT, NJ, R, 8>: NJ rows per thread of the staged window, ceil((G R + 2 rw) / G)
+constexpr int k5_nj(int rw) {
+    if (k5_geom(rw).r == 8) return rw <= 16 ? 12 : 14;
+    const int nj = (8 * 4 + 2 * rw + 7) / 8;
+    return nj <= 10 ? 10 : (nj <= 12 ? 12 : 16);
+}
+// k_wz_solve_dma<F, RelT, NJ2, R, 8, NB>: NJ2 row groups per wave (fp64: <= 7 for rw <= 24,
+// <= 8 for rw <= 48; fp32: <= 4)
+template <typename F>
+constexpr int k5_dma_nj2(int rw) {
+    const K5Geom k = k5_geom(rw);
+    const int nj2 = (k5_groups<F>(rw) + k.g - 1) / k.g;
+    if constexpr (sizeof(F) == 8) {
+        if (k.r == 8) return nj2 <= 6 ? 6 : 7;
+        return nj2 <= 6 ? 6 : (nj2 <= 7 ? 7 : 8);
+    } else {
+        return nj2 <= 3 ? 3 : 4;
+    }
+}
+
 }  // namespace

@@ -626,9 +626,11 @@ int set_attrs_t(of3d_plan* p) {
 // Radii the tiled kernels cannot stage (the legacy K1's 64-wide strips need rd <= 24, every
 // tile at most 160 KiB of LDS, kMaxR for the tap padding) run the general-radius path
 // (k_corr_gen passes: the same arithmetic, any radius).  OF3D_GENERAL=1 forces it (tests).
+// So do caller-made taps with rs > rd: k_grad_xy stages an rd halo of rows and columns and
+// would run its smooth passes past it (make_taps never gives such taps: rs = ceil(3 sig / 4)).
 bool needs_general(const of3d_plan* p) {
     if (p->kn.general) return true;
-    if (p->rd > 24 || p->rs > kMaxR || p->rw > kMaxR) return true;
+    if (p->rd > 24 || p->rs > kMaxR || p->rw > kMaxR || p->rs > p->rd) return true;
     const size_t e = p->fp32 ? 4 : 8, lim = 160 * 1024;
     const size_t k3 = (size_t)(K3_STEP + 2 * p->rw) * 64 * e;
     const size_t k4 = (size_t)K4_ROWS * (((K4_TX + 2 * k4_halo(p->rw)) | 1) + (K4_TX + 1)) * e;
@@ -658,8 +660,9 @@ Ranges ranges(const of3d_plan* p, int64_t zo0, int64_t zo1) {
     }
     r.zg0 = std::max<int64_t>(zo0 - p->rw, 0);
     r.zg1 = std::min<int64_t>(zo1 + p->rw, p->nz);
-    r.zb0 = std::max<int64_t>(r.zg0 - p->rd, 0);
-    r.zb1 = std::min<int64_t>(r.zg1 + p->rd, p->nz);
+    const int rg = std::max(p->rd, p->rs);  // gradient z passes: G / D (rd) and S (rs <= rd but for caller-made taps)
+    r.zb0 = std::max<int64_t>(r.zg0 - rg, 0);
+    r.zb1 = std::min<int64_t>(r.zg1 + rg, p->nz);
     return r;
 }
 
@@ -1299,7 +1302,7 @@ int plan_create(of3d_plan** out, int ndim, int64_t nz, int64_t ny, int64_t nx, c
     OF3D_HIP(hipSetDevice(device));
     OF3D_HIP(hipDeviceGetAttribute(&p->ncu, hipDeviceAttributeMultiprocessorCount, device));
     int64_t mo = (max_out_planes <= 0 || max_out_planes > nz) ? nz : max_out_planes;
-    p->cap_planes = ndim == 2 ? mo : std::min<int64_t>(nz, mo + 2 * (p->rw + p->rd));
+    p->cap_planes = ndim == 2 ? mo : std::min<int64_t>(nz, mo + 2 * (p->rw + std::max(p->rd, p->rs)));
     p->fs = (size_t)p->cap_planes * ny * nx;
     if (set_attrs(p.get())) return -1;
     // the z-tiled W-xy hand-off wherever the fused K34 writes it and K5c reads it (nx a multiple
@@ -1716,17 +1719,28 @@ int of3d_plan_geometry(const of3d_plan* p, char* buf, size_t n) {
     if (!p) return fail("of3d: null plan");
     int smax = p->k34.s;
     for (const auto& k : p->k34_cand) smax = std::max(smax, k.s);
-    char tmp[768];
+    // the runtime-radius kernels' rungs for the plan's radii, from the functions their getters
+    // switch on (zeros on the general path, which launches none of them)
+    const bool rr = !p->general;
+    const int k5d_nj2 = !p->k5_nb ? 0 : (p->fp32 ? k5_dma_nj2<float>(p->rw) : k5_dma_nj2<double>(p->rw));
+    char rrs[256];
+    snprintf(rrs, sizeof(rrs),
+             "{\"k1_nj\": %d, \"k3_tj\": %d, \"k4_tj\": %d, \"k5\": {\"r\": %d, \"nj\": %d}, "
+             "\"k5_dma\": {\"nb\": %d, \"nj2\": %d}, \"general\": %s}",
+             rr ? k1_nj(p->rd) : 0, rr ? k3_tj(p->rw) : 0, rr ? k4_tj(p->rw) : 0, rr ? k5_geom(p->rw).r : 0,
+             rr ? k5_nj(p->rw) : 0, rr ? p->k5_nb : 0, rr ? k5d_nj2 : 0, p->general ? "true" : "false");
+    char tmp[1024];
     snprintf(tmp, sizeof(tmp),
              "{\"ndim\": %d, \"nz\": %lld, \"ny\": %lld, \"nx\": %lld, \"fp32\": %d, \"general\": %d, "
              "\"cap_planes\": %lld, \"wxy_zt\": %d, \"k34\": {\"cw\": %d, \"s\": %d, \"tx\": %d, \"nbx\": %d, "
              "\"threads\": %d, \"lds\": %zu, \"candidates\": %zu, \"s_max\": %d}, \"k5c\": {\"r\": %d, \"nw\": %d, "
-             "\"lds\": %zu}, \"k12\": {\"march\": %d, \"grid\": [%d, %d], \"deep\": %d}, \"k0_batch\": %d, \"ncu\": %d}",
+             "\"lds\": %zu}, \"k12\": {\"march\": %d, \"grid\": [%d, %d], \"deep\": %d}, \"k0_batch\": %d, \"ncu\": %d, "
+             "\"runtime_radius\": %s}",
              p->ndim, (long long)p->nz, (long long)p->ny, (long long)p->nx, (int)p->fp32, (int)p->general,
              (long long)p->cap_planes, p->wxy_zt, p->k34.cw, p->k34.s, p->k34.tx, p->k34.nbx,
              p->k34.nthr ? p->k34.nthr : p->k34.cw, p->k34.lds, p->k34_cand.size(), smax, p->k5c ? p->k5c_r : 0,
              p->k5c ? p->k5c_nw : 0, p->k5c_lds, p->last_k12_zc, p->last_k12_gx, p->last_k12_gy, p->last_k12_deep, p->last_k0m,
-             p->ncu);
+             p->ncu, rrs);
     const std::string out(tmp);
     if (buf && n) {
         const size_t k = std::min(n - 1, out.size());
