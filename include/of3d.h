@@ -455,6 +455,84 @@ int of3d_flow_whist(const void* d_vx, const void* d_vy, const void* d_vz, const 
                     double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const int* nbins,
                     const double* const* edges, void* d_result, void* workspace, void* stream);
 
+/* Area opening of the JOINT reliability mask of two channels (figure 3: myosin and actin):
+ *   relMask = (rel > prctile(rel(:),relPer)) | (rel1 > prctile(rel1(:),relPer));
+ *   relMask = relMask & (rel > 0) & (rel1 > 0);   relMask = bwareaopen(relMask, 10^5);
+ * (plot_figure3_ROIfigures.m:93-96, plot_figure3_ChannelCompare.m:137-140: one mask for both
+ * channels, "for a fair comparison of dot products, magnitude, etc.").  d_rel0, d_rel1: two
+ * fields of one dtype (rel_f64) and shape; d_thresh0, d_thresh1: one device element each of that
+ * dtype (of3d_quantile's output per channel).  For every box r the mask is
+ *   M_r = C(rel0 > *t0, rel1 > *t1) && ((double)rel0 > floor) && ((double)rel1 > floor)
+ * cropped to the box; C is OR for combine == 0 (the scripts'), AND for combine == 1, anything
+ * else is an error.  A NaN field value gives false (it fails the floor clause whatever the
+ * floor); a NaN threshold makes its own comparison false everywhere, so that under OR the other
+ * channel decides and under AND nothing passes.  The scripts' floor is 0; -INFINITY switches the
+ * clause off (only NaN and -inf then fail it); a NaN floor is an error.
+ * Everything after the predicate is of3d_mask_open's, by the same kernels: the components inside
+ * the box, min_size >= 1, connectivity 4 / 8 or 6 / 18 / 26, bit r of d_keep, d_counts[n_roi][4],
+ * the workspace of of3d_mask_open_workspace_bytes(rois, n_roi), stream ordering, no host
+ * synchronisation, no workgroup waiting for another.  d_keep has of3d_mask_open's format, so it
+ * also feeds of3d_flow_pair, of3d_mask_axes, of3d_flow_summary_masked and of3d_flow_whist.
+ * rel1 == rel0 with equal thresholds and floor -INFINITY gives of3d_mask_open's bits. */
+int of3d_mask_open_pair(const void* d_rel0, const void* d_thresh0, const void* d_rel1, const void* d_thresh1,
+                        int rel_f64, double floor, int combine, int64_t nz, int64_t ny, int64_t nx,
+                        const int64_t* rois, int n_roi, int64_t min_size, int connectivity, uint16_t* d_keep,
+                        int64_t* d_counts, void* workspace, void* stream);
+
+/* Two channels' flows of one frame compared over the same voxels, in one pass over both
+ * channels' fields: what the reference's figure 3 reduces them to
+ * (plot_figure3_ROIfigures.m:98-193, plot_figure3_ChannelCompare.m:142-164: the velocities under
+ * the joint mask, theta / theta1, mag / mag1, badRows = isnan(theta) | isnan(theta1), then per
+ * ROI the plain and magnitude-weighted circular means of both channels over ~badRows), with the
+ * per-voxel comparisons the scripts' joint mask is made for.  d_vx0.. / d_vx1..: the channels'
+ * fields, one dtype (v_f32), shape and set of scales (one acquisition); d_vz0 and d_vz1 both
+ * given, or both NULL: the in-plane mode, legal for any nz (figure 3 uses the in-plane magnitude
+ * and theta of a 3-slice volume).  d_keep (required): of3d_mask_open_pair's output, or any other
+ * keep volume; min_size 1 there gives the unopened mask.  rois as of3d_flow_summary's.
+ * Per voxel of box r, m = bit r of d_keep as 1.0 / 0.0:
+ *   every component of both channels: v*m, an exact zero -> NaN, (v*scale)/tscale;
+ *   mag_c = sqrt(vx^2 + vy^2 [+ vz^2]) in of3d_flow_summary's expression order;
+ *   valid <=> mag_0 and mag_1 are both not NaN (in-plane: ~(isnan(theta) | isnan(theta1)));
+ *   h_c = sqrt(vx_c^2 + vy_c^2), sn_c = vy_c/h_c, cs_c = vx_c/h_c;
+ *   dot = (vx0*vx1 + vy0*vy1) + vz0*vz1 (in-plane: without the z term);
+ *   cosine = dot / (mag0*mag1) — NOT clamped: rounding may leave it a few ulp beyond +-1, and
+ *     such a value falls outside histogram edges that end at +-1 (end the edges a little wider);
+ *   cosD = cs0*cs1 + sn0*sn1, sinD = cs0*sn1 - sn0*cs1, dtheta = atan2(sinD, cosD) (histogram only);
+ *   diff = sqrt(((vx1-vx0)^2 + (vy1-vy0)^2) + (vz1-vz0)^2);  dmagnitude = mag1 - mag0;
+ * plain multiplies and adds in the written order (no FMA).
+ *
+ * Result (device, of3d_flow_pair_result_bytes(n_roi, nbins4) bytes, 8-byte words, zeroed on the
+ * stream first), per box OF3D_PAIR_ROI_WORDS + sum(nbins4) words:
+ *    0       n_valid (int64)         1  n_voxels (int64)
+ *    2..9    channel 0: of3d_flow_summary's eight float64 sums over the valid voxels (magnitude,
+ *            vx, vy, vz [0 in-plane], sin(theta), cos(theta), magnitude*sin, magnitude*cos)
+ *   10..17   channel 1: the same
+ *   18..25   float64 sums of dot, cosine, mag0*mag1, mag0^2, mag1^2, sinD, cosD, diff
+ *   26..     uint64 histogram counts of dot, cosine, dtheta, dmagnitude (nbins4[q] words each;
+ *            np.histogram semantics, at most 256 bins, edges4: host double*[4]; all 0 is legal)
+ * atan2(sum sin, sum cos) and atan2(sum mag*sin, sum mag*cos) of a channel's block are the
+ * scripts' ch0_theta / ch0_thetaW (atan2 is invariant under the common positive factor 1/n).
+ * Deterministic under of3d_flow_summary's contract: its workgroup partition, per-thread
+ * accumulators in a fixed order, a fixed shuffle tree over the lanes, the waves' partials in wave
+ * order into the workgroup's own workspace slot, a second kernel adding a sum's slots in
+ * workgroup-index order; counts by integer atomics; no floating-point atomic.  Equal inputs give
+ * equal bits on every run, a box's words do not depend on the other boxes, and where every kept
+ * voxel is valid in both channels a channel's block is bitwise of3d_flow_summary_masked's for the
+ * same d_keep.
+ * `workspace`: device memory of of3d_flow_pair_workspace_bytes(rois, n_roi, nbins4) bytes — the
+ * edges, then one slot of 24 float64 per workgroup of every box; host arithmetic only, 0 (and
+ * of3d_last_error's text) for an invalid box, more than 16 boxes or a workgroup share of 2^31
+ * voxels or more.  Enqueued on `stream`; no host copy, no host synchronisation, no workgroup
+ * waits for another. */
+#define OF3D_PAIR_QUANTITIES 4 /* histograms: 0 dot, 1 cosine, 2 dtheta, 3 dmagnitude */
+#define OF3D_PAIR_ROI_WORDS 26
+size_t of3d_flow_pair_result_bytes(int n_roi, const int* nbins4);
+size_t of3d_flow_pair_workspace_bytes(const int64_t* rois, int n_roi, const int* nbins4);
+int of3d_flow_pair(const void* d_vx0, const void* d_vy0, const void* d_vz0, const void* d_vx1, const void* d_vy1,
+                   const void* d_vz1, int v_f32, int64_t nz, int64_t ny, int64_t nx, double xyscale, double zscale,
+                   double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const int* nbins4,
+                   const double* const* edges4, void* d_result, void* workspace, void* stream);
+
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order
  * x2 y2 z2 xy xz yz (calc_flow.py:352-354's matrix (x2 xy xz / xy y2 yz /

@@ -46,6 +46,7 @@ EXPORTED = (
     "of3d_mask_open", "of3d_mask_open_workspace_bytes", "of3d_flow_summary_masked",
     "of3d_mask_axes", "of3d_mask_axes_workspace_bytes", "of3d_mask_axes_result_bytes",
     "of3d_flow_whist", "of3d_flow_whist_workspace_bytes", "of3d_flow_whist_result_bytes",
+    "of3d_mask_open_pair", "of3d_flow_pair", "of3d_flow_pair_workspace_bytes", "of3d_flow_pair_result_bytes",
 )
 
 CSRC = os.path.join(_HERE, "csrc")
@@ -234,6 +235,17 @@ def load():
                                         ctypes.POINTER(i64), ctypes.c_int, P, ctypes.POINTER(ctypes.c_int),
                                         ctypes.POINTER(D), P, P, P]
         lib.of3d_flow_whist.restype = ctypes.c_int
+        lib.of3d_mask_open_pair.argtypes = [P, P, P, P, ctypes.c_int, d, ctypes.c_int, i64, i64, i64,
+                                            ctypes.POINTER(i64), ctypes.c_int, i64, ctypes.c_int, P, P, P, P]
+        lib.of3d_mask_open_pair.restype = ctypes.c_int
+        lib.of3d_flow_pair_result_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.of3d_flow_pair_result_bytes.restype = ctypes.c_size_t
+        lib.of3d_flow_pair_workspace_bytes.argtypes = [ctypes.POINTER(i64), ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_int)]
+        lib.of3d_flow_pair_workspace_bytes.restype = ctypes.c_size_t
+        lib.of3d_flow_pair.argtypes = [P, P, P, P, P, P, ctypes.c_int, i64, i64, i64, d, d, d, ctypes.POINTER(i64),
+                                       ctypes.c_int, P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(D), P, P, P]
+        lib.of3d_flow_pair.restype = ctypes.c_int
         lib.of3d_rel3d.argtypes = [P, i64, P, ctypes.c_int, P]
         lib.of3d_rel3d.restype = ctypes.c_int
         lib.of3d_copy_async.argtypes = [P, P, ctypes.c_size_t, ctypes.c_int, P]

@@ -130,6 +130,12 @@ OPEN_COUNTS = ("n_mask", "n_components", "n_components_kept", "n_kept")  # of3d_
 AXIS_NAMES = ("axis1", "axis2", "axis3")
 MOMENTS = ("n", "x", "y", "z", "xx", "yy", "zz", "xy", "xz", "yz")  # the integer sums of a box's result
 _AX_HEAD = 44  # a box's result words before its histograms (include/of3d.h)
+# of3d_flow_pair (csrc/kt_pair.hip): two channels over the joint mask (figure 3)
+PAIR_QUANTITIES = ("dot", "cosine", "dtheta", "dmagnitude")
+PAIR_SUMS = ("sum_dot", "sum_cosine", "sum_mag0_mag1", "sum_mag0_sq", "sum_mag1_sq", "sum_sin_dtheta",
+             "sum_cos_dtheta", "sum_diff")
+_PAIR_HEAD = 26  # a box's result words before its histograms (include/of3d.h)
+COMBINE = {"or": 0, "and": 1}  # of3d_mask_open_pair's combine
 
 
 def _np_dtype(t):
@@ -198,13 +204,14 @@ class SummarySpec:
     weighted_bins: dict | None = None
 
     @staticmethod
-    def _quantity_bins(bins, ndim, kind=""):
+    def _quantity_bins(bins, ndim, kind="", names=QUANTITIES):
         """Validated (nbins [6], edges [6 arrays or None]) of a `bins` / `weighted_bins` dict
-        (kind: "" / "weighted ", for the messages)."""
-        nbins, edges = [0] * len(QUANTITIES), [None] * len(QUANTITIES)
+        (kind: "" / "weighted ", for the messages); with names=PAIR_QUANTITIES (kind "pair ") the
+        four of channel_compare's `bins`."""
+        nbins, edges = [0] * len(names), [None] * len(names)
         for name, e in (bins or {}).items():
-            if name not in QUANTITIES:
-                raise ValueError(f"summary: unknown {kind}histogram quantity {name!r} (one of {QUANTITIES})")
+            if name not in names:
+                raise ValueError(f"summary: unknown {kind}histogram quantity {name!r} (one of {names})")
             if ndim == 2 and name in ("vz", "phi"):
                 raise ValueError(f"summary: a {kind}{name} histogram needs a 3D volume")
             e = np.ascontiguousarray(e, dtype=np.float64)
@@ -212,7 +219,7 @@ class SummarySpec:
                 raise ValueError(f"summary: {kind}{name} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
             if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
                 raise ValueError(f"summary: {kind}{name} bin edges must be strictly ascending")
-            q = QUANTITIES.index(name)
+            q = names.index(name)
             nbins[q], edges[q] = e.size - 1, e
         return nbins, edges
 
@@ -323,6 +330,13 @@ class _OpenCall:
                                            self.min_size, self.connectivity, self.keep.data_ptr(), counts_ptr,
                                            self.ws.data_ptr(), stream or None))
 
+    def enqueue_pair(self, rel0, thresh0_ptr, rel1, thresh1_ptr, floor, combine, counts_ptr, stream):
+        """of3d_mask_open_pair: the joint mask of two channels, opened like the single one."""
+        _lib.check(self.lib.of3d_mask_open_pair(rel0, thresh0_ptr, rel1, thresh1_ptr, self.rel_f64, float(floor),
+                                                int(combine), *self.dims, self.roi_arr, len(self.boxes),
+                                                self.min_size, self.connectivity, self.keep.data_ptr(), counts_ptr,
+                                                self.ws.data_ptr(), stream or None))
+
 
 class _AxesCall:
     """of3d_mask_axes bound to boxes and a device: sizes, the workspace and the decoding."""
@@ -421,6 +435,130 @@ class _WhistCall:
             if self.nbins[q]:
                 out["hist_weighted"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.float64)
                 out["edges_weighted"][name] = self.edges[q].copy()
+                off += self.nbins[q]
+        return out
+
+
+def _pair_options(floor, combine):
+    """Validated (floor, combine code) of the joint mask; ValueError on a bad value."""
+    if not isinstance(combine, str) or combine not in COMBINE:
+        raise ValueError(f"summary: combine {combine!r} is not one of {tuple(COMBINE)}")
+    try:
+        floor = float(floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"summary: floor {floor!r} is not a number") from None
+    if np.isnan(floor):
+        raise ValueError("summary: floor must not be NaN (-inf switches the clause off)")
+    return floor, COMBINE[combine]
+
+
+def _pair_spec(shape, rel_percentile, rois, min_size, connectivity):
+    """(boxes, dims, min_size, connectivity) of a two-channel call, validated by SummarySpec."""
+    spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
+    boxes = spec.resolve(shape)[0]
+    min_size, connectivity = spec.opening(len(shape))
+    if min_size < 1:
+        raise ValueError("summary: the joint mask needs min_size >= 1 (1: no opening)")
+    shape = tuple(int(v) for v in shape)
+    return boxes, (shape if len(shape) == 3 else (1,) + shape), min_size, connectivity
+
+
+class _PairCall:
+    """The two-channel comparison of one frame bound to boxes and a device: two of3d_quantile,
+    of3d_mask_open_pair, then of3d_flow_pair.  Holds the boxes, sizes, workspaces, the keep volume
+    and the result tensor: of3d_flow_pair's words, then the opening's 4 counts per box, then the
+    two thresholds (one word each, in rel's dtype) — one small download."""
+
+    def __init__(self, shape, rel_dtype, device, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None,
+                 bins=None, floor=0.0, combine="or", min_size=1, connectivity=None):
+        import torch
+
+        self.boxes, self.dims, min_size, connectivity = _pair_spec(shape, rel_percentile, rois, min_size, connectivity)
+        self.floor, self.combine = _pair_options(floor, combine)
+        self.nbins, self.edges = SummarySpec._quantity_bins(bins, len(shape), "pair ", PAIR_QUANTITIES)
+        self.scales = (float(xyscale), float(zscale), float(tscale))
+        lib = self.lib = _lib.load()
+        self.rel_f64 = int(rel_dtype == torch.float64)
+        self.rel_dt = np.dtype(np.float64 if self.rel_f64 else np.float32)
+        D = ctypes.POINTER(ctypes.c_double)
+        self.nb_arr = (ctypes.c_int * 4)(*self.nbins)
+        self.edge_arr = (D * 4)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
+        self.open = _OpenCall(self.boxes, self.dims, self.rel_f64, min_size, connectivity, device)
+        self.roi_arr = self.open.roi_arr
+        nbytes = lib.of3d_flow_pair_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr)
+        if nbytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.qws = torch.empty(lib.of3d_quantile_workspace_bytes(self.rel_f64), dtype=torch.uint8, device=device)
+        self.pair_bytes = lib.of3d_flow_pair_result_bytes(len(self.boxes), self.nb_arr)
+        self.counts_off = self.pair_bytes
+        self.thresh_off = self.counts_off + 32 * len(self.boxes)
+        # zeros for the padding beside float32 thresholds (every other byte is written per call);
+        # a blocking upload, so that no fill is pending on another stream than enqueue's
+        self.result = torch.zeros((self.thresh_off + 16) // 8, dtype=torch.int64).to(device)
+        self.n = int(np.prod(self.dims))
+        self.ranks = _linear_ranks(self.n, rel_percentile, self.rel_dt)
+
+    @property
+    def keep(self):
+        """The joint mask's keep volume (uint16, bit r: box r), as the last enqueue left it."""
+        return self.open.keep
+
+    def enqueue(self, ptrs0, ptrs1, v_f32, stream):
+        """Both channels' quantiles, the joint opening and the pair pass on `stream`.  ptrs0 /
+        ptrs1: device pointers (vx, vy, vz or None, rel) of the channels; vz None in both: the
+        in-plane mode.  Returns the result tensor (decode its host copy)."""
+        lo, hi, gamma = self.ranks
+        lib, res = self.lib, self.result.data_ptr()
+        t0, t1 = res + self.thresh_off, res + self.thresh_off + 8
+        for rel, t in ((ptrs0[3], t0), (ptrs1[3], t1)):
+            _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), t, self.qws.data_ptr(),
+                                         stream or None))
+        self.open.enqueue_pair(ptrs0[3], t0, ptrs1[3], t1, self.floor, self.combine, res + self.counts_off, stream)
+        _lib.check(lib.of3d_flow_pair(ptrs0[0], ptrs0[1], ptrs0[2] or None, ptrs1[0], ptrs1[1], ptrs1[2] or None,
+                                      int(v_f32), *self.dims, *self.scales, self.roi_arr, len(self.boxes),
+                                      self.open.keep.data_ptr(), self.nb_arr, self.edge_arr, res, self.ws.data_ptr(),
+                                      stream or None))
+        return self.result
+
+    def decode(self, words):
+        """The result words (host int64 array) as channel_compare's dict."""
+        words = np.ascontiguousarray(words, dtype=np.int64)
+        n_roi, ntot = len(self.boxes), sum(self.nbins)
+        body = words[:n_roi * (_PAIR_HEAD + ntot)].reshape(n_roi, _PAIR_HEAD + ntot)
+        th = words[self.thresh_off // 8:self.thresh_off // 8 + 2]
+        out = {"rois": self.boxes.copy(), "thresholds": np.array([th[i:i + 1].view(self.rel_dt)[0] for i in (0, 1)]),
+               "n_valid": body[:, 0].copy(), "n_voxels": body[:, 1].copy()}
+        counts = words[self.counts_off // 8:self.counts_off // 8 + 4 * n_roi].reshape(n_roi, 4)
+        for i, k in enumerate(OPEN_COUNTS):
+            out[k] = counts[:, i].copy()
+        sums = np.ascontiguousarray(body[:, 2:_PAIR_HEAD]).view(np.float64)
+        nv = out["n_valid"].astype(np.float64)
+        nv[nv == 0] = np.nan  # empty box: NaN means, no division warnings
+        for c in (0, 1):
+            ch = {k: sums[:, 8 * c + i].copy() for i, k in enumerate(SUMS)}
+            ch["mean_magnitude"] = ch["sum_magnitude"] / nv
+            ch["theta_mean"] = np.arctan2(ch["sum_sin"] / nv, ch["sum_cos"] / nv)
+            ch["theta_mean_weighted"] = np.arctan2(ch["sum_mag_sin"] / nv, ch["sum_mag_cos"] / nv)
+            out[f"ch{c}"] = ch
+        for i, k in enumerate(PAIR_SUMS):
+            out[k] = sums[:, 16 + i].copy()
+        out["mean_dot"] = out["sum_dot"] / nv
+        out["mean_cosine"] = out["sum_cosine"] / nv
+        out["dtheta_mean"] = np.arctan2(out["sum_sin_dtheta"] / nv, out["sum_cos_dtheta"] / nv)
+        out["mean_diff"] = out["sum_diff"] / nv
+        # Pearson's r of the two magnitudes from the five magnitude sums
+        s0, s1 = out["ch0"]["sum_magnitude"], out["ch1"]["sum_magnitude"]
+        cov = nv * out["sum_mag0_mag1"] - s0 * s1
+        var = (nv * out["sum_mag0_sq"] - s0 * s0) * (nv * out["sum_mag1_sq"] - s1 * s1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["magnitude_correlation"] = cov / np.sqrt(np.where(var > 0, var, np.nan))
+        out["hist"], out["edges"] = {}, {}
+        off = _PAIR_HEAD
+        for q, name in enumerate(PAIR_QUANTITIES):
+            if self.nbins[q]:
+                out["hist"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.uint64)
+                out["edges"][name] = self.edges[q].copy()
                 off += self.nbins[q]
         return out
 
@@ -581,6 +719,138 @@ def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connect
     for i, name in enumerate(OPEN_COUNTS):
         out[name] = counts[:, i].copy()
     return out
+
+
+def _rel_pair(rel0, rel1, device, what):
+    """Two rel fields as contiguous CUDA tensors of one dtype and shape (numpy input: uploaded);
+    TypeError / ValueError before anything reaches the device."""
+    import torch
+
+    host = isinstance(rel0, np.ndarray)
+    if host != isinstance(rel1, np.ndarray):
+        raise TypeError(f"{what}: both channels must be numpy arrays or both torch tensors")
+    names = {str(np.dtype(a.dtype)) if host else str(a.dtype).replace("torch.", "") for a in (rel0, rel1)}
+    if len(names) != 1 or not names <= {"float32", "float64"}:
+        raise TypeError(f"{what}: both rel fields must be float32, or both float64")
+    if tuple(rel0.shape) != tuple(rel1.shape) or len(rel0.shape) not in (2, 3):
+        raise ValueError(f"{what}: the rel fields must share one (nz, ny, nx) or (ny, nx) shape, got "
+                         f"{tuple(rel0.shape)} and {tuple(rel1.shape)}")
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    to = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host else a.contiguous()
+    return host, (lambda: (to(rel0), to(rel1)))
+
+
+def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor=0.0, combine="or", min_size=1,
+                           connectivity=None, rois=None, device=None):
+    """The opened JOINT reliability mask of two channels of one frame, per ROI: figure 3's
+    ``relMask = (rel > prctile(rel(:),relPer)) | (rel1 > prctile(rel1(:),relPer)); relMask =
+    relMask & (rel > 0) & (rel1 > 0); relMask = bwareaopen(relMask, 10^5)``
+    (plot_figure3_ROIfigures.m:93-96) on the device (of3d_mask_open_pair).
+
+    rel0, rel1: numpy arrays or CUDA tensors of one shape and dtype.  Each channel's threshold is
+    its own rel_percentile-th percentile (percentile_threshold_device; nothing goes to the host
+    before the counts) unless `thresholds` (two Python floats) is given.  floor: both fields must
+    exceed it (the scripts' 0; -inf switches the clause off); combine: "or" (the scripts') or
+    "and" of the two threshold tests.  A NaN in a field fails there; it also makes that channel's
+    percentile NaN, whose test then fails everywhere.  min_size, connectivity, rois and the
+    returned dict as reliability_mask, with `thresholds` (2 values of rel's dtype) in place of
+    `threshold`.  keep has reliability_mask's format: it feeds the same consumers."""
+    import torch
+
+    host, upload = _rel_pair(rel0, rel1, device, "joint_reliability_mask")
+    boxes, dims, min_size, connectivity = _pair_spec(tuple(rel0.shape), rel_percentile, rois, min_size, connectivity)
+    floor, combine = _pair_options(floor, combine)
+    if thresholds is not None and len(thresholds) != 2:
+        raise ValueError("joint_reliability_mask: thresholds must be two values, one per channel")
+    t0, t1 = upload()
+    call = _OpenCall(boxes, dims, t0.dtype == torch.float64, min_size, connectivity, t0.device)
+    with torch.cuda.device(t0.device):
+        if thresholds is None:
+            thresh = torch.empty(2, dtype=t0.dtype, device=t0.device)
+            for i, t in enumerate((t0, t1)):
+                percentile_threshold_device(t, rel_percentile, out=thresh[i:i + 1])
+        else:
+            thresh = torch.tensor([float(v) for v in thresholds], dtype=t0.dtype).to(t0.device)
+        counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=t0.device)
+        esz = thresh.element_size()
+        call.enqueue_pair(t0.data_ptr(), thresh.data_ptr(), t1.data_ptr(), thresh.data_ptr() + esz, floor, combine,
+                          counts.data_ptr(), torch.cuda.current_stream(t0.device).cuda_stream)
+        keep = call.keep.view(t0.shape)
+        counts = counts.cpu().numpy()
+        out = {"keep": keep.cpu().numpy() if host else keep, "rois": boxes.copy(),
+               "thresholds": thresh.cpu().numpy().astype(_np_dtype(t0))}
+    k = out["keep"]
+    if host:
+        out["mask"] = lambda r: ((k >> np.uint16(r)) & np.uint16(1)).astype(bool)
+    else:
+        out["mask"] = lambda r: ((k.view(torch.int16) >> r) & 1).bool()  # uint16 has no shifts in torch
+    for i, name in enumerate(OPEN_COUNTS):
+        out[name] = counts[:, i].copy()
+    return out
+
+
+def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None, floor=0.0,
+                    combine="or", min_size=1, connectivity=None, in_plane=False, device=None):
+    """Two channels' flows of one frame compared over the same voxels, reduced on the device to
+    a few kilobytes (one small device->host copy): figure 3 of the reference
+    (plot_figure3_ROIfigures.m:67-193, plot_figure3_ChannelCompare.m:111-164).
+
+    ch0, ch1: (vx, vy, vz or None, rel) of each channel, numpy arrays or CUDA tensors; all six
+    velocity fields share one dtype (float64 / float32) and the fields one shape, both rel one
+    dtype.  The mask is joint_reliability_mask's (rel_percentile per channel, floor, combine,
+    min_size, connectivity, rois); a voxel is valid when it is kept and both channels' magnitudes
+    are not NaN, so both channels are averaged over the same voxels.  in_plane: ignore vz
+    (magnitude = sqrt(vx^2 + vy^2), as the figure's scripts on their 3-slice volumes); 2D fields
+    are in-plane by nature.  bins: "dot" | "cosine" | "dtheta" | "dmagnitude" -> ascending edges
+    (np.histogram semantics, at most 256 bins).  The cosine is not clamped: rounding may leave it
+    a few ulp past +-1, outside edges that end exactly there.
+    Returns a dict of numpy values: rois, thresholds (2), per ROI n_valid, n_voxels, n_mask,
+    n_components, n_components_kept, n_kept; ch0 and ch1, each a dict of flow_summary's eight
+    sums (sum_magnitude .. sum_mag_cos) with mean_magnitude, theta_mean, theta_mean_weighted (the
+    scripts' ch0_theta / ch0_thetaW); the cross sums sum_dot, sum_cosine, sum_mag0_mag1,
+    sum_mag0_sq, sum_mag1_sq, sum_sin_dtheta, sum_cos_dtheta (of dtheta = theta1 - theta0),
+    sum_diff (|v1 - v0|); the derived mean_dot, mean_cosine, dtheta_mean = atan2(sum_sin_dtheta,
+    sum_cos_dtheta), mean_diff and magnitude_correlation (Pearson's r of the two magnitudes);
+    hist[name] (n_roi, nbins) uint64 with edges[name].  An empty box gives NaN means.
+    Bit-reproducible: the same inputs give the same bits on every run."""
+    import torch
+
+    ch0, ch1 = tuple(ch0), tuple(ch1)
+    if len(ch0) != 4 or len(ch1) != 4:
+        raise ValueError("channel_compare: a channel is (vx, vy, vz or None, rel)")
+    host, upload_rel = _rel_pair(ch0[3], ch1[3], device, "channel_compare")
+    if in_plane:
+        ch0, ch1 = (ch0[0], ch0[1], None, ch0[3]), (ch1[0], ch1[1], None, ch1[3])
+    if (ch0[2] is None) != (ch1[2] is None):
+        raise ValueError("channel_compare: vz of both channels or of neither")
+    shape = tuple(ch0[3].shape)
+    if ch0[2] is None and len(shape) == 3 and not in_plane:
+        raise ValueError("channel_compare: (nz, ny, nx) fields need vz, or in_plane=True")
+    if ch0[2] is not None and len(shape) == 2:
+        raise ValueError("channel_compare: (ny, nx) fields take no vz")
+    fields = [a for a in ch0[:3] + ch1[:3] if a is not None]
+    if any(isinstance(a, np.ndarray) != host for a in fields):
+        raise TypeError("channel_compare: all fields must be numpy arrays or all torch tensors")
+    names = {str(np.dtype(a.dtype)) if host else str(a.dtype).replace("torch.", "") for a in fields}
+    if len(names) != 1 or not names <= {"float32", "float64"}:
+        raise TypeError("channel_compare: all velocity fields must be float64, or all float32")
+    if any(tuple(a.shape) != shape for a in fields):
+        raise ValueError(f"channel_compare: every field must have the shape {shape}")
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    if not host:
+        dev = ch0[3].device
+    rel_dtype = torch.float64 if str(ch0[3].dtype).endswith("float64") else torch.float32
+    call = _PairCall(shape, rel_dtype, dev, rel_percentile, xyscale, zscale, tscale, rois, bins, floor, combine,
+                     min_size, connectivity)
+    to = lambda a: None if a is None else (torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host
+                                            else a.contiguous())
+    r0, r1 = upload_rel()
+    t0, t1 = [to(a) for a in ch0[:3]] + [r0], [to(a) for a in ch1[:3]] + [r1]
+    ptrs = lambda t: tuple(a.data_ptr() if a is not None else None for a in t)
+    with torch.cuda.device(dev):
+        res = call.enqueue(ptrs(t0), ptrs(t1), t0[0].dtype == torch.float32,
+                           torch.cuda.current_stream(dev).cuda_stream)
+        return call.decode(res.cpu().numpy())
 
 
 def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectivity=None, rois=None, physical=False,

@@ -1,7 +1,9 @@
 // kt_ccl.hip — area opening of the reliability mask (of3d_mask_open): MATLAB's
 // bwareaopen(rel > relThresh, minSize) of the reference's figure scripts
 // (plot_figure4_timeTraces.m:75-79, plot_figure5.m:87-88, plot_figure3_ROIfigures.m:96), per
-// ROI box, on the device.  Connected components by label-equivalence union-find: every
+// ROI box, on the device; of3d_mask_open_pair: the same opening of the joint mask of two
+// channels (plot_figure3_ROIfigures.m:93-96), which differs in the foreground test of phase 1
+// alone.  Connected components by label-equivalence union-find: every
 // component ends rooted at its smallest linear index, so the component sizes, the counts and
 // the kept mask are integers fixed by the input alone, whatever the dispatch order.
 // Stream-ordered end to end: one launch per phase, nothing returns to the host, no workgroup
@@ -98,11 +100,36 @@ __device__ __forceinline__ void unite(u32* L, u32 a, u32 b) {
     }
 }
 
+// The foreground tests of phase 1, at the voxel's index in the whole volume.  FgSingle:
+// of3d_mask_open's rel > thresh.  FgPair: of3d_mask_open_pair's joint test of two channels
+// (plot_figure3_ROIfigures.m:93-95): the two threshold tests combined by OR or AND, and both
+// fields above `floor`; a NaN field value fails the floor clause whatever the floor.
+template <typename RelT>
+struct FgSingle {
+    const RelT* __restrict__ rel;
+    const RelT* __restrict__ thr;
+    __device__ __forceinline__ bool operator()(size_t g) const { return rel[g] > *thr; }  // NaN on either side: false
+};
+
+template <typename RelT>
+struct FgPair {
+    const RelT* __restrict__ rel0;
+    const RelT* __restrict__ thr0;
+    const RelT* __restrict__ rel1;
+    const RelT* __restrict__ thr1;
+    double floor;
+    int combine;  // 0: OR, 1: AND
+    __device__ __forceinline__ bool operator()(size_t g) const {
+        const RelT a = rel0[g], b = rel1[g];
+        const bool p0 = a > *thr0, p1 = b > *thr1;
+        return (combine ? (p0 && p1) : (p0 || p1)) && (double)a > floor && (double)b > floor;
+    }
+};
+
 // Phase 1: label[i] = first index of i's x-run inside its wave (foreground), kBg (background);
 // size[i] = 0.
-template <typename RelT>
-__global__ __launch_bounds__(kCclThreads) void k_ccl_init(const RelT* __restrict__ rel, const RelT* __restrict__ thr_p,
-                                                          CclParams P, u32* __restrict__ label,
+template <typename Fg>
+__global__ __launch_bounds__(kCclThreads) void k_ccl_init(Fg is_fg, CclParams P, u32* __restrict__ label,
                                                           u32* __restrict__ size) {
     const u64 i64 = (u64)blockIdx.x * kCclThreads + threadIdx.x;
     const bool in = i64 < P.n;
@@ -110,7 +137,7 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_init(const RelT* __restrict
     bool fg = false, first = false;
     if (in) {
         const Vox v = locate(P, i);
-        fg = rel[v.g] > *thr_p;  // NaN on either side: false
+        fg = is_fg(v.g);
         first = v.x == 0;
     }
     const u64 b = __ballot(fg), rs = __ballot(first);
@@ -274,22 +301,11 @@ int check_boxes(const int64_t* rois, int n_roi, const int64_t dims[3], int64_t* 
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t of3d_mask_open_workspace_bytes(const int64_t* rois, int n_roi) {
-    int64_t vox[kMaxRoi], most = 0;
-    if (check_boxes(rois, n_roi, nullptr, vox) != 0) return 0;
-    for (int r = 0; r < n_roi; ++r) most = vox[r] > most ? vox[r] : most;
-    return (size_t)most * 2 * sizeof(u32);
-}
-
-int of3d_mask_open(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64_t nx, const void* d_thresh,
-                   const int64_t* rois, int n_roi, int64_t min_size, int connectivity, uint16_t* d_keep,
-                   int64_t* d_counts, void* workspace, void* stream) {
-    if (!d_rel || !d_thresh || !rois || !d_keep || !d_counts || !workspace)
-        return of3dk::set_error("of3d: null argument");
+// Everything of an opening but the argument checks of its foreground test: the phases per box,
+// phase 1 with `is_fg` (of3d_mask_open and of3d_mask_open_pair differ in nothing else).
+template <typename Fg>
+int open_launch(Fg is_fg, int64_t nz, int64_t ny, int64_t nx, const int64_t* rois, int n_roi, int64_t min_size,
+                int connectivity, uint16_t* d_keep, int64_t* d_counts, void* workspace, void* stream) {
     if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
         return of3dk::set_error("of3d: mask dims must lie in [1, 2^31)");
     if (min_size < 1) return of3dk::set_error("of3d: min_size must be at least 1");
@@ -318,12 +334,7 @@ int of3d_mask_open(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64
         P.min_size = (u64)min_size;
         const dim3 grid((unsigned)((P.n + kCclThreads - 1) / kCclThreads)), block(kCclThreads);
         u64* counts = (u64*)d_counts + (size_t)r * 4;
-        if (rel_f64)
-            hipLaunchKernelGGL(k_ccl_init<double>, grid, block, 0, s, (const double*)d_rel, (const double*)d_thresh, P,
-                               label, size);
-        else
-            hipLaunchKernelGGL(k_ccl_init<float>, grid, block, 0, s, (const float*)d_rel, (const float*)d_thresh, P,
-                               label, size);
+        hipLaunchKernelGGL(k_ccl_init<Fg>, grid, block, 0, s, is_fg, P, label, size);
         hipLaunchKernelGGL(k_ccl_merge, grid, block, 0, s, P, label);
         // the counting phases: a bounded grid that strides over the box (one atomic per workgroup
         // and count into the result, not one per 256 voxels)
@@ -333,6 +344,46 @@ int of3d_mask_open(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64
     }
     CCL_HIP(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t of3d_mask_open_workspace_bytes(const int64_t* rois, int n_roi) {
+    int64_t vox[kMaxRoi], most = 0;
+    if (check_boxes(rois, n_roi, nullptr, vox) != 0) return 0;
+    for (int r = 0; r < n_roi; ++r) most = vox[r] > most ? vox[r] : most;
+    return (size_t)most * 2 * sizeof(u32);
+}
+
+int of3d_mask_open(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64_t nx, const void* d_thresh,
+                   const int64_t* rois, int n_roi, int64_t min_size, int connectivity, uint16_t* d_keep,
+                   int64_t* d_counts, void* workspace, void* stream) {
+    if (!d_rel || !d_thresh || !rois || !d_keep || !d_counts || !workspace)
+        return of3dk::set_error("of3d: null argument");
+    if (rel_f64)
+        return open_launch(FgSingle<double>{(const double*)d_rel, (const double*)d_thresh}, nz, ny, nx, rois, n_roi,
+                           min_size, connectivity, d_keep, d_counts, workspace, stream);
+    return open_launch(FgSingle<float>{(const float*)d_rel, (const float*)d_thresh}, nz, ny, nx, rois, n_roi,
+                       min_size, connectivity, d_keep, d_counts, workspace, stream);
+}
+
+int of3d_mask_open_pair(const void* d_rel0, const void* d_thresh0, const void* d_rel1, const void* d_thresh1,
+                        int rel_f64, double floor, int combine, int64_t nz, int64_t ny, int64_t nx,
+                        const int64_t* rois, int n_roi, int64_t min_size, int connectivity, uint16_t* d_keep,
+                        int64_t* d_counts, void* workspace, void* stream) {
+    if (!d_rel0 || !d_thresh0 || !d_rel1 || !d_thresh1 || !rois || !d_keep || !d_counts || !workspace)
+        return of3dk::set_error("of3d: null argument");
+    if (combine != 0 && combine != 1) return of3dk::set_error("of3d: combine must be 0 (OR) or 1 (AND)");
+    if (floor != floor) return of3dk::set_error("of3d: floor must not be NaN (-INFINITY switches the clause off)");
+    if (rel_f64)
+        return open_launch(FgPair<double>{(const double*)d_rel0, (const double*)d_thresh0, (const double*)d_rel1,
+                                          (const double*)d_thresh1, floor, combine},
+                           nz, ny, nx, rois, n_roi, min_size, connectivity, d_keep, d_counts, workspace, stream);
+    return open_launch(FgPair<float>{(const float*)d_rel0, (const float*)d_thresh0, (const float*)d_rel1,
+                                     (const float*)d_thresh1, floor, combine},
+                       nz, ny, nx, rois, n_roi, min_size, connectivity, d_keep, d_counts, workspace, stream);
 }
 
 }  // extern "C"

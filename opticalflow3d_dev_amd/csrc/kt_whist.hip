@@ -28,7 +28,7 @@ using u64 = unsigned long long;
             return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
     } while (0)
 
-using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks;
+using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::plan_boxes;
 constexpr int kNQ = OF3D_SUMMARY_QUANTITIES;
 constexpr int kMaxBins = OF3D_SUMMARY_MAX_BINS, kMaxRoi = OF3D_SUMMARY_MAX_ROI;
 constexpr size_t kEdgeWordsMax = (size_t)kNQ * (kMaxBins + 1);
@@ -200,37 +200,6 @@ int total_bins(const int* nbins) {
     int n = 0;
     for (int q = 0; q < kNQ; ++q) n += nbins[q];
     return n;
-}
-
-// The boxes as of3d_flow_summary validates them (dims NULL: against 2^31 alone) and their
-// workgroups; slot_words: the sum over the boxes of workgroups * ntot.
-int plan_boxes(const int64_t* rois, int n_roi, const int64_t* dims, int ntot, int* nb_out, long long* soff_out,
-               size_t* slot_words) {
-    if (!rois) return of3dk::set_error("of3d: null argument");
-    if (n_roi < 1 || n_roi > kMaxRoi) return of3dk::set_error("of3d: 1 to 16 ROI boxes");
-    size_t words = 0;
-    for (int r = 0; r < n_roi; ++r) {
-        int64_t ext[3];
-        for (int a = 0; a < 3; ++a) {
-            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
-            if (b0 < 0 || b0 >= b1 || b1 > (dims ? dims[a] : (int64_t)INT32_MAX))
-                return of3dk::set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
-            ext[a] = b1 - b0;
-        }
-        // a function of the box alone (never of the device): the summation order is fixed
-        const int64_t rows = ext[0] * ext[1];  // < 2^62
-        const int64_t big = INT64_MAX / 2;     // stands for any larger voxel count: the cap decides
-        const int64_t nb = of3dk::sum_workgroups(ext[2] > big / rows ? big : rows * ext[2], rows);
-        // a workgroup's share, at most ceil(rows / nb) rows of ext[2] voxels, must stay below lim
-        const int64_t lim = ((int64_t)1 << 31) - 4 * kSumThreads;
-        if ((rows + nb - 1) / nb >= (lim + ext[2] - 1) / ext[2])
-            return of3dk::set_error("of3d: ROI too large (2^31 voxels per workgroup)");
-        if (nb_out) nb_out[r] = (int)nb;
-        if (soff_out) soff_out[r] = (long long)words;
-        words += (size_t)nb * ntot;
-    }
-    *slot_words = words;
-    return 0;
 }
 
 }  // namespace

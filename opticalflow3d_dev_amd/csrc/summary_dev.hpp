@@ -1,15 +1,20 @@
 #pragma once
 // summary_dev.hpp — the per-voxel device helpers shared by the frame summary (kt_summary.hip:
-// k_sum_boxes), the projected flow (kt_axes.hip: k_proj_boxes) and the magnitude-weighted
-// histograms (kt_whist.hip: k_whist_boxes): one statement of the masking arithmetic, the
-// histogram bin search and the walk over a box, so the passes cannot drift apart.
+// k_sum_boxes), the projected flow (kt_axes.hip: k_proj_boxes), the magnitude-weighted
+// histograms (kt_whist.hip: k_whist_boxes) and the two-channel comparison (kt_pair.hip:
+// k_pair_boxes): one statement of the masking arithmetic, the histogram bin search, the walk
+// over a box and the plan of the boxes' workgroups, so the passes cannot drift apart.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
+
+#include "../../include/of3d.h"
+#include "kernels.hpp"
 
 namespace of3dk {
 
-// The workgroup partition of a box's reduction (k_sum_boxes, k_proj_boxes, k_whist_boxes): workgroup b of nb
+// The workgroup partition of a box's reduction (k_sum_boxes, k_proj_boxes, k_whist_boxes, k_pair_boxes): workgroup b of nb
 // walks rows [b*R/nb, (b+1)*R/nb) of the box's R = dz*dy rows.  nb is a function of the box
 // alone (never of the device), so the summation order is fixed.
 constexpr int kSumThreads = 512, kSumWaves = kSumThreads / 64;
@@ -19,6 +24,40 @@ inline int64_t sum_workgroups(int64_t vox, int64_t rows) {
     int64_t nb = (vox + kSumVoxPerBlock - 1) / kSumVoxPerBlock;
     nb = nb > kSumMaxBlocks ? kSumMaxBlocks : nb;
     return nb > rows ? rows : nb;
+}
+
+// The boxes of a pass with per-workgroup workspace slots (of3d_flow_whist, of3d_flow_pair) as
+// of3d_flow_summary validates them (dims NULL: against 2^31 alone) and their workgroups;
+// soff_out[r]: the first slot word of box r, slot_words: the sum over the boxes of
+// workgroups * wg_words.
+inline int plan_boxes(const int64_t* rois, int n_roi, const int64_t* dims, int wg_words, int* nb_out,
+                      long long* soff_out, size_t* slot_words) {
+    constexpr int kMaxRoi = OF3D_SUMMARY_MAX_ROI;
+    if (!rois) return set_error("of3d: null argument");
+    if (n_roi < 1 || n_roi > kMaxRoi) return set_error("of3d: 1 to 16 ROI boxes");
+    size_t words = 0;
+    for (int r = 0; r < n_roi; ++r) {
+        int64_t ext[3];
+        for (int a = 0; a < 3; ++a) {
+            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
+            if (b0 < 0 || b0 >= b1 || b1 > (dims ? dims[a] : (int64_t)INT32_MAX))
+                return set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
+            ext[a] = b1 - b0;
+        }
+        // a function of the box alone (never of the device): the summation order is fixed
+        const int64_t rows = ext[0] * ext[1];  // < 2^62
+        const int64_t big = INT64_MAX / 2;     // stands for any larger voxel count: the cap decides
+        const int64_t nb = sum_workgroups(ext[2] > big / rows ? big : rows * ext[2], rows);
+        // a workgroup's share, at most ceil(rows / nb) rows of ext[2] voxels, must stay below lim
+        const int64_t lim = ((int64_t)1 << 31) - 4 * kSumThreads;
+        if ((rows + nb - 1) / nb >= (lim + ext[2] - 1) / ext[2])
+            return set_error("of3d: ROI too large (2^31 voxels per workgroup)");
+        if (nb_out) nb_out[r] = (int)nb;
+        if (soff_out) soff_out[r] = (long long)words;
+        words += (size_t)nb * wg_words;
+    }
+    *slot_words = words;
+    return 0;
 }
 
 // np.histogram(v, bins=e): e[i] <= v < e[i+1], the last bin closed; -1: dropped (outside, NaN)
