@@ -21,6 +21,25 @@ import numpy as np
 from . import _lib
 
 
+def _dtype_name(a):
+    """'float32', ... of a numpy array or a torch tensor."""
+    return str(a.dtype).replace("torch.", "")
+
+
+def _np_dtype(t):
+    return np.dtype(_dtype_name(t))
+
+
+def _to_device(a, host, dev):
+    """A field as a contiguous tensor: a numpy array (host) uploaded to dev, a tensor where it is;
+    None stays None."""
+    import torch
+
+    if a is None:
+        return None
+    return torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host else a.contiguous()
+
+
 def _linear_ranks(n, percentile, dt):
     """numpy's 'linear' percentile of n values of dtype dt as two 0-based ranks and a weight:
     (lo, hi, gamma) with lo <= hi <= n-1 and gamma of dtype dt, numpy's arithmetic in the array's
@@ -59,7 +78,7 @@ def percentile_threshold(rel, percentile):
     n = flat.numel()
     if n == 0:
         raise ValueError("percentile of an empty array")
-    dt = np.dtype(str(flat.dtype).replace("torch.", ""))
+    dt = _np_dtype(flat)
     if bool(torch.isnan(flat).any()):
         return dt.type(np.nan)
     lo, hi, gamma = _linear_ranks(n, percentile, dt)
@@ -81,9 +100,7 @@ def flow_statistics(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0,
 
     host = isinstance(vx, np.ndarray)
     dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    to = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host else a.contiguous()
-    tx, ty, tr = to(vx), to(vy), to(rel)
-    tz = to(vz) if vz is not None else None
+    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
     if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
         raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
     shape = tuple(tx.shape)
@@ -136,10 +153,6 @@ PAIR_SUMS = ("sum_dot", "sum_cosine", "sum_mag0_mag1", "sum_mag0_sq", "sum_mag1_
              "sum_cos_dtheta", "sum_diff")
 _PAIR_HEAD = 26  # a box's result words before its histograms (include/of3d.h)
 COMBINE = {"or": 0, "and": 1}  # of3d_mask_open_pair's combine
-
-
-def _np_dtype(t):
-    return np.dtype(str(t.dtype).replace("torch.", ""))
 
 
 def percentile_threshold_device(rel, percentile, out=None):
@@ -204,6 +217,16 @@ class SummarySpec:
     weighted_bins: dict | None = None
 
     @staticmethod
+    def _bin_edges(e, label):
+        """One histogram's edges as a validated float64 array (label: what the messages call it)."""
+        e = np.ascontiguousarray(e, dtype=np.float64)
+        if e.ndim != 1 or e.size < 2 or e.size > MAX_BINS + 1:
+            raise ValueError(f"summary: {label} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
+        if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
+            raise ValueError(f"summary: {label} bin edges must be strictly ascending")
+        return e
+
+    @staticmethod
     def _quantity_bins(bins, ndim, kind="", names=QUANTITIES):
         """Validated (nbins [6], edges [6 arrays or None]) of a `bins` / `weighted_bins` dict
         (kind: "" / "weighted ", for the messages); with names=PAIR_QUANTITIES (kind "pair ") the
@@ -214,13 +237,9 @@ class SummarySpec:
                 raise ValueError(f"summary: unknown {kind}histogram quantity {name!r} (one of {names})")
             if ndim == 2 and name in ("vz", "phi"):
                 raise ValueError(f"summary: a {kind}{name} histogram needs a 3D volume")
-            e = np.ascontiguousarray(e, dtype=np.float64)
-            if e.ndim != 1 or e.size < 2 or e.size > MAX_BINS + 1:
-                raise ValueError(f"summary: {kind}{name} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
-            if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
-                raise ValueError(f"summary: {kind}{name} bin edges must be strictly ascending")
             q = names.index(name)
-            nbins[q], edges[q] = e.size - 1, e
+            edges[q] = SummarySpec._bin_edges(e, kind + name)
+            nbins[q] = edges[q].size - 1
         return nbins, edges
 
     def weighted(self, ndim):
@@ -255,13 +274,9 @@ class SummarySpec:
                 raise ValueError(f"summary: unknown axis histogram {name!r} (one of {AXIS_NAMES})")
             if ndim == 2 and name == "axis3":
                 raise ValueError("summary: an axis3 histogram needs a 3D volume")
-            e = np.ascontiguousarray(e, dtype=np.float64)
-            if e.ndim != 1 or e.size < 2 or e.size > MAX_BINS + 1:
-                raise ValueError(f"summary: {name} edges must be a 1-D array of 2 to {MAX_BINS + 1} values")
-            if np.any(np.isnan(e)) or not np.all(e[1:] > e[:-1]):
-                raise ValueError(f"summary: {name} bin edges must be strictly ascending")
             k = AXIS_NAMES.index(name)
-            nbins[k], edges[k] = e.size - 1, e
+            edges[k] = self._bin_edges(e, name)
+            nbins[k] = edges[k].size - 1
         return given, nbins, edges
 
     def opening(self, ndim):
@@ -308,21 +323,60 @@ class SummarySpec:
         return np.array(boxes, dtype=np.int64), nbins, edges
 
 
-class _OpenCall:
+def _decode_hists(body, off, names, nbins, edges, view_dtype, hist, edges_out):
+    """The histograms of a result block: body (n_roi, words) int64, the requested ones of `names`
+    one after the other from column `off`; hist[name] (n_roi, nbins) viewed as view_dtype and
+    edges_out[name] filled."""
+    for q, name in enumerate(names):
+        if nbins[q]:
+            hist[name] = np.ascontiguousarray(body[:, off:off + nbins[q]]).view(view_dtype)
+            edges_out[name] = edges[q].copy()
+            off += nbins[q]
+
+
+def _decode_open_counts(words, n_roi, out):
+    """of3d_mask_open's d_counts (4 int64 words per box, from words[0]) as out[name] per box."""
+    counts = np.asarray(words[:4 * n_roi]).reshape(n_roi, 4)
+    for i, name in enumerate(OPEN_COUNTS):
+        out[name] = counts[:, i].copy()
+
+
+class _BoxCall:
+    """What every summary pass is bound to: the library, the boxes (int64 (n_roi, 6)) with their
+    ctypes view, the volume's dims (nz, ny, nx) and whether rel is float64."""
+
+    def __init__(self, boxes, dims, rel_f64):
+        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
+        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+    def _bind_bins(self, nbins, edges):
+        """nbins / edges (one entry per quantity, None without bins) kept, with their ctypes arrays."""
+        self.nbins, self.edges = list(nbins), list(edges)
+        D = ctypes.POINTER(ctypes.c_double)
+        self.nb_arr = (ctypes.c_int * len(self.nbins))(*self.nbins)
+        self.edge_arr = (D * len(self.edges))(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
+
+    @staticmethod
+    def _workspace(nbytes, device):
+        """A workspace of the size a *_workspace_bytes function gave; 0 is its refusal of the boxes."""
+        import torch
+
+        if nbytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+class _OpenCall(_BoxCall):
     """of3d_mask_open bound to boxes and a device: the keep volume and the label / size
     workspace, allocated once."""
 
     def __init__(self, boxes, dims, rel_f64, min_size, connectivity, device):
         import torch
 
-        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
+        super().__init__(boxes, dims, rel_f64)
         self.min_size, self.connectivity = int(min_size), int(connectivity)
-        self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
-        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-        nbytes = self.lib.of3d_mask_open_workspace_bytes(self.roi_arr, len(self.boxes))
-        if nbytes == 0:
-            raise ValueError("of3d: " + _lib.last_error())
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.ws = self._workspace(self.lib.of3d_mask_open_workspace_bytes(self.roi_arr, len(self.boxes)), device)
         self.keep = torch.empty(self.dims, dtype=torch.uint16, device=device)
 
     def enqueue(self, rel, thresh_ptr, counts_ptr, stream):
@@ -338,25 +392,17 @@ class _OpenCall:
                                                 self.ws.data_ptr(), stream or None))
 
 
-class _AxesCall:
+class _AxesCall(_BoxCall):
     """of3d_mask_axes bound to boxes and a device: sizes, the workspace and the decoding."""
 
     def __init__(self, boxes, dims, rel_f64, request, physical, scales, device):
-        import torch
-
-        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
-        self.given, self.nbins, self.edges = request
+        super().__init__(boxes, dims, rel_f64)
+        self.given = request[0]
+        self._bind_bins(*request[1:])
         self.physical, self.scales = int(bool(physical)), tuple(float(v) for v in scales)
-        self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
-        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-        D = ctypes.POINTER(ctypes.c_double)
-        self.nb_arr = (ctypes.c_int * 3)(*self.nbins)
-        self.edge_arr = (D * 3)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
-        self.given_arr = self.given.ctypes.data_as(D) if self.given is not None else None
-        nbytes = self.lib.of3d_mask_axes_workspace_bytes(self.roi_arr, len(self.boxes))
-        if nbytes == 0:
-            raise ValueError("of3d: " + _lib.last_error())
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.given_arr = (self.given.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+                          if self.given is not None else None)
+        self.ws = self._workspace(self.lib.of3d_mask_axes_workspace_bytes(self.roi_arr, len(self.boxes)), device)
         self.result_bytes = self.lib.of3d_mask_axes_result_bytes(len(self.boxes), self.nb_arr)
 
     def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
@@ -388,33 +434,19 @@ class _AxesCall:
         for k, name in enumerate(AXIS_NAMES):
             out["sum_" + name] = sums[:, k].copy()
             out["mean_" + name] = sums[:, k] / nv
-        off = _AX_HEAD
-        for k, name in enumerate(AXIS_NAMES):
-            if self.nbins[k]:
-                out["hist"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[k]]).view(np.uint64)
-                out["edges"][name] = self.edges[k].copy()
-                off += self.nbins[k]
+        _decode_hists(body, _AX_HEAD, AXIS_NAMES, self.nbins, self.edges, np.uint64, out["hist"], out["edges"])
         return out
 
 
-class _WhistCall:
+class _WhistCall(_BoxCall):
     """of3d_flow_whist bound to boxes and a device: sizes, the workspace and the decoding."""
 
     def __init__(self, boxes, dims, rel_f64, nbins, edges, scales, device):
-        import torch
-
-        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
-        self.nbins, self.edges = list(nbins), list(edges)
+        super().__init__(boxes, dims, rel_f64)
+        self._bind_bins(nbins, edges)
         self.scales = tuple(float(v) for v in scales)
-        self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
-        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-        D = ctypes.POINTER(ctypes.c_double)
-        self.nb_arr = (ctypes.c_int * 6)(*self.nbins)
-        self.edge_arr = (D * 6)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
-        nbytes = self.lib.of3d_flow_whist_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr)
-        if nbytes == 0:
-            raise ValueError("of3d: " + _lib.last_error())
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.ws = self._workspace(
+            self.lib.of3d_flow_whist_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr), device)
         self.result_bytes = self.lib.of3d_flow_whist_result_bytes(len(self.boxes), self.nb_arr)
 
     def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
@@ -430,12 +462,8 @@ class _WhistCall:
         body = np.ascontiguousarray(words[:n_roi * (1 + ntot)], dtype=np.int64).reshape(n_roi, 1 + ntot)
         assert np.array_equal(body[:, 0], out["n_valid"]), (body[:, 0], out["n_valid"])
         out["hist_weighted"], out["edges_weighted"] = {}, {}
-        off = 1
-        for q, name in enumerate(QUANTITIES):
-            if self.nbins[q]:
-                out["hist_weighted"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.float64)
-                out["edges_weighted"][name] = self.edges[q].copy()
-                off += self.nbins[q]
+        _decode_hists(body, 1, QUANTITIES, self.nbins, self.edges, np.float64, out["hist_weighted"],
+                      out["edges_weighted"])
         return out
 
 
@@ -463,7 +491,7 @@ def _pair_spec(shape, rel_percentile, rois, min_size, connectivity):
     return boxes, (shape if len(shape) == 3 else (1,) + shape), min_size, connectivity
 
 
-class _PairCall:
+class _PairCall(_BoxCall):
     """The two-channel comparison of one frame bound to boxes and a device: two of3d_quantile,
     of3d_mask_open_pair, then of3d_flow_pair.  Holds the boxes, sizes, workspaces, the keep volume
     and the result tensor: of3d_flow_pair's words, then the opening's 4 counts per box, then the
@@ -473,22 +501,16 @@ class _PairCall:
                  bins=None, floor=0.0, combine="or", min_size=1, connectivity=None):
         import torch
 
-        self.boxes, self.dims, min_size, connectivity = _pair_spec(shape, rel_percentile, rois, min_size, connectivity)
+        boxes, dims, min_size, connectivity = _pair_spec(shape, rel_percentile, rois, min_size, connectivity)
         self.floor, self.combine = _pair_options(floor, combine)
-        self.nbins, self.edges = SummarySpec._quantity_bins(bins, len(shape), "pair ", PAIR_QUANTITIES)
+        super().__init__(boxes, dims, rel_dtype == torch.float64)
+        self._bind_bins(*SummarySpec._quantity_bins(bins, len(shape), "pair ", PAIR_QUANTITIES))
         self.scales = (float(xyscale), float(zscale), float(tscale))
-        lib = self.lib = _lib.load()
-        self.rel_f64 = int(rel_dtype == torch.float64)
+        lib = self.lib
         self.rel_dt = np.dtype(np.float64 if self.rel_f64 else np.float32)
-        D = ctypes.POINTER(ctypes.c_double)
-        self.nb_arr = (ctypes.c_int * 4)(*self.nbins)
-        self.edge_arr = (D * 4)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
         self.open = _OpenCall(self.boxes, self.dims, self.rel_f64, min_size, connectivity, device)
-        self.roi_arr = self.open.roi_arr
-        nbytes = lib.of3d_flow_pair_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr)
-        if nbytes == 0:
-            raise ValueError("of3d: " + _lib.last_error())
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.ws = self._workspace(lib.of3d_flow_pair_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr),
+                                  device)
         self.qws = torch.empty(lib.of3d_quantile_workspace_bytes(self.rel_f64), dtype=torch.uint8, device=device)
         self.pair_bytes = lib.of3d_flow_pair_result_bytes(len(self.boxes), self.nb_arr)
         self.counts_off = self.pair_bytes
@@ -529,9 +551,7 @@ class _PairCall:
         th = words[self.thresh_off // 8:self.thresh_off // 8 + 2]
         out = {"rois": self.boxes.copy(), "thresholds": np.array([th[i:i + 1].view(self.rel_dt)[0] for i in (0, 1)]),
                "n_valid": body[:, 0].copy(), "n_voxels": body[:, 1].copy()}
-        counts = words[self.counts_off // 8:self.counts_off // 8 + 4 * n_roi].reshape(n_roi, 4)
-        for i, k in enumerate(OPEN_COUNTS):
-            out[k] = counts[:, i].copy()
+        _decode_open_counts(words[self.counts_off // 8:], n_roi, out)
         sums = np.ascontiguousarray(body[:, 2:_PAIR_HEAD]).view(np.float64)
         nv = out["n_valid"].astype(np.float64)
         nv[nv == 0] = np.nan  # empty box: NaN means, no division warnings
@@ -554,34 +574,26 @@ class _PairCall:
         with np.errstate(invalid="ignore", divide="ignore"):
             out["magnitude_correlation"] = cov / np.sqrt(np.where(var > 0, var, np.nan))
         out["hist"], out["edges"] = {}, {}
-        off = _PAIR_HEAD
-        for q, name in enumerate(PAIR_QUANTITIES):
-            if self.nbins[q]:
-                out["hist"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.uint64)
-                out["edges"][name] = self.edges[q].copy()
-                off += self.nbins[q]
+        _decode_hists(body, _PAIR_HEAD, PAIR_QUANTITIES, self.nbins, self.edges, np.uint64, out["hist"], out["edges"])
         return out
 
 
-class _SummaryCall:
+class _SummaryCall(_BoxCall):
     """One resolved spec bound to a device: sizes, workspaces and the kernel launches."""
 
     def __init__(self, spec, shape, rel_dtype, device):
         import torch
 
         self.spec, self.shape = spec, tuple(int(v) for v in shape)
-        self.boxes, self.nbins, self.edges = spec.resolve(shape)
+        boxes, nbins, edges = spec.resolve(shape)
         self.min_size, self.connectivity = spec.opening(len(self.shape))
-        self.dims = self.shape if len(self.shape) == 3 else (1,) + self.shape
-        lib = self.lib = _lib.load()
-        self.nb_arr = (ctypes.c_int * 6)(*self.nbins)
-        D = ctypes.POINTER(ctypes.c_double)
-        self.edge_arr = (D * 6)(*[e.ctypes.data_as(D) if e is not None else None for e in self.edges])
-        self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        super().__init__(boxes, self.shape if len(self.shape) == 3 else (1,) + self.shape,
+                         rel_dtype == torch.float64)
+        self._bind_bins(nbins, edges)
+        lib = self.lib
         # the summary words, then (min_size >= 1) of3d_mask_open's 4 counts per box: one download
         self.summary_bytes = lib.of3d_flow_summary_result_bytes(len(self.boxes), self.nb_arr)
         self.result_bytes = self.summary_bytes + (32 * len(self.boxes) if self.min_size else 0)
-        self.rel_f64 = int(rel_dtype == torch.float64)
         # then (axes) of3d_mask_axes' block
         request = spec.axes_request(len(self.shape))
         self.axes, self.axes_off = None, self.result_bytes
@@ -602,7 +614,7 @@ class _SummaryCall:
         self.qws = torch.empty(lib.of3d_quantile_workspace_bytes(self.rel_f64), dtype=torch.uint8, device=device)
         self.thresh = torch.empty(1, dtype=rel_dtype, device=device)
         self.n = int(np.prod(self.dims))
-        self.ranks = _linear_ranks(self.n, spec.rel_percentile, np.dtype(str(rel_dtype).replace("torch.", "")))
+        self.ranks = _linear_ranks(self.n, spec.rel_percentile, _np_dtype(self.thresh))
 
     def new_result(self, device):
         import torch
@@ -651,21 +663,43 @@ class _SummaryCall:
         out["theta_mean"] = np.arctan2(out["sum_sin"] / nv, out["sum_cos"] / nv)
         out["theta_mean_weighted"] = np.arctan2(out["sum_mag_sin"] / nv, out["sum_mag_cos"] / nv)
         out["hist"], out["edges"] = {}, {}
-        off = _ROI_HEAD
-        for q, name in enumerate(QUANTITIES):
-            if self.nbins[q]:
-                out["hist"][name] = np.ascontiguousarray(body[:, off:off + self.nbins[q]]).view(np.uint64)
-                out["edges"][name] = self.edges[q].copy()
-                off += self.nbins[q]
+        _decode_hists(body, _ROI_HEAD, QUANTITIES, self.nbins, self.edges, np.uint64, out["hist"], out["edges"])
         if self.min_size:
-            counts = words[self.summary_bytes // 8:self.summary_bytes // 8 + 4 * n_roi].reshape(n_roi, 4)
-            for i, k in enumerate(OPEN_COUNTS):
-                out[k] = counts[:, i].copy()
+            _decode_open_counts(words[self.summary_bytes // 8:], n_roi, out)
         if self.axes is not None:
             self.axes.decode(words[self.axes_off // 8:], out)
         if self.whist is not None:
             self.whist.decode(words[self.whist_off // 8:], out)
         return out
+
+
+def _thresholds_device(rels, rel_percentile, given):
+    """One threshold per rel field as a tensor of their dtype on their device: the `given` values,
+    or each field's rel_percentile-th percentile selected on the device (nothing goes to the host)."""
+    import torch
+
+    t = rels[0]
+    if given is not None:
+        return torch.tensor([float(v) for v in given], dtype=t.dtype).to(t.device)
+    thresh = torch.empty(len(rels), dtype=t.dtype, device=t.device)
+    for i, r in enumerate(rels):
+        percentile_threshold_device(r, rel_percentile, out=thresh[i:i + 1])
+    return thresh
+
+
+def _mask_dict(keep, host, boxes, counts):
+    """reliability_mask's dict but for the threshold(s): keep (numpy for host input), mask, rois
+    and the opening's counts per ROI (counts: the device tensor (n_roi, 4))."""
+    import torch
+
+    k = keep.cpu().numpy() if host else keep
+    out = {"keep": k, "rois": boxes.copy()}
+    if host:
+        out["mask"] = lambda r: ((k >> np.uint16(r)) & np.uint16(1)).astype(bool)
+    else:
+        out["mask"] = lambda r: ((k.view(torch.int16) >> r) & 1).bool()  # uint16 has no shifts in torch
+    _decode_open_counts(counts.cpu().numpy().reshape(-1), len(boxes), out)
+    return out
 
 
 def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connectivity=None, rois=None, device=None):
@@ -687,7 +721,7 @@ def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connect
 
     host = isinstance(rel, np.ndarray)
     dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    tr = torch.as_tensor(np.ascontiguousarray(rel)).to(dev) if host else rel.contiguous()
+    tr = _to_device(rel, host, dev)
     if tr.dtype not in (torch.float32, torch.float64):
         raise TypeError("rel must be float32 or float64")
     if tr.dim() not in (2, 3):
@@ -700,24 +734,12 @@ def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connect
     dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
     call = _OpenCall(boxes, dims, tr.dtype == torch.float64, min_size, connectivity, tr.device)
     with torch.cuda.device(tr.device):
-        if threshold is None:
-            thresh = percentile_threshold_device(tr, rel_percentile)
-        else:
-            thresh = torch.tensor([float(threshold)], dtype=tr.dtype).to(tr.device)
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
         counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tr.device)
         call.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(),
                      torch.cuda.current_stream(tr.device).cuda_stream)
-        keep = call.keep.view(tr.shape)
-        counts = counts.cpu().numpy()
-        out = {"keep": keep.cpu().numpy() if host else keep, "rois": boxes.copy(),
-               "threshold": _np_dtype(tr).type(thresh.cpu().numpy()[0])}
-    k = out["keep"]
-    if host:
-        out["mask"] = lambda r: ((k >> np.uint16(r)) & np.uint16(1)).astype(bool)
-    else:
-        out["mask"] = lambda r: ((k.view(torch.int16) >> r) & 1).bool()  # uint16 has no shifts in torch
-    for i, name in enumerate(OPEN_COUNTS):
-        out[name] = counts[:, i].copy()
+        out = _mask_dict(call.keep.view(tr.shape), host, boxes, counts)
+        out["threshold"] = _np_dtype(tr).type(thresh.cpu().numpy()[0])
     return out
 
 
@@ -729,15 +751,14 @@ def _rel_pair(rel0, rel1, device, what):
     host = isinstance(rel0, np.ndarray)
     if host != isinstance(rel1, np.ndarray):
         raise TypeError(f"{what}: both channels must be numpy arrays or both torch tensors")
-    names = {str(np.dtype(a.dtype)) if host else str(a.dtype).replace("torch.", "") for a in (rel0, rel1)}
+    names = {_dtype_name(a) for a in (rel0, rel1)}
     if len(names) != 1 or not names <= {"float32", "float64"}:
         raise TypeError(f"{what}: both rel fields must be float32, or both float64")
     if tuple(rel0.shape) != tuple(rel1.shape) or len(rel0.shape) not in (2, 3):
         raise ValueError(f"{what}: the rel fields must share one (nz, ny, nx) or (ny, nx) shape, got "
                          f"{tuple(rel0.shape)} and {tuple(rel1.shape)}")
     dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    to = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host else a.contiguous()
-    return host, (lambda: (to(rel0), to(rel1)))
+    return host, (lambda: (_to_device(rel0, host, dev), _to_device(rel1, host, dev)))
 
 
 def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor=0.0, combine="or", min_size=1,
@@ -765,27 +786,13 @@ def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor
     t0, t1 = upload()
     call = _OpenCall(boxes, dims, t0.dtype == torch.float64, min_size, connectivity, t0.device)
     with torch.cuda.device(t0.device):
-        if thresholds is None:
-            thresh = torch.empty(2, dtype=t0.dtype, device=t0.device)
-            for i, t in enumerate((t0, t1)):
-                percentile_threshold_device(t, rel_percentile, out=thresh[i:i + 1])
-        else:
-            thresh = torch.tensor([float(v) for v in thresholds], dtype=t0.dtype).to(t0.device)
+        thresh = _thresholds_device([t0, t1], rel_percentile, thresholds)
         counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=t0.device)
         esz = thresh.element_size()
         call.enqueue_pair(t0.data_ptr(), thresh.data_ptr(), t1.data_ptr(), thresh.data_ptr() + esz, floor, combine,
                           counts.data_ptr(), torch.cuda.current_stream(t0.device).cuda_stream)
-        keep = call.keep.view(t0.shape)
-        counts = counts.cpu().numpy()
-        out = {"keep": keep.cpu().numpy() if host else keep, "rois": boxes.copy(),
-               "thresholds": thresh.cpu().numpy().astype(_np_dtype(t0))}
-    k = out["keep"]
-    if host:
-        out["mask"] = lambda r: ((k >> np.uint16(r)) & np.uint16(1)).astype(bool)
-    else:
-        out["mask"] = lambda r: ((k.view(torch.int16) >> r) & 1).bool()  # uint16 has no shifts in torch
-    for i, name in enumerate(OPEN_COUNTS):
-        out[name] = counts[:, i].copy()
+        out = _mask_dict(call.keep.view(t0.shape), host, boxes, counts)
+        out["thresholds"] = thresh.cpu().numpy().astype(_np_dtype(t0))
     return out
 
 
@@ -831,7 +838,7 @@ def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale
     fields = [a for a in ch0[:3] + ch1[:3] if a is not None]
     if any(isinstance(a, np.ndarray) != host for a in fields):
         raise TypeError("channel_compare: all fields must be numpy arrays or all torch tensors")
-    names = {str(np.dtype(a.dtype)) if host else str(a.dtype).replace("torch.", "") for a in fields}
+    names = {_dtype_name(a) for a in fields}
     if len(names) != 1 or not names <= {"float32", "float64"}:
         raise TypeError("channel_compare: all velocity fields must be float64, or all float32")
     if any(tuple(a.shape) != shape for a in fields):
@@ -842,10 +849,8 @@ def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale
     rel_dtype = torch.float64 if str(ch0[3].dtype).endswith("float64") else torch.float32
     call = _PairCall(shape, rel_dtype, dev, rel_percentile, xyscale, zscale, tscale, rois, bins, floor, combine,
                      min_size, connectivity)
-    to = lambda a: None if a is None else (torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host
-                                            else a.contiguous())
     r0, r1 = upload_rel()
-    t0, t1 = [to(a) for a in ch0[:3]] + [r0], [to(a) for a in ch1[:3]] + [r1]
+    t0, t1 = ([_to_device(a, host, dev) for a in ch[:3]] + [r] for ch, r in ((ch0, r0), (ch1, r1)))
     ptrs = lambda t: tuple(a.data_ptr() if a is not None else None for a in t)
     with torch.cuda.device(dev):
         res = call.enqueue(ptrs(t0), ptrs(t1), t0[0].dtype == torch.float32,
@@ -871,7 +876,7 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
 
     host = isinstance(rel, np.ndarray)
     dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    tr = torch.as_tensor(np.ascontiguousarray(rel)).to(dev) if host else rel.contiguous()
+    tr = _to_device(rel, host, dev)
     if tr.dtype not in (torch.float32, torch.float64):
         raise TypeError("rel must be float32 or float64")
     if tr.dim() not in (2, 3):
@@ -886,10 +891,7 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
     opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tr.device) if min_size else None
     with torch.cuda.device(tr.device):
         stream = torch.cuda.current_stream(tr.device).cuda_stream
-        if threshold is None:
-            thresh = percentile_threshold_device(tr, rel_percentile)
-        else:
-            thresh = torch.tensor([float(threshold)], dtype=tr.dtype).to(tr.device)
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
         res = torch.empty(call.result_bytes // 8 + 4 * len(boxes), dtype=torch.int64, device=tr.device)
         counts_ptr = res.data_ptr() + call.result_bytes
         if opening is not None:
@@ -901,9 +903,7 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
     call.decode(words, out, projected=False)
     del out["axes_used"]
     if opening is not None:
-        counts = words[call.result_bytes // 8:].reshape(len(boxes), 4)
-        for i, name in enumerate(OPEN_COUNTS):
-            out[name] = counts[:, i].copy()
+        _decode_open_counts(words[call.result_bytes // 8:], len(boxes), out)
     return out
 
 
@@ -939,9 +939,7 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
 
     host = isinstance(vx, np.ndarray)
     dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    to = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev) if host else a.contiguous()
-    tx, ty, tr = to(vx), to(vy), to(rel)
-    tz = to(vz) if vz is not None else None
+    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
     if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
         raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
     if tx.dim() != (3 if tz is not None else 2):

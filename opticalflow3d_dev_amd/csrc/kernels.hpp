@@ -23,3 +23,12 @@ template <typename F, typename RelT> const void* k5_dma_kernel(int rw, int nb); 
 template <typename F, typename RelT> const void* k5c_fn(int rw, int nb, int r, int nw, int rt0 = 0);  // kt_solve.hip
 int set_error(const char* msg);  // of3d_host.hip: records of3d_last_error's message, returns -1
 }  // namespace of3dk
+
+// A HIP call of an entry point outside of3d_host.hip (the summary passes): its error becomes
+// of3d_last_error's message and the entry point's -1.  Needs <string> and the HIP runtime.
+#define OF3DK_HIP(call)                                                                        \
+    do {                                                                                       \
+        hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)

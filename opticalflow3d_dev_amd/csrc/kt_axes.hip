@@ -24,16 +24,8 @@ using u64 = unsigned long long;
 using u128 = unsigned __int128;
 using i128 = __int128;
 
-#define AX_HIP(call)                                                                           \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
+using of3dk::kSumMaxBlocks, of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kMaxBins, of3dk::kMaxRoi;  // summary_host.hpp
 
-using of3dk::kSumMaxBlocks, of3dk::kSumThreads, of3dk::kSumWaves;
-
-constexpr int kMaxRoi = OF3D_SUMMARY_MAX_ROI, kMaxBins = OF3D_SUMMARY_MAX_BINS;
 constexpr int kNA = OF3D_AXES_QUANTITIES;  // projections (axes)
 constexpr int kNMom = 10;                  // n x y z xx yy zz xy xz yz
 // a box's result words (include/of3d.h)
@@ -49,10 +41,7 @@ constexpr size_t kAxSlotBytes = (size_t)kMaxRoi * kSumMaxBlocks * kNA * sizeof(d
 constexpr size_t kAxEdgeWords = (size_t)kNA * (kMaxBins + 1);
 constexpr size_t kAxWsBytes = kAxSlotBytes + kAxEdgeWords * sizeof(double);
 
-struct AxParams {
-    int nz, ny, nx, n_roi;
-    int box[kMaxRoi][6];  // z0 z1 y0 y1 x0 x1
-    int nb[kMaxRoi];      // workgroups of the box in k_proj_boxes (of3dk::sum_workgroups)
+struct AxParams : of3dk::BoxParams {  // nb: the workgroups of the box in k_proj_boxes, 0 without a projection
     int nbins[kNA];
     int eoff[kNA];  // first edge of the axis in the workspace's edge array
     int hoff[kNA];  // first bin of the axis in a box's histogram words
@@ -61,20 +50,10 @@ struct AxParams {
     double sxy, sz, st;
 };
 
-constexpr int kEdgeChunk = 384;  // edges carried by one k_put_axis_edges launch (kernel arguments)
-struct EdgeChunk {
-    double e[kEdgeChunk];
-};
-
 struct GivenAxes {
     double a[9];  // e1 e2 e3, each x y z
     int use;
 };
-
-// the edges travel as kernel arguments: stream-ordered, no host copy to wait for
-__global__ void k_put_axis_edges(double* __restrict__ dst, EdgeChunk c, int n) {
-    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
-}
 
 // ---------------------------------------------------------------------------
 // Moments.  Wave w of the grid takes the rows (z, y) w, w + W, ... of the box (W waves in all)
@@ -292,6 +271,9 @@ __global__ __launch_bounds__(64) void k_axes(AxParams P, GivenAxes given, u64* _
 // Projection.  k_sum_boxes' partition, masking and reduction (summary_dev.hpp, kt_summary.hip)
 // with p_k = (vx*e_k.x + vy*e_k.y) + vz*e_k.z in place of its eight quantities.
 // ---------------------------------------------------------------------------
+// The kernel spells out its share of the box and its reduction where k_sum_boxes, k_whist_boxes
+// and k_pair_boxes call of3dk::box_share, reduce_to_slot and flush_hist (the same statements):
+// with the helpers the register allocation of three of its eight instances moves by two VGPRs.
 template <typename VT, typename RelT, bool Masked>
 __global__ __launch_bounds__(kSumThreads) void k_proj_boxes(const VT* __restrict__ vx, const VT* __restrict__ vy,
                                                             const VT* __restrict__ vz, const RelT* __restrict__ rel,
@@ -378,13 +360,11 @@ __global__ __launch_bounds__(kSumThreads) void k_proj_boxes(const VT* __restrict
         }
     }
 
-    // lanes: a fixed shuffle tree; waves: the partials added in wave order
+    // lanes: the fixed shuffle tree; waves: the partials added in wave order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < kNA; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        const double v = of3dk::wave_sum(acc[q]);
         if (lane == 0) wsum[wave][q] = v;
     }
     if (nvalid) atomicAdd(&nvalid_s, nvalid);
@@ -400,42 +380,28 @@ __global__ __launch_bounds__(kSumThreads) void k_proj_boxes(const VT* __restrict
 }
 
 // One workgroup per box: its slots staged in LDS, then added in index order.
-__global__ __launch_bounds__(256) void k_proj_final(const double* __restrict__ slots, AxParams P,
-                                                    u64* __restrict__ result) {
+__global__ __launch_bounds__(of3dk::kFinalThreads) void k_proj_final(const double* __restrict__ slots, AxParams P,
+                                                                     u64* __restrict__ result) {
     __shared__ double s[kSumMaxBlocks * kNA];
-    const int roi = blockIdx.x, nb = P.nb[roi];
-    for (int i = threadIdx.x; i < nb * kNA; i += 256) s[i] = slots[(size_t)roi * kSumMaxBlocks * kNA + i];
-    __syncthreads();
-    if (threadIdx.x < kNA) {
-        double v = s[threadIdx.x];
-        for (int b = 1; b < nb; ++b) v += s[b * kNA + threadIdx.x];
-        result[(size_t)roi * P.roi_words + kWSum + threadIdx.x] = (u64)__double_as_longlong(v);
-    }
+    const int roi = blockIdx.x;
+    of3dk::add_slots<kNA, kNA>(slots + (size_t)roi * kSumMaxBlocks * kNA, P.nb[roi], s,
+                               result + (size_t)roi * P.roi_words + kWSum);
 }
 
-bool bins_ok(const int* nbins3) {
-    if (!nbins3) return false;
-    for (int q = 0; q < kNA; ++q)
-        if (nbins3[q] < 0 || nbins3[q] > kMaxBins) return false;
-    return true;
-}
-
-int roi_words(const int* nbins3) { return kAxHead + nbins3[0] + nbins3[1] + nbins3[2]; }
+int roi_words(const int* nbins3) { return kAxHead + of3dk::total_bins<kNA>(nbins3); }
 
 // The boxes as of3d_flow_summary validates them, and the moments' range: the largest sum is
 // sum a^2 <= voxels * (L - 1)^2 with L the box's longest edge, which must stay below 2^63.
 int check_boxes(const int64_t* rois, int n_roi, const int64_t dims[3]) {
-    if (!rois) return of3dk::set_error("of3d: null argument");
-    if (n_roi < 1 || n_roi > kMaxRoi) return of3dk::set_error("of3d: 1 to 16 ROI boxes");
+    if (of3dk::check_roi_count(rois, n_roi) != 0) return -1;
     for (int r = 0; r < n_roi; ++r) {
         u128 vox = 1;
         int64_t longest = 0;
         for (int a = 0; a < 3; ++a) {
-            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
-            if (b0 < 0 || b0 >= b1 || (dims && b1 > dims[a]) || b1 > INT32_MAX)
-                return of3dk::set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
-            vox *= (u128)(b1 - b0);
-            longest = b1 - b0 > longest ? b1 - b0 : longest;
+            const int64_t ext = of3dk::box_extent(rois, r, a, dims);
+            if (ext < 0) return -1;
+            vox *= (u128)ext;
+            longest = ext > longest ? ext : longest;
         }
         // vox < 2^93 and (L - 1)^2 < 2^62: the first test keeps the product inside 128 bits
         if (vox >= ((u128)1 << 63) || vox * (u128)(longest - 1) * (u128)(longest - 1) >= ((u128)1 << 63))
@@ -453,7 +419,7 @@ size_t of3d_mask_axes_workspace_bytes(const int64_t* rois, int n_roi) {
 }
 
 size_t of3d_mask_axes_result_bytes(int n_roi, const int* nbins3) {
-    if (n_roi < 1 || n_roi > kMaxRoi || !bins_ok(nbins3)) return 0;
+    if (n_roi < 1 || n_roi > kMaxRoi || !of3dk::bins_ok<kNA>(nbins3)) return 0;
     return (size_t)n_roi * roi_words(nbins3) * 8;
 }
 
@@ -469,7 +435,7 @@ int of3d_mask_axes(const void* vx, const void* vy, const void* vz, const void* r
     if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
         return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
     if (project && !vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
-    if (!bins_ok(nbins3)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
+    if (!of3dk::bins_ok<kNA>(nbins3)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     if (!project && (nbins3[0] || nbins3[1] || nbins3[2]))
         return of3dk::set_error("of3d: axis histograms need the velocity fields");
     if (project && !vz && nbins3[2]) return of3dk::set_error("of3d: an axis3 histogram needs a 3D volume");
@@ -484,53 +450,28 @@ int of3d_mask_axes(const void* vx, const void* vy, const void* vz, const void* r
         }
         given.use = 1;
     }
-    AxParams P;
-    memset(&P, 0, sizeof(P));
-    P.nz = (int)nz, P.ny = (int)ny, P.nx = (int)nx, P.n_roi = n_roi;
+    AxParams P{};
     P.sxy = xyscale, P.sz = zscale, P.st = tscale, P.physical = axes_physical != 0;
-    int max_nb = 1;
+    if (project && of3dk::plan_boxes(rois, n_roi, dims, 0, P.nb) != 0) return -1;
+    const int max_nb = of3dk::fill_boxes(P, dims, rois, n_roi);
     unsigned max_mom = 1;
     for (int r = 0; r < n_roi; ++r) {
-        for (int a = 0; a < 6; ++a) P.box[r][a] = (int)rois[r * 6 + a];
-        const int64_t dz = rois[r * 6 + 1] - rois[r * 6], dy = rois[r * 6 + 3] - rois[r * 6 + 2];
-        const int64_t dx = rois[r * 6 + 5] - rois[r * 6 + 4];
-        const int64_t rows = dz * dy, vox = rows * dx;  // below 2^63 (check_boxes)
-        const int64_t nb = of3dk::sum_workgroups(vox, rows);
-        if (project && ((rows + nb - 1) / nb) * dx >= ((int64_t)1 << 31) - 4 * kSumThreads)
-            return of3dk::set_error("of3d: ROI too large (2^31 voxels per workgroup)");
-        P.nb[r] = (int)nb;
-        max_nb = nb > max_nb ? (int)nb : max_nb;
         // the moment pass: a row per wave and step
+        const int64_t rows = (rois[r * 6 + 1] - rois[r * 6]) * (rois[r * 6 + 3] - rois[r * 6 + 2]);
         const int64_t want = (rows + kMomWaves - 1) / kMomWaves;
         const unsigned mb = (unsigned)(want > kMomMaxBlocks ? kMomMaxBlocks : want);
         max_mom = mb > max_mom ? mb : max_mom;
     }
-    int eo = 0, ho = 0;
     double host_edges[kAxEdgeWords];
-    for (int q = 0; q < kNA; ++q) {
-        P.nbins[q] = nbins3[q], P.eoff[q] = eo, P.hoff[q] = ho;
-        if (!nbins3[q]) continue;
-        if (!edges3 || !edges3[q]) return of3dk::set_error("of3d: bins requested without edges");
-        for (int i = 0; i <= nbins3[q]; ++i) {
-            const double e = edges3[q][i];
-            if (!(e == e) || (i && !(e > edges3[q][i - 1])))
-                return of3dk::set_error("of3d: bin edges must ascend strictly and hold no NaN");
-            host_edges[eo + i] = e;
-        }
-        eo += nbins3[q] + 1, ho += nbins3[q];
-    }
+    const int eo = of3dk::plan_hists<kNA>(nbins3, edges3, P.nbins, P.eoff, P.hoff, host_edges);
+    if (eo < 0) return -1;
     P.roi_words = roi_words(nbins3);
     hipStream_t s = (hipStream_t)stream;
     double* slots = (double*)workspace;
     double* d_edges = (double*)((char*)workspace + kAxSlotBytes);
     u64* res = (u64*)d_result;
-    AX_HIP(hipMemsetAsync(d_result, 0, of3d_mask_axes_result_bytes(n_roi, nbins3), s));
-    for (int o = 0; o < eo; o += kEdgeChunk) {
-        EdgeChunk c;
-        const int cnt = eo - o < kEdgeChunk ? eo - o : kEdgeChunk;
-        memcpy(c.e, host_edges + o, sizeof(double) * cnt);
-        hipLaunchKernelGGL(k_put_axis_edges, dim3(1), dim3(kEdgeChunk), 0, s, d_edges + o, c, cnt);
-    }
+    OF3DK_HIP(hipMemsetAsync(d_result, 0, of3d_mask_axes_result_bytes(n_roi, nbins3), s));
+    of3dk::put_edges(s, d_edges, host_edges, eo);
     const dim3 mgrid(max_mom, n_roi), mblock(kMomThreads);
     if (d_keep)
         hipLaunchKernelGGL((k_mom_boxes<float, true>), mgrid, mblock, 0, s, (const float*)nullptr,
@@ -554,14 +495,14 @@ int of3d_mask_axes(const void* vx, const void* vy, const void* vz, const void* r
                 hipLaunchKernelGGL((k_proj_boxes<VT, RT, false>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
                                    (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh,
                                    d_keep, P, (const double*)d_edges, slots, res);
-            hipLaunchKernelGGL(k_proj_final, dim3(n_roi), dim3(256), 0, s, (const double*)slots, P, res);
+            hipLaunchKernelGGL(k_proj_final, dim3(n_roi), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, P, res);
         };
         if (v_f32)
             rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
         else
             rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
     }
-    AX_HIP(hipGetLastError());
+    OF3DK_HIP(hipGetLastError());
     return 0;
 }
 

@@ -16,23 +16,17 @@
 
 #include "../../include/of3d.h"
 #include "kernels.hpp"
+#include "summary_host.hpp"
 
 namespace {
 
 using u32 = unsigned;
 using u64 = unsigned long long;
 
-#define CCL_HIP(call)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
 constexpr int kCclThreads = 256;  // a multiple of the wave: lane l of a wave holds voxel base + l
 constexpr int kCclWalkBlocks = 4096;  // workgroups of the strided counting phases at most
 constexpr u32 kBg = 0xFFFFFFFFu;  // background label
-constexpr int kMaxRoi = OF3D_SUMMARY_MAX_ROI;
+using of3dk::kMaxRoi;  // summary_host.hpp
 
 // The 13 "backward" neighbours (negative linear offset) as rows (dz, dy) of three x offsets
 // -1, 0, +1, and the in-row neighbour x-1.  Bit 3*row + (dx+1) of the neighbour mask selects
@@ -284,15 +278,13 @@ u32 neighbour_mask(int connectivity) {
 
 // the boxes as of3d_flow_summary validates them; vox[r] = voxels of box r
 int check_boxes(const int64_t* rois, int n_roi, const int64_t dims[3], int64_t* vox) {
-    if (!rois) return of3dk::set_error("of3d: null argument");
-    if (n_roi < 1 || n_roi > kMaxRoi) return of3dk::set_error("of3d: 1 to 16 ROI boxes");
+    if (of3dk::check_roi_count(rois, n_roi) != 0) return -1;
     for (int r = 0; r < n_roi; ++r) {
         vox[r] = 1;
         for (int a = 0; a < 3; ++a) {
-            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
-            if (b0 < 0 || b0 >= b1 || (dims && b1 > dims[a]) || b1 > INT32_MAX)
-                return of3dk::set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
-            vox[r] *= b1 - b0;  // three factors below 2^31 each: the first two fit, the third is checked
+            const int64_t ext = of3dk::box_extent(rois, r, a, dims);
+            if (ext < 0) return -1;
+            vox[r] *= ext;  // three factors below 2^31 each: the first two fit, the third is checked
             if (a == 1 && vox[r] >= (int64_t)kBg) break;
         }
         if (vox[r] >= (int64_t)kBg)
@@ -319,8 +311,8 @@ int open_launch(Fg is_fg, int64_t nz, int64_t ny, int64_t nx, const int64_t* roi
     hipStream_t s = (hipStream_t)stream;
     u32* label = (u32*)workspace;
     u32* size = label + most;
-    CCL_HIP(hipMemsetAsync(d_keep, 0, (size_t)nz * ny * nx * sizeof(uint16_t), s));
-    CCL_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_roi * 4 * sizeof(int64_t), s));
+    OF3DK_HIP(hipMemsetAsync(d_keep, 0, (size_t)nz * ny * nx * sizeof(uint16_t), s));
+    OF3DK_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_roi * 4 * sizeof(int64_t), s));
     for (int r = 0; r < n_roi; ++r) {
         CclParams P;
         memset(&P, 0, sizeof(P));
@@ -342,7 +334,7 @@ int open_launch(Fg is_fg, int64_t nz, int64_t ny, int64_t nx, const int64_t* roi
         hipLaunchKernelGGL(k_ccl_count, walk, block, 0, s, P, label, size, counts);
         hipLaunchKernelGGL(k_ccl_write, walk, block, 0, s, P, (const u32*)label, (const u32*)size, d_keep, counts);
     }
-    CCL_HIP(hipGetLastError());
+    OF3DK_HIP(hipGetLastError());
     return 0;
 }
 

@@ -15,7 +15,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstring>
 #include <string>
 
 #include "../../include/of3d.h"
@@ -26,27 +25,15 @@ namespace {
 
 using u64 = unsigned long long;
 
-#define PAIR_HIP(call)                                                                         \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
-using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::plan_boxes;
+using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::kMaxBins, of3dk::kMaxRoi, of3dk::plan_boxes;
 constexpr int kNQ = OF3D_PAIR_QUANTITIES;  // 0 dot, 1 cosine, 2 dtheta, 3 dmagnitude
 constexpr int kRoiHead = OF3D_PAIR_ROI_WORDS;
 constexpr int kNSum = 24, kGroup = 8;  // sums per box; sums per workgroup of the final pass
-constexpr int kMaxBins = OF3D_SUMMARY_MAX_BINS, kMaxRoi = OF3D_SUMMARY_MAX_ROI;
 constexpr size_t kEdgeWordsMax = (size_t)kNQ * (kMaxBins + 1);
-constexpr int kEdgeChunk = 384;  // edges carried by one k_put_pair_edges launch (kernel arguments)
 static_assert(kRoiHead == 2 + kNSum && kNSum % kGroup == 0);
 
 // Workspace: the edges (eo words), then the slots [roi][workgroup][24].
-struct PairParams {
-    int nz, ny, nx, n_roi;
-    int box[kMaxRoi][6];      // z0 z1 y0 y1 x0 x1
-    int nb[kMaxRoi];          // workgroups of the box (of3dk::sum_workgroups)
+struct PairParams : of3dk::BoxParams {
     long long soff[kMaxRoi];  // first slot word of the box: sum over earlier boxes of nb * 24
     int nbins[kNQ];
     int eoff[kNQ];  // first edge of the quantity in the workspace's edge array
@@ -54,15 +41,6 @@ struct PairParams {
     int ntot;       // bins of a box, all quantities
     double sxy, sz, st;
 };
-
-struct EdgeChunk {
-    double e[kEdgeChunk];
-};
-
-// the edges travel as kernel arguments: stream-ordered, no host copy to wait for
-__global__ void k_put_pair_edges(double* __restrict__ dst, EdgeChunk c, int n) {
-    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
-}
 
 // Grid (max workgroups of a box, n_roi).  InPlane: no vz fields, magnitude = sqrt(vx^2 + vy^2)
 // for any nz.  The voxel loop runs the same trips in every lane (tail lanes carry mask factor
@@ -85,12 +63,8 @@ __global__ __launch_bounds__(kSumThreads) void k_pair_boxes(
     if (threadIdx.x == 0) nvalid_s = 0;
     __syncthreads();
 
-    const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
-    const unsigned dy = P.box[roi][3] - y0, dx = P.box[roi][5] - x0;
-    const long long R = (long long)(P.box[roi][1] - z0) * dy;
-    const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
-    const long long count = (r1 - r0) * dx;  // this workgroup's voxels (< 2^31: checked on the host)
-    of3dk::BoxWalk w(dy, dx, r0, threadIdx.x, kSumThreads);
+    of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
+    const long long count = sh.count;
     double acc[kNSum];
 #pragma unroll
     for (int q = 0; q < kNSum; ++q) acc[q] = 0.0;
@@ -105,7 +79,7 @@ __global__ __launch_bounds__(kSumThreads) void k_pair_boxes(
             fx0[u] = fy0[u] = fz0[u] = fx1[u] = fy1[u] = fz1[u] = (VT)0;  // past the end: mask factor 0, not valid
             kept[u] = false;
             if (e0 + threadIdx.x + (long long)u * kSumThreads < count) {
-                const size_t i = ((size_t)(z0 + w.z) * P.ny + (y0 + w.y)) * P.nx + (x0 + w.x);
+                const size_t i = sh.index();
                 kept[u] = keep[i] >> roi & 1;
                 fx0[u] = vx0[i];
                 fy0[u] = vy0[i];
@@ -116,7 +90,7 @@ __global__ __launch_bounds__(kSumThreads) void k_pair_boxes(
                     fz1[u] = vz1[i];
                 }
             }
-            w.advance();
+            sh.w.advance();
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -181,60 +155,25 @@ __global__ __launch_bounds__(kSumThreads) void k_pair_boxes(
         }
     }
 
-    // lanes: the fixed shuffle tree under full EXEC; waves: the partials added in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < kNSum; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) wsum[wave][q] = v;
-    }
     if (nvalid) atomicAdd(&nvalid_s, nvalid);
-    __syncthreads();
-    if (threadIdx.x < kNSum) {
-        double v = wsum[0][threadIdx.x];
-        for (int j = 1; j < kSumWaves; ++j) v += wsum[j][threadIdx.x];
-        slots[P.soff[roi] + (long long)blockIdx.x * kNSum + threadIdx.x] = v;
-    }
+    of3dk::reduce_to_slot(acc, wsum, slots + P.soff[roi] + (long long)blockIdx.x * kNSum);
     u64* rr = result + (size_t)roi * (kRoiHead + P.ntot);
     if (threadIdx.x == 0 && nvalid_s) atomicAdd(&rr[0], (u64)nvalid_s);
-    for (int i = threadIdx.x; i < P.ntot; i += kSumThreads)
-        if (hist[i]) atomicAdd(&rr[kRoiHead + i], (u64)hist[i]);
+    of3dk::flush_hist(hist, P.ntot, rr + kRoiHead);
 }
 
 // Grid (n_roi, 3): workgroup (r, g) stages sums 8g .. 8g+7 of box r's slots in LDS (at most
 // 1024 x 8 doubles = 64 KiB) and adds each in workgroup-index order.
-__global__ __launch_bounds__(256) void k_pair_final(const double* __restrict__ slots, PairParams P,
-                                                    u64* __restrict__ result) {
+__global__ __launch_bounds__(of3dk::kFinalThreads) void k_pair_final(const double* __restrict__ slots, PairParams P,
+                                                                     u64* __restrict__ result) {
     __shared__ double s[kSumMaxBlocks * kGroup];
-    const int roi = blockIdx.x, g = blockIdx.y, nb = P.nb[roi];
-    const double* src = slots + P.soff[roi] + g * kGroup;
-    for (int i = threadIdx.x; i < nb * kGroup; i += 256) s[i] = src[(size_t)(i / kGroup) * kNSum + i % kGroup];
-    __syncthreads();
+    const int roi = blockIdx.x, g = blockIdx.y;
     u64* rr = result + (size_t)roi * (kRoiHead + P.ntot);
-    if (threadIdx.x < kGroup) {
-        double v = s[threadIdx.x];
-        for (int b = 1; b < nb; ++b) v += s[b * kGroup + threadIdx.x];
-        rr[2 + g * kGroup + threadIdx.x] = (u64)__double_as_longlong(v);
-    }
+    of3dk::add_slots<kGroup, kNSum>(slots + P.soff[roi] + g * kGroup, P.nb[roi], s, rr + 2 + g * kGroup);
     if (g == 0 && threadIdx.x == 0) {
         const int* bx = P.box[roi];
         rr[1] = (u64)((long long)(bx[1] - bx[0]) * (bx[3] - bx[2]) * (bx[5] - bx[4]));
     }
-}
-
-bool bins_ok(const int* nbins) {
-    if (!nbins) return false;
-    for (int q = 0; q < kNQ; ++q)
-        if (nbins[q] < 0 || nbins[q] > kMaxBins) return false;
-    return true;
-}
-
-int total_bins(const int* nbins) {
-    int n = 0;
-    for (int q = 0; q < kNQ; ++q) n += nbins[q];
-    return n;
 }
 
 }  // namespace
@@ -242,19 +181,18 @@ int total_bins(const int* nbins) {
 extern "C" {
 
 size_t of3d_flow_pair_result_bytes(int n_roi, const int* nbins4) {
-    if (n_roi < 1 || n_roi > kMaxRoi || !bins_ok(nbins4)) return 0;
-    return (size_t)n_roi * (kRoiHead + total_bins(nbins4)) * 8;
+    if (n_roi < 1 || n_roi > kMaxRoi || !of3dk::bins_ok<kNQ>(nbins4)) return 0;
+    return (size_t)n_roi * (kRoiHead + of3dk::total_bins<kNQ>(nbins4)) * 8;
 }
 
 size_t of3d_flow_pair_workspace_bytes(const int64_t* rois, int n_roi, const int* nbins4) {
-    if (!bins_ok(nbins4)) {
+    if (!of3dk::bins_ok<kNQ>(nbins4)) {
         of3dk::set_error("of3d: 0 to 256 bins per quantity");
         return 0;
     }
-    size_t slot_words = 0, edge_words = 0;
+    size_t slot_words = 0;
     if (plan_boxes(rois, n_roi, nullptr, kNSum, nullptr, nullptr, &slot_words) != 0) return 0;
-    for (int q = 0; q < kNQ; ++q) edge_words += nbins4[q] ? nbins4[q] + 1 : 0;
-    return (edge_words + slot_words) * sizeof(double);
+    return (of3dk::edge_words<kNQ>(nbins4) + slot_words) * sizeof(double);
 }
 
 int of3d_flow_pair(const void* vx0, const void* vy0, const void* vz0, const void* vx1, const void* vy1,
@@ -266,45 +204,22 @@ int of3d_flow_pair(const void* vx0, const void* vy0, const void* vz0, const void
     if (!vz0 != !vz1) return of3dk::set_error("of3d: vz of both channels or of neither (in-plane mode)");
     if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
         return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
-    if (!bins_ok(nbins4)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
-    PairParams P;
-    memset(&P, 0, sizeof(P));
-    P.nz = (int)nz, P.ny = (int)ny, P.nx = (int)nx, P.n_roi = n_roi;
+    if (!of3dk::bins_ok<kNQ>(nbins4)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
+    PairParams P{};
     P.sxy = xyscale, P.sz = zscale, P.st = tscale;
-    P.ntot = total_bins(nbins4);
+    P.ntot = of3dk::total_bins<kNQ>(nbins4);
     const int64_t dims[3] = {nz, ny, nx};
-    size_t slot_words = 0;
-    if (plan_boxes(rois, n_roi, dims, kNSum, P.nb, P.soff, &slot_words) != 0) return -1;
-    int max_nb = 1;
-    for (int r = 0; r < n_roi; ++r) {
-        for (int a = 0; a < 6; ++a) P.box[r][a] = (int)rois[r * 6 + a];
-        max_nb = P.nb[r] > max_nb ? P.nb[r] : max_nb;
-    }
-    int eo = 0, ho = 0;
+    if (plan_boxes(rois, n_roi, dims, kNSum, P.nb, P.soff) != 0) return -1;
+    const int max_nb = of3dk::fill_boxes(P, dims, rois, n_roi);
     double host_edges[kEdgeWordsMax];
-    for (int q = 0; q < kNQ; ++q) {
-        P.nbins[q] = nbins4[q], P.eoff[q] = eo, P.hoff[q] = ho;
-        if (!nbins4[q]) continue;
-        if (!edges4 || !edges4[q]) return of3dk::set_error("of3d: bins requested without edges");
-        for (int i = 0; i <= nbins4[q]; ++i) {
-            const double e = edges4[q][i];
-            if (!(e == e) || (i && !(e > edges4[q][i - 1])))
-                return of3dk::set_error("of3d: bin edges must ascend strictly and hold no NaN");
-            host_edges[eo + i] = e;
-        }
-        eo += nbins4[q] + 1, ho += nbins4[q];
-    }
+    const int eo = of3dk::plan_hists<kNQ>(nbins4, edges4, P.nbins, P.eoff, P.hoff, host_edges);
+    if (eo < 0) return -1;
     hipStream_t s = (hipStream_t)stream;
     double* d_edges = (double*)workspace;
     double* slots = d_edges + eo;
     u64* res = (u64*)d_result;
-    PAIR_HIP(hipMemsetAsync(d_result, 0, of3d_flow_pair_result_bytes(n_roi, nbins4), s));
-    for (int o = 0; o < eo; o += kEdgeChunk) {
-        EdgeChunk c;
-        const int cnt = eo - o < kEdgeChunk ? eo - o : kEdgeChunk;
-        memcpy(c.e, host_edges + o, sizeof(double) * cnt);
-        hipLaunchKernelGGL(k_put_pair_edges, dim3(1), dim3(kEdgeChunk), 0, s, d_edges + o, c, cnt);
-    }
+    OF3DK_HIP(hipMemsetAsync(d_result, 0, of3d_flow_pair_result_bytes(n_roi, nbins4), s));
+    of3dk::put_edges(s, d_edges, host_edges, eo);
     const dim3 grid(max_nb, n_roi);
     auto launch = [&](auto vt) {
         using VT = decltype(vt);
@@ -321,8 +236,8 @@ int of3d_flow_pair(const void* vx0, const void* vy0, const void* vz0, const void
         launch(float{});
     else
         launch(double{});
-    hipLaunchKernelGGL(k_pair_final, dim3(n_roi, kNSum / kGroup), dim3(256), 0, s, (const double*)slots, P, res);
-    PAIR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_pair_final, dim3(n_roi, kNSum / kGroup), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, P, res);
+    OF3DK_HIP(hipGetLastError());
     return 0;
 }
 

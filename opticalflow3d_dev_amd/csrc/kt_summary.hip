@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstring>
 #include <string>
 
 #include "../../include/of3d.h"
@@ -16,13 +15,6 @@
 namespace {
 
 using u64 = unsigned long long;
-
-#define SUM_HIP(call)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 // ---------------------------------------------------------------------------
 // Radix select.  key(v): the order-preserving unsigned image of the float bits (sign bit set:
@@ -201,7 +193,7 @@ int quantile_launch(const void* a, int64_t n, int64_t lo, int64_t hi, double gam
                     hipStream_t s) {
     SelState* st = (SelState*)ws;
     u64* hist = (u64*)((char*)ws + sizeof(SelState));
-    SUM_HIP(hipMemsetAsync(ws, 0, kSelBytes, s));
+    OF3DK_HIP(hipMemsetAsync(ws, 0, kSelBytes, s));
     hipLaunchKernelGGL(k_sel_init, dim3(1), dim3(1), 0, s, st, (u64)lo, (u64)hi);
     // 16 elements per thread and pass at least; at most 2048 workgroups
     const int64_t want = (n + (int64_t)kSelThreads * 16 - 1) / ((int64_t)kSelThreads * 16);
@@ -211,7 +203,7 @@ int quantile_launch(const void* a, int64_t n, int64_t lo, int64_t hi, double gam
         hipLaunchKernelGGL(k_sel_pick<T>, dim3(1), dim3(kSelThreads), 0, s, p, st, (const u64*)hist, gamma,
                            (T*)out);
     }
-    SUM_HIP(hipGetLastError());
+    OF3DK_HIP(hipGetLastError());
     return 0;
 }
 
@@ -224,35 +216,21 @@ int quantile_launch(const void* a, int64_t n, int64_t lo, int64_t hi, double gam
 // then 64-bit integer atomics into the (zeroed) result.  No floating-point atomics: the same
 // inputs give the same bits on every run, and a box's row does not depend on the other boxes.
 // ---------------------------------------------------------------------------
-using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::kSumVoxPerBlock;  // summary_dev.hpp
+using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::kMaxBins, of3dk::kMaxRoi;  // summary_host.hpp
 constexpr int kNSum = 8;                   // mag x y z sin cos mag*sin mag*cos
 constexpr int kNQ = OF3D_SUMMARY_QUANTITIES;
-constexpr int kMaxBins = OF3D_SUMMARY_MAX_BINS, kMaxRoi = OF3D_SUMMARY_MAX_ROI;
 constexpr int kHead = 8, kRoiHead = 2 + kNSum;  // result words before the boxes / before a box's histograms
 constexpr size_t kSumSlotBytes = (size_t)kMaxRoi * kSumMaxBlocks * kNSum * sizeof(double);
 constexpr size_t kEdgeWords = (size_t)kNQ * (kMaxBins + 1);
 constexpr size_t kSumWsBytes = kSumSlotBytes + kEdgeWords * sizeof(double);
-constexpr int kEdgeChunk = 384;  // edges carried by one k_put_edges launch (kernel arguments)
 
-struct SumParams {
-    int nz, ny, nx, n_roi;
-    int box[kMaxRoi][6];  // z0 z1 y0 y1 x0 x1
-    int nb[kMaxRoi];      // workgroups of the box
+struct SumParams : of3dk::BoxParams {
     int nbins[kNQ];
     int eoff[kNQ];  // first edge of the quantity in the workspace's edge array
     int hoff[kNQ];  // first bin of the quantity in a box's histogram words
     int roi_words;  // result words per box
     double sxy, sz, st;
 };
-
-struct EdgeChunk {
-    double e[kEdgeChunk];
-};
-
-// the edges travel as kernel arguments: stream-ordered, no host copy to wait for
-__global__ void k_put_edges(double* __restrict__ dst, EdgeChunk c, int n) {
-    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
-}
 
 using of3dk::find_bin;  // summary_dev.hpp, shared with kt_axes.hip
 
@@ -280,13 +258,8 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
     if (threadIdx.x == 0) nvalid_s = 0;
     __syncthreads();
 
-    const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
-    const unsigned dy = P.box[roi][3] - y0, dx = P.box[roi][5] - x0;
-    const long long R = (long long)(P.box[roi][1] - z0) * dy;
-    const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
-    const long long count = (r1 - r0) * dx;  // this workgroup's voxels (< 2^31: checked on the host)
-    // this thread's voxel as (z, y, x) inside the box, advanced by kSumThreads voxels per step
-    of3dk::BoxWalk w(dy, dx, r0, threadIdx.x, kSumThreads);
+    of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
+    const long long count = sh.count;
     const double thr = (double)*thr_p;
     const bool is3 = vz != nullptr;
     double acc[kNSum] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -301,7 +274,7 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
             in[u] = e + (long long)u * kSumThreads < count;
             fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
             if (in[u]) {
-                const size_t i = ((size_t)(z0 + w.z) * P.ny + (y0 + w.y)) * P.nx + (x0 + w.x);
+                const size_t i = sh.index();
                 if constexpr (Masked)
                     fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
                 else
@@ -310,7 +283,7 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
                 fy[u] = (double)vy[i];
                 if (is3) fz[u] = (double)vz[i];
             }
-            w.advance();
+            sh.w.advance();
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -346,42 +319,22 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
         }
     }
 
-    // lanes: a fixed shuffle tree; waves: wave 0 adds the partials in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < kNSum; ++q) {
-        double v = acc[q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) wsum[wave][q] = v;
-    }
     if (nvalid) atomicAdd(&nvalid_s, nvalid);
-    __syncthreads();
-    if (threadIdx.x < kNSum) {
-        double v = wsum[0][threadIdx.x];
-        for (int w = 1; w < kSumWaves; ++w) v += wsum[w][threadIdx.x];
-        slots[((size_t)roi * kSumMaxBlocks + blockIdx.x) * kNSum + threadIdx.x] = v;
-    }
+    of3dk::reduce_to_slot(acc, wsum, slots + ((size_t)roi * kSumMaxBlocks + blockIdx.x) * kNSum);
     u64* rr = result + kHead + (size_t)roi * P.roi_words;
     if (threadIdx.x == 0 && nvalid_s) atomicAdd(&rr[0], (u64)nvalid_s);
-    for (int i = threadIdx.x; i < ntot; i += kSumThreads)
-        if (hist[i]) atomicAdd(&rr[kRoiHead + i], (u64)hist[i]);
+    of3dk::flush_hist(hist, ntot, rr + kRoiHead);
 }
 
 // One workgroup per box: its slots staged in LDS, then added in index order.
 template <typename RelT>
-__global__ __launch_bounds__(256) void k_sum_final(const double* __restrict__ slots, const RelT* __restrict__ thr_p,
-                                                   SumParams P, u64* __restrict__ result) {
+__global__ __launch_bounds__(of3dk::kFinalThreads) void k_sum_final(const double* __restrict__ slots,
+                                                                    const RelT* __restrict__ thr_p, SumParams P,
+                                                                    u64* __restrict__ result) {
     __shared__ double s[kSumMaxBlocks * kNSum];
-    const int roi = blockIdx.x, nb = P.nb[roi];
-    for (int i = threadIdx.x; i < nb * kNSum; i += 256) s[i] = slots[(size_t)roi * kSumMaxBlocks * kNSum + i];
-    __syncthreads();
+    const int roi = blockIdx.x;
     u64* rr = result + kHead + (size_t)roi * P.roi_words;
-    if (threadIdx.x < kNSum) {
-        double v = s[threadIdx.x];
-        for (int b = 1; b < nb; ++b) v += s[b * kNSum + threadIdx.x];
-        rr[2 + threadIdx.x] = (u64)__double_as_longlong(v);
-    }
+    of3dk::add_slots<kNSum, kNSum>(slots + (size_t)roi * kSumMaxBlocks * kNSum, P.nb[roi], s, rr + 2);
     if (threadIdx.x == 0) {
         const int* bx = P.box[roi];
         rr[1] = (u64)((long long)(bx[1] - bx[0]) * (bx[3] - bx[2]) * (bx[5] - bx[4]));
@@ -393,18 +346,7 @@ __global__ __launch_bounds__(256) void k_sum_final(const double* __restrict__ sl
     }
 }
 
-int roi_words(const int* nbins) {
-    int w = kRoiHead;
-    for (int q = 0; q < kNQ; ++q) w += nbins[q];
-    return w;
-}
-
-bool bins_ok(const int* nbins) {
-    if (!nbins) return false;
-    for (int q = 0; q < kNQ; ++q)
-        if (nbins[q] < 0 || nbins[q] > kMaxBins) return false;
-    return true;
-}
+int roi_words(const int* nbins) { return kRoiHead + of3dk::total_bins<kNQ>(nbins); }
 
 }  // namespace
 
@@ -427,7 +369,7 @@ int of3d_quantile(const void* a, int is_f64, int64_t n, int64_t lo, int64_t hi, 
 }
 
 size_t of3d_flow_summary_result_bytes(int n_roi, const int* nbins) {
-    if (n_roi < 1 || n_roi > kMaxRoi || !bins_ok(nbins)) return 0;
+    if (n_roi < 1 || n_roi > kMaxRoi || !of3dk::bins_ok<kNQ>(nbins)) return 0;
     return ((size_t)kHead + (size_t)n_roi * roi_words(nbins)) * 8;
 }
 
@@ -444,57 +386,22 @@ static int summary_launch(const void* vx, const void* vy, const void* vz, const 
         return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
     if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
     if (n_roi < 1 || n_roi > kMaxRoi) return of3dk::set_error("of3d: 1 to 16 ROI boxes");
-    if (!bins_ok(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
+    if (!of3dk::bins_ok<kNQ>(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     if (!vz && (nbins[2] || nbins[5])) return of3dk::set_error("of3d: vz and phi histograms need a 3D volume");
-    SumParams P;
-    memset(&P, 0, sizeof(P));
-    P.nz = (int)nz, P.ny = (int)ny, P.nx = (int)nx, P.n_roi = n_roi;
+    SumParams P{};
     P.sxy = xyscale, P.sz = zscale, P.st = tscale;
     const int64_t dims[3] = {nz, ny, nx};
-    int max_nb = 1;
-    for (int r = 0; r < n_roi; ++r) {
-        int64_t vox = 1;
-        for (int a = 0; a < 3; ++a) {
-            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
-            if (b0 < 0 || b0 >= b1 || b1 > dims[a])
-                return of3dk::set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
-            P.box[r][2 * a] = (int)b0, P.box[r][2 * a + 1] = (int)b1;
-            vox *= b1 - b0;
-        }
-        // a function of the box alone (never of the device): the summation order is fixed
-        const int64_t rows = (rois[r * 6 + 1] - rois[r * 6]) * (rois[r * 6 + 3] - rois[r * 6 + 2]);
-        const int64_t nb = of3dk::sum_workgroups(vox, rows);
-        // a workgroup's share: at most ceil(rows / nb) rows
-        if (((rows + nb - 1) / nb) * (rois[r * 6 + 5] - rois[r * 6 + 4]) >= ((int64_t)1 << 31) - 4 * kSumThreads)
-            return of3dk::set_error("of3d: ROI too large (2^31 voxels per workgroup)");
-        P.nb[r] = (int)nb;
-        max_nb = nb > max_nb ? (int)nb : max_nb;
-    }
-    int eo = 0, ho = 0;
+    if (of3dk::plan_boxes(rois, n_roi, dims, 0, P.nb) != 0) return -1;
+    const int max_nb = of3dk::fill_boxes(P, dims, rois, n_roi);
     double host_edges[kEdgeWords];
-    for (int q = 0; q < kNQ; ++q) {
-        P.nbins[q] = nbins[q], P.eoff[q] = eo, P.hoff[q] = ho;
-        if (!nbins[q]) continue;
-        if (!edges || !edges[q]) return of3dk::set_error("of3d: bins requested without edges");
-        for (int i = 0; i <= nbins[q]; ++i) {
-            const double e = edges[q][i];
-            if (!(e == e) || (i && !(e > edges[q][i - 1])))
-                return of3dk::set_error("of3d: bin edges must ascend strictly and hold no NaN");
-            host_edges[eo + i] = e;
-        }
-        eo += nbins[q] + 1, ho += nbins[q];
-    }
+    const int eo = of3dk::plan_hists<kNQ>(nbins, edges, P.nbins, P.eoff, P.hoff, host_edges);
+    if (eo < 0) return -1;
     P.roi_words = roi_words(nbins);
     hipStream_t s = (hipStream_t)stream;
     double* slots = (double*)workspace;
     double* d_edges = (double*)((char*)workspace + kSumSlotBytes);
-    SUM_HIP(hipMemsetAsync(d_result, 0, of3d_flow_summary_result_bytes(n_roi, nbins), s));
-    for (int o = 0; o < eo; o += kEdgeChunk) {
-        EdgeChunk c;
-        const int cnt = eo - o < kEdgeChunk ? eo - o : kEdgeChunk;
-        memcpy(c.e, host_edges + o, sizeof(double) * cnt);
-        hipLaunchKernelGGL(k_put_edges, dim3(1), dim3(kEdgeChunk), 0, s, d_edges + o, c, cnt);
-    }
+    OF3DK_HIP(hipMemsetAsync(d_result, 0, of3d_flow_summary_result_bytes(n_roi, nbins), s));
+    of3dk::put_edges(s, d_edges, host_edges, eo);
     auto launch = [&](auto vt, auto rt) {
         using VT = decltype(vt);
         using RT = decltype(rt);
@@ -506,14 +413,14 @@ static int summary_launch(const void* vx, const void* vy, const void* vz, const 
             hipLaunchKernelGGL((k_sum_boxes<VT, RT, false>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
                                (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, keep,
                                P, (const double*)d_edges, slots, (u64*)d_result);
-        hipLaunchKernelGGL(k_sum_final<RT>, dim3(n_roi), dim3(256), 0, s, (const double*)slots, (const RT*)d_thresh,
+        hipLaunchKernelGGL(k_sum_final<RT>, dim3(n_roi), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, (const RT*)d_thresh,
                            P, (u64*)d_result);
     };
     if (v_f32)
         rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
     else
         rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
-    SUM_HIP(hipGetLastError());
+    OF3DK_HIP(hipGetLastError());
     return 0;
 }
 

@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstring>
 #include <string>
 
 #include "../../include/of3d.h"
@@ -21,25 +20,13 @@ namespace {
 
 using u64 = unsigned long long;
 
-#define WH_HIP(call)                                                                           \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return of3dk::set_error((std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
-using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::plan_boxes;
+using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kMaxBins, of3dk::kMaxRoi, of3dk::plan_boxes;  // summary_host.hpp
 constexpr int kNQ = OF3D_SUMMARY_QUANTITIES;
-constexpr int kMaxBins = OF3D_SUMMARY_MAX_BINS, kMaxRoi = OF3D_SUMMARY_MAX_ROI;
 constexpr size_t kEdgeWordsMax = (size_t)kNQ * (kMaxBins + 1);
-constexpr int kEdgeChunk = 384;  // edges carried by one k_put_whist_edges launch (kernel arguments)
 
 // Requested quantities are numbered k = 0.. in QUANTITIES order; everything per quantity is
 // indexed by k.  Workspace: the edges (eo words), then the slots [roi][k][workgroup][bin].
-struct WhParams {
-    int nz, ny, nx, n_roi;
-    int box[kMaxRoi][6];      // z0 z1 y0 y1 x0 x1
-    int nb[kMaxRoi];          // workgroups of the box (of3dk::sum_workgroups)
+struct WhParams : of3dk::BoxParams {
     long long soff[kMaxRoi];  // first slot word of the box: sum over earlier boxes of nb * ntot
     int nq;                   // requested quantities
     int q[kNQ];               // the quantity (0 vx .. 5 phi)
@@ -49,15 +36,6 @@ struct WhParams {
     int ntot;       // bins of a box, all quantities
     double sxy, sz, st;
 };
-
-struct EdgeChunk {
-    double e[kEdgeChunk];
-};
-
-// the edges travel as kernel arguments: stream-ordered, no host copy to wait for
-__global__ void k_put_whist_edges(double* __restrict__ dst, EdgeChunk c, int n) {
-    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.e[threadIdx.x];
-}
 
 __device__ __forceinline__ double readlane_f64(double v, int src) {
     const long long b = __double_as_longlong(v);
@@ -80,14 +58,7 @@ __device__ __forceinline__ void wave_add(double* __restrict__ mine, int bin, dou
         const int b = __builtin_amdgcn_readlane(bin, leader);
         const bool match = bin == b;
         const u64 mm = __ballot(match);
-        double v;
-        if (mm & (mm - 1)) {
-            v = match ? wgt : 0.0;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        } else {
-            v = readlane_f64(wgt, leader);
-        }
+        const double v = (mm & (mm - 1)) ? of3dk::wave_sum(match ? wgt : 0.0) : readlane_f64(wgt, leader);
         if (lane == 0) mine[b] += v;
         pending &= ~mm;
     }
@@ -115,12 +86,8 @@ __global__ __launch_bounds__(kSumThreads) void k_whist_boxes(const VT* __restric
     if (threadIdx.x == 0) nvalid_s = 0;
     __syncthreads();
 
-    const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
-    const unsigned dy = P.box[roi][3] - y0, dx = P.box[roi][5] - x0;
-    const long long R = (long long)(P.box[roi][1] - z0) * dy;
-    const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
-    const long long count = (r1 - r0) * dx;  // this workgroup's voxels (< 2^31: checked on the host)
-    of3dk::BoxWalk w(dy, dx, r0, threadIdx.x, kSumThreads);
+    of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
+    const long long count = sh.count;
     const double thr = Masked ? 0.0 : (double)*thr_p;
     const bool is3 = vz != nullptr;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -134,7 +101,7 @@ __global__ __launch_bounds__(kSumThreads) void k_whist_boxes(const VT* __restric
         for (int u = 0; u < U; ++u) {
             fx[u] = fy[u] = fz[u] = fr[u] = 0.0;  // past the end: mask factor 0, not valid
             if (e0 + threadIdx.x + (long long)u * kSumThreads < count) {
-                const size_t i = ((size_t)(z0 + w.z) * P.ny + (y0 + w.y)) * P.nx + (x0 + w.x);
+                const size_t i = sh.index();
                 if constexpr (Masked)
                     fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
                 else
@@ -143,7 +110,7 @@ __global__ __launch_bounds__(kSumThreads) void k_whist_boxes(const VT* __restric
                 fy[u] = (double)vy[i];
                 if (is3) fz[u] = (double)vz[i];
             }
-            w.advance();
+            sh.w.advance();
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -189,42 +156,28 @@ __global__ __launch_bounds__(256) void k_whist_final(const double* __restrict__ 
     result[(size_t)roi * (1 + P.ntot) + 1 + i] = (u64)__double_as_longlong(v);
 }
 
-bool bins_ok(const int* nbins) {
-    if (!nbins) return false;
-    for (int q = 0; q < kNQ; ++q)
-        if (nbins[q] < 0 || nbins[q] > kMaxBins) return false;
-    return true;
-}
-
-int total_bins(const int* nbins) {
-    int n = 0;
-    for (int q = 0; q < kNQ; ++q) n += nbins[q];
-    return n;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t of3d_flow_whist_result_bytes(int n_roi, const int* nbins) {
-    if (n_roi < 1 || n_roi > kMaxRoi || !bins_ok(nbins)) return 0;
-    return (size_t)n_roi * (1 + total_bins(nbins)) * 8;
+    if (n_roi < 1 || n_roi > kMaxRoi || !of3dk::bins_ok<kNQ>(nbins)) return 0;
+    return (size_t)n_roi * (1 + of3dk::total_bins<kNQ>(nbins)) * 8;
 }
 
 size_t of3d_flow_whist_workspace_bytes(const int64_t* rois, int n_roi, const int* nbins) {
-    if (!bins_ok(nbins)) {
+    if (!of3dk::bins_ok<kNQ>(nbins)) {
         of3dk::set_error("of3d: 0 to 256 bins per quantity");
         return 0;
     }
-    const int ntot = total_bins(nbins);
+    const int ntot = of3dk::total_bins<kNQ>(nbins);
     if (!ntot) {
         of3dk::set_error("of3d: a weighted histogram needs bins for at least one quantity");
         return 0;
     }
-    size_t slot_words = 0, edge_words = 0;
+    size_t slot_words = 0;
     if (plan_boxes(rois, n_roi, nullptr, ntot, nullptr, nullptr, &slot_words) != 0) return 0;
-    for (int q = 0; q < kNQ; ++q) edge_words += nbins[q] ? nbins[q] + 1 : 0;
-    return (edge_words + slot_words) * sizeof(double);
+    return (of3dk::edge_words<kNQ>(nbins) + slot_words) * sizeof(double);
 }
 
 int of3d_flow_whist(const void* vx, const void* vy, const void* vz, const void* rel, int v_f32, int rel_f64,
@@ -236,48 +189,30 @@ int of3d_flow_whist(const void* vx, const void* vy, const void* vz, const void* 
     if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
         return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
     if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
-    if (!bins_ok(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
+    if (!of3dk::bins_ok<kNQ>(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     if (!vz && (nbins[2] || nbins[5])) return of3dk::set_error("of3d: vz and phi histograms need a 3D volume");
-    WhParams P;
-    memset(&P, 0, sizeof(P));
-    P.nz = (int)nz, P.ny = (int)ny, P.nx = (int)nx, P.n_roi = n_roi;
+    WhParams P{};
     P.sxy = xyscale, P.sz = zscale, P.st = tscale;
-    P.ntot = total_bins(nbins);
+    P.ntot = of3dk::total_bins<kNQ>(nbins);
     if (!P.ntot) return of3dk::set_error("of3d: a weighted histogram needs bins for at least one quantity");
     const int64_t dims[3] = {nz, ny, nx};
-    size_t slot_words = 0;
-    if (plan_boxes(rois, n_roi, dims, P.ntot, P.nb, P.soff, &slot_words) != 0) return -1;
-    int max_nb = 1;
-    for (int r = 0; r < n_roi; ++r) {
-        for (int a = 0; a < 6; ++a) P.box[r][a] = (int)rois[r * 6 + a];
-        max_nb = P.nb[r] > max_nb ? P.nb[r] : max_nb;
-    }
-    int eo = 0, ho = 0;
+    if (plan_boxes(rois, n_roi, dims, P.ntot, P.nb, P.soff) != 0) return -1;
+    const int max_nb = of3dk::fill_boxes(P, dims, rois, n_roi);
+    int all_nbins[kNQ], eoff[kNQ], hoff[kNQ];
     double host_edges[kEdgeWordsMax];
-    for (int q = 0; q < kNQ; ++q) {
+    const int eo = of3dk::plan_hists<kNQ>(nbins, edges, all_nbins, eoff, hoff, host_edges);
+    if (eo < 0) return -1;
+    for (int q = 0; q < kNQ; ++q) {  // the requested quantities, compacted
         if (!nbins[q]) continue;
-        if (!edges || !edges[q]) return of3dk::set_error("of3d: bins requested without edges");
-        for (int i = 0; i <= nbins[q]; ++i) {
-            const double e = edges[q][i];
-            if (!(e == e) || (i && !(e > edges[q][i - 1])))
-                return of3dk::set_error("of3d: bin edges must ascend strictly and hold no NaN");
-            host_edges[eo + i] = e;
-        }
         const int k = P.nq++;
-        P.q[k] = q, P.nbins[k] = nbins[q], P.eoff[k] = eo, P.hoff[k] = ho;
-        eo += nbins[q] + 1, ho += nbins[q];
+        P.q[k] = q, P.nbins[k] = nbins[q], P.eoff[k] = eoff[q], P.hoff[k] = hoff[q];
     }
     hipStream_t s = (hipStream_t)stream;
     double* d_edges = (double*)workspace;
     double* slots = d_edges + eo;
     u64* res = (u64*)d_result;
-    WH_HIP(hipMemsetAsync(d_result, 0, of3d_flow_whist_result_bytes(n_roi, nbins), s));
-    for (int o = 0; o < eo; o += kEdgeChunk) {
-        EdgeChunk c;
-        const int cnt = eo - o < kEdgeChunk ? eo - o : kEdgeChunk;
-        memcpy(c.e, host_edges + o, sizeof(double) * cnt);
-        hipLaunchKernelGGL(k_put_whist_edges, dim3(1), dim3(kEdgeChunk), 0, s, d_edges + o, c, cnt);
-    }
+    OF3DK_HIP(hipMemsetAsync(d_result, 0, of3d_flow_whist_result_bytes(n_roi, nbins), s));
+    of3dk::put_edges(s, d_edges, host_edges, eo);
     const dim3 grid(max_nb, n_roi, P.nq);
     auto launch = [&](auto vt, auto rt) {
         using VT = decltype(vt);
@@ -296,7 +231,7 @@ int of3d_flow_whist(const void* vx, const void* vy, const void* vz, const void* 
     else
         rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
     hipLaunchKernelGGL(k_whist_final, dim3((P.ntot + 255) / 256, n_roi), dim3(256), 0, s, (const double*)slots, P, res);
-    WH_HIP(hipGetLastError());
+    OF3DK_HIP(hipGetLastError());
     return 0;
 }
 

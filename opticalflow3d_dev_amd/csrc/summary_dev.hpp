@@ -3,62 +3,16 @@
 // k_sum_boxes), the projected flow (kt_axes.hip: k_proj_boxes), the magnitude-weighted
 // histograms (kt_whist.hip: k_whist_boxes) and the two-channel comparison (kt_pair.hip:
 // k_pair_boxes): one statement of the masking arithmetic, the histogram bin search, the walk
-// over a box and the plan of the boxes' workgroups, so the passes cannot drift apart.
+// over a box, a workgroup's share of a box and the reduction of its sums, so the passes cannot
+// drift apart.  The host side (box check, workgroup plan, histogram plan, edge upload) is
+// summary_host.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <string>
 
-#include "../../include/of3d.h"
-#include "kernels.hpp"
+#include "summary_host.hpp"
 
 namespace of3dk {
-
-// The workgroup partition of a box's reduction (k_sum_boxes, k_proj_boxes, k_whist_boxes, k_pair_boxes): workgroup b of nb
-// walks rows [b*R/nb, (b+1)*R/nb) of the box's R = dz*dy rows.  nb is a function of the box
-// alone (never of the device), so the summation order is fixed.
-constexpr int kSumThreads = 512, kSumWaves = kSumThreads / 64;
-constexpr int kSumMaxBlocks = 1024;        // workgroups (workspace slots) per box at most
-constexpr int64_t kSumVoxPerBlock = 8192;  // a workgroup's share of a box at least
-inline int64_t sum_workgroups(int64_t vox, int64_t rows) {
-    int64_t nb = (vox + kSumVoxPerBlock - 1) / kSumVoxPerBlock;
-    nb = nb > kSumMaxBlocks ? kSumMaxBlocks : nb;
-    return nb > rows ? rows : nb;
-}
-
-// The boxes of a pass with per-workgroup workspace slots (of3d_flow_whist, of3d_flow_pair) as
-// of3d_flow_summary validates them (dims NULL: against 2^31 alone) and their workgroups;
-// soff_out[r]: the first slot word of box r, slot_words: the sum over the boxes of
-// workgroups * wg_words.
-inline int plan_boxes(const int64_t* rois, int n_roi, const int64_t* dims, int wg_words, int* nb_out,
-                      long long* soff_out, size_t* slot_words) {
-    constexpr int kMaxRoi = OF3D_SUMMARY_MAX_ROI;
-    if (!rois) return set_error("of3d: null argument");
-    if (n_roi < 1 || n_roi > kMaxRoi) return set_error("of3d: 1 to 16 ROI boxes");
-    size_t words = 0;
-    for (int r = 0; r < n_roi; ++r) {
-        int64_t ext[3];
-        for (int a = 0; a < 3; ++a) {
-            const int64_t b0 = rois[r * 6 + 2 * a], b1 = rois[r * 6 + 2 * a + 1];
-            if (b0 < 0 || b0 >= b1 || b1 > (dims ? dims[a] : (int64_t)INT32_MAX))
-                return set_error(("of3d: ROI " + std::to_string(r) + " is empty or outside the volume").c_str());
-            ext[a] = b1 - b0;
-        }
-        // a function of the box alone (never of the device): the summation order is fixed
-        const int64_t rows = ext[0] * ext[1];  // < 2^62
-        const int64_t big = INT64_MAX / 2;     // stands for any larger voxel count: the cap decides
-        const int64_t nb = sum_workgroups(ext[2] > big / rows ? big : rows * ext[2], rows);
-        // a workgroup's share, at most ceil(rows / nb) rows of ext[2] voxels, must stay below lim
-        const int64_t lim = ((int64_t)1 << 31) - 4 * kSumThreads;
-        if ((rows + nb - 1) / nb >= (lim + ext[2] - 1) / ext[2])
-            return set_error("of3d: ROI too large (2^31 voxels per workgroup)");
-        if (nb_out) nb_out[r] = (int)nb;
-        if (soff_out) soff_out[r] = (long long)words;
-        words += (size_t)nb * wg_words;
-    }
-    *slot_words = words;
-    return 0;
-}
 
 // np.histogram(v, bins=e): e[i] <= v < e[i+1], the last bin closed; -1: dropped (outside, NaN)
 __device__ __forceinline__ int find_bin(const double* e, int nb, double v) {
@@ -124,5 +78,72 @@ struct BoxWalk {
         z += step_z + c;
     }
 };
+
+// Workgroup blockIdx.x's share of box `roi` (rows [b*R/nb, (b+1)*R/nb) of its R = dz*dy rows) and
+// this thread's walk over it, kSumThreads voxels per step.
+struct BoxShare {
+    int z0, y0, x0, ny, nx;
+    unsigned dy, dx;
+    long long count;  // this workgroup's voxels (< 2^31: checked on the host)
+    BoxWalk w;        // this thread's voxel as (z, y, x) inside the box
+
+    // the walk's voxel in the whole volume
+    __device__ __forceinline__ size_t index() const { return ((size_t)(z0 + w.z) * ny + (y0 + w.y)) * nx + (x0 + w.x); }
+};
+
+__device__ __forceinline__ BoxShare box_share(const BoxParams& P, int roi, int nb) {
+    const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
+    const unsigned dy = P.box[roi][3] - y0, dx = P.box[roi][5] - x0;
+    const long long R = (long long)(P.box[roi][1] - z0) * dy;
+    const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
+    return {z0, y0, x0, P.ny, P.nx, dy, dx, (r1 - r0) * dx, BoxWalk(dy, dx, r0, threadIdx.x, kSumThreads)};
+}
+
+// The fixed shuffle tree over a wave's 64 lanes, all of them active: lane 0 returns the sum
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// A workgroup's N sums into its workspace slot, called by all kSumThreads threads (full EXEC):
+// per sum wave_sum's tree over the lanes, then the waves' partials added in wave order.
+template <int N>
+__device__ __forceinline__ void reduce_to_slot(const double (&acc)[N], double (*wsum)[N], double* __restrict__ slot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        const double v = wave_sum(acc[q]);
+        if (lane == 0) wsum[wave][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        double v = wsum[0][threadIdx.x];
+        for (int j = 1; j < kSumWaves; ++j) v += wsum[j][threadIdx.x];
+        slot[threadIdx.x] = v;
+    }
+}
+
+// A workgroup's LDS histogram (counts) into a box's result words by 64-bit integer atomics
+__device__ __forceinline__ void flush_hist(const unsigned* hist, int ntot, unsigned long long* __restrict__ dst) {
+    for (int i = threadIdx.x; i < ntot; i += kSumThreads)
+        if (hist[i]) atomicAdd(&dst[i], (unsigned long long)hist[i]);
+}
+
+// The final pass of a box, one workgroup of kFinalThreads: G sums of each of its nb slots (slot
+// b's at src + b * Stride) staged in LDS (s: nb * G doubles), each then added in slot order by
+// one thread and stored as its bits in dst[0 .. G).
+constexpr int kFinalThreads = 256;
+template <int G, int Stride>
+__device__ __forceinline__ void add_slots(const double* __restrict__ src, int nb, double* s,
+                                          unsigned long long* __restrict__ dst) {
+    for (int i = threadIdx.x; i < nb * G; i += kFinalThreads) s[i] = src[(size_t)(i / G) * Stride + i % G];
+    __syncthreads();
+    if (threadIdx.x < G) {
+        double v = s[threadIdx.x];
+        for (int b = 1; b < nb; ++b) v += s[b * G + threadIdx.x];
+        dst[threadIdx.x] = (unsigned long long)__double_as_longlong(v);
+    }
+}
 
 }  // namespace of3dk
