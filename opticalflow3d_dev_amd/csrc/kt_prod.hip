@@ -4,23 +4,26 @@
 
 namespace of3dk {
 
-// K34 instances: W radii with a compiled register ring, wSig 3..7 (others use K3 + K4)
+// K34 instances: W radii with a compiled register ring, wSig 3..7 (others use K3 + K4).  Every
+// getter picks by radius and tile height: OF3D_K34_PICK(RW, SA, SB) returns the getter's kernel
+// OF3D_K34_KERNEL(RW, S) for radius RW at tile height SA or SB.
+#define OF3D_K34_PICK(RW, SA, SB)                                     \
+    if (rw == RW) {                                                   \
+        if (s == SA) return (const void*)OF3D_K34_KERNEL(RW, SA);     \
+        if (s == SB) return (const void*)OF3D_K34_KERNEL(RW, SB);     \
+    }
+
 template <typename F, int NP>
 const void* k34_fn(int rw, int s, int rb) {
-#define OF3D_K34(RW, SA, SB)                                    \
-    case RW:                                                    \
-        if (s == SA) return rb == 2 ? nullptr : (const void*)k_prod_wyx<F, NP, RW, SA>;                                     \
-        if (s == SB) return rb == 2 ? nullptr : (const void*)k_prod_wyx<F, NP, RW, SB>;                                     \
-        return nullptr;
-    switch (rw) {
-        OF3D_K34(9, 16, 8)
-        OF3D_K34(12, 16, 8)
-        OF3D_K34(15, 16, 8)
-        OF3D_K34(18, 8, 4)  // register ring of 38-48 rows: shorter tiles
-        OF3D_K34(21, 8, 4)
-        default: return nullptr;
-    }
-#undef OF3D_K34
+    if (rb == 2) return nullptr;
+#define OF3D_K34_KERNEL(RW, S) k_prod_wyx<F, NP, RW, S>
+    OF3D_K34_PICK(9, 16, 8)
+    OF3D_K34_PICK(12, 16, 8)
+    OF3D_K34_PICK(15, 16, 8)
+    OF3D_K34_PICK(18, 8, 4)  // register ring of 38-48 rows: shorter tiles
+    OF3D_K34_PICK(21, 8, 4)
+#undef OF3D_K34_KERNEL
+    return nullptr;
 }
 
 // Unique-staging instances (k_prod_wyx UQ: no duplicated halo columns, edge replicas copied)
@@ -30,17 +33,13 @@ const void* k34_fn(int rw, int s, int rb) {
 // deeper prefetch (8, 11 rows) or LDS distance 4 within noise.
 template <typename F, int NP>
 const void* k34_fn_uq(int rw, int s) {
-#define OF3D_K34U(RW)                                                                      \
-    if (rw == RW) {                                                                        \
-        if (s == 8) return (const void*)k_prod_wyx<F, NP, RW, 8, 4, 2, 4, 2, true>;        \
-        if (s == 4) return (const void*)k_prod_wyx<F, NP, RW, 4, 4, 2, 4, 2, true>;        \
-    }
-    OF3D_K34U(21)
-    OF3D_K34U(18)
-    OF3D_K34U(15)
-    OF3D_K34U(12)
-    OF3D_K34U(9)
-#undef OF3D_K34U
+#define OF3D_K34_KERNEL(RW, S) k_prod_wyx<F, NP, RW, S, 4, 2, 4, 2, true>
+    OF3D_K34_PICK(21, 8, 4)
+    OF3D_K34_PICK(18, 8, 4)
+    OF3D_K34_PICK(15, 8, 4)
+    OF3D_K34_PICK(12, 8, 4)
+    OF3D_K34_PICK(9, 8, 4)
+#undef OF3D_K34_KERNEL
     return nullptr;
 }
 
@@ -54,45 +53,40 @@ const void* k34_fn_ws(int rw, int s, int npw, int pd) {
     if (npw != 8 && (npw != 9 || sizeof(F) != 8)) return nullptr;
     if (pd == 4) {
         if (sizeof(F) != 8 || s != 4) return nullptr;
-#define OF3D_K34W4(RW) \
-        if (rw == RW) return npw == 8 ? (const void*)k_prod_wyx_ws<F, NP, RW, 4, 4, 2, 8> : (const void*)k_prod_wyx_ws<F, NP, RW, 4, 4, 2, 9>;
-        OF3D_K34W4(15)
-        OF3D_K34W4(12)
-        OF3D_K34W4(9)
-#undef OF3D_K34W4
+#define OF3D_K34_PD4(RW) \
+    if (rw == RW) return npw == 8 ? (const void*)k_prod_wyx_ws<F, NP, RW, 4, 4, 2, 8> : (const void*)k_prod_wyx_ws<F, NP, RW, 4, 4, 2, 9>;
+        OF3D_K34_PD4(15)
+        OF3D_K34_PD4(12)
+        OF3D_K34_PD4(9)
+#undef OF3D_K34_PD4
         return nullptr;
     }
     if (pd != 2) return nullptr;
-#define OF3D_K34W(RW)                                                                                              \
-    if (rw == RW) {                                                                                                \
-        if (s == 8) return npw == 8 ? (const void*)k_prod_wyx_ws<F, NP, RW, 8> : (const void*)k_prod_wyx_ws<F, NP, RW, 8, 2, 2, 9>; \
-        if (s == 4) return npw == 8 ? (const void*)k_prod_wyx_ws<F, NP, RW, 4> : (const void*)k_prod_wyx_ws<F, NP, RW, 4, 2, 2, 9>; \
-    }
-    OF3D_K34W(21)
-    OF3D_K34W(18)
-    OF3D_K34W(15)
-    OF3D_K34W(12)
-    OF3D_K34W(9)
-#undef OF3D_K34W
+#define OF3D_K34_KERNEL(RW, S) \
+    (npw == 8 ? (const void*)k_prod_wyx_ws<F, NP, RW, S> : (const void*)k_prod_wyx_ws<F, NP, RW, S, 2, 2, 9>)
+    OF3D_K34_PICK(21, 8, 4)
+    OF3D_K34_PICK(18, 8, 4)
+    OF3D_K34_PICK(15, 8, 4)
+    OF3D_K34_PICK(12, 8, 4)
+    OF3D_K34_PICK(9, 8, 4)
+#undef OF3D_K34_KERNEL
     return nullptr;
 }
 
 // Packed-fp32 instances (k_prod_wyx_pk: 4 producer + 4 consumer waves on float2 lanes)
 template <int NP>
 const void* k34_fn_pk(int rw, int s) {
-#define OF3D_K34P(RW)                                                      \
-    if (rw == RW) {                                                        \
-        if (s == 8) return (const void*)k_prod_wyx_pk<NP, RW, 8>;          \
-        if (s == 4) return (const void*)k_prod_wyx_pk<NP, RW, 4>;          \
-    }
-    OF3D_K34P(21)
-    OF3D_K34P(18)
-    OF3D_K34P(15)
-    OF3D_K34P(12)
-    OF3D_K34P(9)
-#undef OF3D_K34P
+#define OF3D_K34_KERNEL(RW, S) k_prod_wyx_pk<NP, RW, S>
+    OF3D_K34_PICK(21, 8, 4)
+    OF3D_K34_PICK(18, 8, 4)
+    OF3D_K34_PICK(15, 8, 4)
+    OF3D_K34_PICK(12, 8, 4)
+    OF3D_K34_PICK(9, 8, 4)
+#undef OF3D_K34_KERNEL
     return nullptr;
 }
+#undef OF3D_K34_PICK
+
 template const void* k34_fn_pk<9>(int, int);
 template const void* k34_fn_pk<5>(int, int);
 

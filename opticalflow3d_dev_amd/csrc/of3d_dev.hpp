@@ -768,6 +768,11 @@ __host__ __device__ constexpr int k34_row(int r, int cwp) { return r * cwp + 28 
 __host__ __device__ constexpr int k34_tile(int s, int cwp) { return s * cwp + 28 * (s / 4); }  // per tile buffer
 // tile row pitch for a block of tx outputs: its 2 rw halo positions, = 1 (mod 32)
 __host__ __device__ constexpr int k34_pitch(int tx, int rw) { return ((tx + 2 * rw + 31) & ~31) + 1; }
+// dynamic LDS of a K34 block: two W-y tiles of s rows at pitch cwp, es bytes an element; packed:
+// k_prod_wyx_pk's two tiles of s / 2 row pairs of float2 at pitch cwp, no row offsets
+constexpr size_t k34_lds(int s, int cwp, size_t es, bool packed = false) {
+    return packed ? (size_t)s * cwp * 8 : (size_t)2 * k34_tile(s, cwp) * es;
+}
 
 // value of lane `lane` (wave-uniform index) of a per-lane F, to every lane of the wave
 template <typename F>
@@ -862,22 +867,167 @@ __device__ __forceinline__ unsigned wxy_off(const WxyMap& m, int r, int x) {
     return (unsigned)r * m.rs + ((ux >> m.sh) * m.cm + (ux & m.msk)) * (unsigned)sizeof(F);
 }
 
+// ---- the parts the three K34 kernels share (k_prod_wyx, k_prod_wyx_ws, k_prod_wyx_pk) ----
+// Force-inlined into the same arithmetic order in each kernel.  A kernel uses a part unless the
+// part moves the registers, scratch or occupancy of one of its instances, or measurably slows it
+// (which kernel uses which part; the ring prologue, the march loop and the tail
+// store stay written out in each kernel).
+
+// Block geometry: output rows [y0, y0 + nrows) of [yb0, yb1) (row-slab plans: the rank's own
+// rows; loads still clamp at [0, ny)), outputs [xo0, xo0 + txu) of the row, and the staged
+// columns, tile position i <-> column xo0 - RW + i.
+// UQ = false (duplicate staging): thread t stages column clamp(xo0 - RW + t) at position t, halo
+//   positions outside the volume (mode='nearest') recomputed as duplicates of the edge column
+//   (txu + 2 RW <= blockDim.x by the host's geometry); no pads.
+// UQ = true (unique staging): the block's outputs and their W-x halo inside the volume, each once
+//   ([sxs, sxs + ns), ns <= the block's staging threads by the host's geometry): thread t holds
+//   column sxs + t at position padL + t (the packed kernel: a column pair per thread); the padL / padR
+//   positions outside the volume are edge replicas copied once per tile (no halo work at all
+//   for a block covering the whole row).
+struct K34Geo {
+    int zl, yc, bx, p;
+    int y0, nrows, xo0, txu, sxs, ns, padL, padR;
+};
+template <bool UQ>
+__device__ __forceinline__ K34Geo k34_geo(const K34Blk& b, int tx, int nyc, int yb0, int yb1, int nx, int rw) {
+    K34Geo g;
+    g.zl = b.zl, g.yc = b.yc, g.bx = b.bx, g.p = b.p;
+    g.y0 = yb0 + b.yc * nyc;
+    g.nrows = min(nyc, yb1 - g.y0);
+    g.xo0 = b.bx * tx;
+    g.txu = min(tx, nx - g.xo0);  // useful outputs of this block
+    g.sxs = UQ ? max(g.xo0 - rw, 0) : g.xo0 - rw;
+    g.ns = UQ ? min(g.xo0 + g.txu + rw, nx) - g.sxs : g.txu + 2 * rw;
+    g.padL = UQ ? g.sxs - (g.xo0 - rw) : 0;
+    g.padR = UQ ? (g.xo0 + g.txu + rw) - (g.sxs + g.ns) : 0;
+    return g;
+}
+
+// Product sources: the two gradient fields of product p of NP (nibble tables as k_prod_wy), in
+// the plane at element offset pl, as buffer descriptors
+struct K34Src {
+    __amdgpu_buffer_rsrc_t a, b;
+};
+template <int NP, typename F>
+__device__ __forceinline__ K34Src k34_src(const F* G, size_t fs, size_t pl, int p) {
+    constexpr unsigned long long pa = NP == 9 ? 0x311222312ull : 0x12212ull;
+    constexpr unsigned long long pb = NP == 9 ? 0x313231000ull : 0x12100ull;
+    const auto a = buf_rsrc(G + (size_t)((pa >> (4 * p)) & 15u) * fs + pl);
+    const auto b = buf_rsrc(G + (size_t)((pb >> (4 * p)) & 15u) * fs + pl);
+    return {a, b};
+}
+// byte offset of ring row idx of a block (row y0 - RW + idx, clamped to the plane; rowb bytes per row)
+template <int RW>
+struct K34Rows {
+    int y0, ny;
+    unsigned rowb;
+    __device__ __forceinline__ unsigned off(int idx) const { return (unsigned)clampi(y0 - RW + idx, 0, ny - 1) * rowb; }
+};
+
+// Edge replicas of a unique-staging tile, copied once per tile by the wave that wrote the edge
+// column (its own LDS writes are ordered before its reads).  The wave index sits in an SGPR: the
+// branches on lpad / rpad (this wave holds column 0 in lane 0 / holds column nx - 1) are scalar, not
+// exec-masked; ln: the lane.
+// ROWS tile rows of V, row r at tile + row_at(r)
+template <int ROWS, typename V, typename RowAt>
+__device__ __forceinline__ void k34_replicas(V* tile, RowAt row_at, bool lpad, bool rpad, int ln, const K34Geo& g) {
+    if (lpad) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            V* row = tile + row_at(r);
+            const V v = row[g.padL];
+            if (ln < g.padL) row[ln] = v;
+        }
+    }
+    if (rpad) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            V* row = tile + row_at(r);
+            const V v = row[g.padL + g.ns - 1];
+            if (ln < g.padR) row[g.padL + g.ns + ln] = v;
+        }
+    }
+}
+
+// Phase A of one thread: the register ring of NR product rows (row j in slot (j - y0 + RW) mod NR)
+// and the raw gradient rows PD ahead (ra, rb); ld(descriptor, row offset): this thread's staged
+// column of one gradient row.  The prologue in the kernels fills slots 0 .. 2 RW and the first
+// PD prefetch rows.
+// Step j of the ring period starting at row u0: the W-y values a0, a1 of rows j, j + 1.  Two
+// rows per step, their tap chains interleaved (ILP: a single chain issues one fp64 op per
+// dependent latency).  Row j + 1's new product lands in row j's outermost slot, so it is
+// written after row j's first tap.
+// FENCED: the two chains side by side: without the two empty asm fences the scheduler issued
+// half of a 16-wave producer's ops right behind the op they depend on; with them 2 % (c3 K34
+// 1.665 -> 1.631 ms, c4 equal: profiles/r04/ab_k34ilp/).  Same ops, same order per chain
+// (bit-identical).  The packed fp32 kernel spills with it and the lockstep one keeps its form.
+template <int j, int RW, bool FENCED, typename V, int NR, int PD, typename Ld>
+__device__ __forceinline__ void k34_ring_step(V (&ring)[NR], V (&ra)[PD], V (&rb)[PD], Ld ld, const K34Src& src,
+                                              const K34Rows<RW>& rows, int u0, const V (&h)[RW + 1], V& a0, V& a1) {
+    static_assert(NR % PD == 0, "ring sizes");
+    constexpr int ic = j + 2 * RW + 1, ic1 = ic + 1;
+    ring[ic % NR] = ra[ic % PD] * rb[ic % PD];
+    const unsigned o = rows.off(u0 + ic + PD);
+    ra[ic % PD] = ld(src.a, o);
+    rb[ic % PD] = ld(src.b, o);
+    V p1 = ra[ic1 % PD] * rb[ic1 % PD];
+    const unsigned o1 = rows.off(u0 + ic1 + PD);
+    ra[ic1 % PD] = ld(src.a, o1);
+    rb[ic1 % PD] = ld(src.b, o1);
+    a0 = ring[(j + RW) % NR] * h[0];
+    a1 = ring[(j + 1 + RW) % NR] * h[0];
+    a0 = a0 + (ring[j % NR] + ring[(j + 2 * RW) % NR]) * h[RW];
+    a1 = a1 + (ring[(j + 1) % NR] + ring[(j + 1 + 2 * RW) % NR]) * h[RW];
+    ring[ic1 % NR] = p1;  // slot of row j - RW (NR = 2 RW + 2): free now
+#pragma unroll
+    for (int k = RW - 1; k >= 1; --k) {
+        if constexpr (FENCED) {
+            V s0 = ring[(j + RW - k) % NR] + ring[(j + RW + k) % NR];
+            V s1 = ring[(j + 1 + RW - k) % NR] + ring[(j + 1 + RW + k) % NR];
+            asm volatile("" : "+v"(s0), "+v"(s1));
+            s0 = s0 * h[k];
+            s1 = s1 * h[k];
+            asm volatile("" : "+v"(s0), "+v"(s1));
+            a0 = a0 + s0;
+            a1 = a1 + s1;
+        } else {
+            a0 = a0 + (ring[(j + RW - k) % NR] + ring[(j + RW + k) % NR]) * h[k];
+            a1 = a1 + (ring[(j + 1 + RW - k) % NR] + ring[(j + 1 + RW + k) % NR]) * h[k];
+        }
+    }
+}
+
+// Phase-B items of a tile of S rows (RB consecutive outputs each).  Item -> lane, conflict-free
+// for both LDS read forms (ds_read_b64: 32-lane groups, 64 banks; ds_read2_b64: 16-lane groups,
+// 32 banks): lane bits b5..b0 give row (b3b2) + 4 b5 and segment (b1b0) + 4 b4, and row r starts
+// at k34_row(r) = r mod 4 (mod 32 doubles), so a lane reads at (b3b2) + 4 (b1b0) + 16 b4 (mod 32):
+// 16 distinct mod 16, 32 distinct mod 32.  S = 4: rows (b3b2), segment (b1b0) + 4 b4 + 8 b5.
+template <int S>
+struct K34Items {
+    static constexpr int RPW = S < 8 ? S : 8, SPW = 64 / RPW;  // rows / segments per wave-item group
+    static constexpr int RG = S / RPW;                          // row groups
+    static __device__ __forceinline__ void at(int i, int& r, int& sg) {
+        const int l = i & 63, wg = i >> 6;
+        r = (wg % RG) * RPW + ((l >> 2) & 3) + (S >= 8 ? 4 * (l >> 5) : 0);
+        sg = (wg / RG) * SPW + (l & 3) + 4 * ((l >> 4) & 1) + (S >= 8 ? 0 : 8 * (l >> 5));
+    }
+};
+
+// The lockstep K34: every wave runs phase A, then phase B of the same tile.
 // OCC: waves per SIMD the register budget is cut for (3: 168 VGPRs; 2: 256, for 8-wave blocks,
 // which run one per CU anyway); PDX: gradient prefetch rows (0: as far as OCC 3 allows);
-// DB: LDS prefetch distance of the phase-B pass; UQ: staging (below).
+// DB: LDS prefetch distance of the phase-B pass; UQ: staging (K34Geo).
+// RB: W-x outputs per phase-B item (RB 2 measured slower: c2 +16 %, c3 +15 %; not instantiated)
 template <typename F, int NP, int RW, int S, int RB = 4, int OCC = 3, int PDX = 0, int DB = 2,
           bool UQ = false>
 __global__ __launch_bounds__(512, OCC) void k_prod_wyx(const F* __restrict__ G, F* __restrict__ Q, int ny,
                                                        int nx, size_t fs, const F* __restrict__ hw, int tx,
                                                        int nyc, int nbx, int nyb, int cpg, int ngroups, int yb0,
                                                        int yb1, int zt) {
-    constexpr int NR = k34_nr(RW, S);
     // gradient prefetch distance (rows): as far as 168 VGPRs (3 waves/SIMD) allow
-    constexpr int PD0 = PDX ? PDX : (sizeof(F) == 8 ? (RW >= 18 ? 2 : 4) : (RW >= 18 ? 4 : 8));
-    constexpr int PD = PD0;
-    // RB: W-x outputs per phase-B item (RB 2 measured slower: c2 +16 %, c3 +15 %; not instantiated)
-    constexpr unsigned ES = sizeof(F);
-    static_assert(NR % PD == 0 && NR % S == 0, "ring sizes");
+    constexpr int NR = k34_nr(RW, S), PD = PDX ? PDX : (sizeof(F) == 8 ? (RW >= 18 ? 2 : 4) : (RW >= 18 ? 4 : 8));
+    static_assert(NR % S == 0, "ring sizes");
+    using It = K34Items<S>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     F* sw = reinterpret_cast<F*>(smem_raw);  // two W-y tiles [2][S][cwp] (tile n in buffer n & 1)
     const int cwp = UQ ? k34_pitch(min(tx, nx), RW) : (int)blockDim.x + 1;
@@ -886,115 +1036,67 @@ __global__ __launch_bounds__(512, OCC) void k_prod_wyx(const F* __restrict__ G, 
     // run, product, column block): one group's blocks share an XCD and are dispatched together
     const K34Blk kbk = k34_block<NP>(nbx, nyb, cpg, ngroups);
     if (!kbk.ok) return;
-    const int bx = kbk.bx, p = kbk.p, zl = kbk.zl, yc = kbk.yc;
-    // output rows [yb0, yb1) (row-slab plans: the rank's own rows; loads still clamp at [0, ny))
-    const int y0 = yb0 + yc * nyc, nrows = min(nyc, yb1 - y0);
-    const int xo0 = bx * tx;
-    const int txu = min(tx, nx - xo0);  // useful outputs of this block
-    // Staged columns, tile position i <-> column xo0 - RW + i.
-    // UQ = false: thread t stages column clamp(xo0 - RW + t) at position t, halo positions
-    //   outside the volume (mode='nearest') recomputed as duplicates of the edge column
-    //   (txu + 2 RW <= blockDim.x by the host's geometry).
-    // UQ = true: the block's outputs and their W-x halo inside the volume, each once
-    //   ([sxs, sxs + ns), ns <= blockDim.x): thread t holds column sxs + t at position padL + t;
-    //   the positions outside the volume are edge replicas copied once per tile (no halo work
-    //   at all for a block covering the whole row).
-    const int sxs = UQ ? max(xo0 - RW, 0) : xo0 - RW;
-    const int ns = UQ ? min(xo0 + txu + RW, nx) - sxs : txu + 2 * RW;
-    const int padL = UQ ? sxs - (xo0 - RW) : 0, padR = UQ ? (xo0 + txu + RW) - (sxs + ns) : 0;
+    const K34Geo g = k34_geo<UQ>(kbk, tx, nyc, yb0, yb1, nx, RW);
     // waves with no staged column leave at once; barriers count only the waves still running
-    const int wa = (ns + 63) >> 6, ca = 64 * wa;
+    const int wa = (g.ns + 63) >> 6, ca = 64 * wa;
     if (t >= ca) return;
-    const unsigned vof = (unsigned)clampi(sxs + t, 0, nx - 1) * ES;  // staged column of this thread
-    // wave index in an SGPR: the edge-replica branches below are scalar, not exec-masked
+    const unsigned vof = (unsigned)clampi(g.sxs + t, 0, nx - 1) * (unsigned)sizeof(F);  // staged column of this thread
+    // wave index in an SGPR: the edge-replica branches are scalar, not exec-masked
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6), ln = t & 63;
-    const bool lpad = UQ && padL > 0 && wv == 0;                  // wave 0 holds column 0 in lane 0
-    const bool rpad = UQ && padR > 0 && wv == ((ns - 1) >> 6);    // this wave holds column nx - 1
+    const bool lpad = UQ && g.padL > 0 && wv == 0;                  // wave 0 holds column 0 in lane 0
+    const bool rpad = UQ && g.padR > 0 && wv == ((g.ns - 1) >> 6);  // this wave holds column nx - 1
     // UQ: lanes past ns (last wave) compute a duplicate and store it past the row's positions
     // (pitch cwp >= txu + 2 RW + 1; that slot only feeds outputs >= txu, never stored)
-    const int wpos = !UQ ? t : (t < ns ? padL + t : padL + ns + padR);
-    // W-y result of one row into the tile; the edge replicas are copied once per tile by the
-    // wave that wrote the edge column (its own LDS writes are ordered before its reads)
-    auto put = [&](F* row, F a) { row[wpos] = a; };
-    auto replicas = [&](F* tile) {
-        if (lpad) {
-#pragma unroll
-            for (int r = 0; r < S; ++r) {
-                F* row = tile + k34_row(r, cwp);
-                const F e = row[padL];
-                if (ln < padL) row[ln] = e;
-            }
-        }
-        if (rpad) {
-#pragma unroll
-            for (int r = 0; r < S; ++r) {
-                F* row = tile + k34_row(r, cwp);
-                const F e = row[padL + ns - 1];
-                if (ln < padR) row[padL + ns + ln] = e;
-            }
-        }
-    };
-    constexpr unsigned long long pa = NP == 9 ? 0x311222312ull : 0x12212ull;  // as k_prod_wy
-    constexpr unsigned long long pb = NP == 9 ? 0x313231000ull : 0x12100ull;
-    const size_t pl = (size_t)zl * ny * nx;
-    const auto ra_ = buf_rsrc(G + (size_t)((pa >> (4 * p)) & 15u) * fs + pl);
-    const auto rb_ = buf_rsrc(G + (size_t)((pb >> (4 * p)) & 15u) * fs + pl);
-    F* const Qp = Q + (size_t)p * fs;
+    const int wpos = !UQ ? t : (t < g.ns ? g.padL + t : g.padL + g.ns + g.padR);
+    const K34Src src = k34_src<NP>(G, fs, (size_t)g.zl * ny * nx, g.p);
+    F* const Qp = Q + (size_t)g.p * fs;
     const WxyMap wm = wxy_map<F>(nx, zt);
-    const unsigned rowb = (unsigned)nx * ES;
+    const K34Rows<RW> rows{g.y0, ny, (unsigned)nx * (unsigned)sizeof(F)};
     F h[RW + 1];
 #pragma unroll
     for (int k = 0; k <= RW; ++k) h[k] = hw[k];
-    auto rowoff = [&](int idx) { return (unsigned)clampi(y0 - RW + idx, 0, ny - 1) * rowb; };
+    auto ld = [&](const __amdgpu_buffer_rsrc_t& r, unsigned o) { return buf_ld<F>(r, vof, o); };
     F ring[NR], ra[PD], rb[PD];
 #pragma unroll
-    for (int i = 0; i <= 2 * RW; ++i) {
-        const unsigned o = rowoff(i);
-        ring[i] = buf_ld<F>(ra_, vof, o) * buf_ld<F>(rb_, vof, o);
+    for (int i = 0; i <= 2 * RW; ++i) {  // ring prologue (see k34_ring_step): products of rows 0 .. 2 RW
+        const unsigned o = rows.off(i);
+        ring[i] = ld(src.a, o) * ld(src.b, o);
     }
 #pragma unroll
-    for (int i = 0; i < PD; ++i) {
-        const unsigned o = rowoff(2 * RW + 1 + i);
-        ra[(2 * RW + 1 + i) % PD] = buf_ld<F>(ra_, vof, o);
-        rb[(2 * RW + 1 + i) % PD] = buf_ld<F>(rb_, vof, o);
+    for (int i = 0; i < PD; ++i) {  // and the first PD prefetch rows
+        const unsigned o = rows.off(2 * RW + 1 + i);
+        ra[(2 * RW + 1 + i) % PD] = ld(src.a, o);
+        rb[(2 * RW + 1 + i) % PD] = ld(src.b, o);
     }
-    const int nseg = (txu + RB - 1) / RB;
-    // phase B: W x over tile buffer `tile` (rows r < S), RB consecutive outputs per item
-    // stored straight from registers (rows [yb, yb + nr) only).  One barrier per tile:
-    // the other buffer is being filled by phase A meanwhile.
-    // Item -> lane, conflict-free for both LDS read forms (ds_read_b64: 32-lane groups,
-    // 64 banks; ds_read2_b64: 16-lane groups, 32 banks): lane bits b5..b0 give row
-    // (b3b2) + 4 b5 and segment (b1b0) + 4 b4, and row r starts at rowoff(r) =
-    // r cwp + off(r) with rowoff(r) = r mod 4 (mod 32 doubles), so a lane reads at
-    // (b3b2) + 4 (b1b0) + 16 b4 (mod 32): 16 distinct mod 16, 32 distinct mod 32.
-    // S = 4: rows (b3b2), segment (b1b0) + 4 b4 + 8 b5.
-    constexpr int RPW = S < 8 ? S : 8, SPW = 64 / RPW;  // rows / segments per wave-item group
-    constexpr int RG = S / RPW;                          // row groups
-    const int nsgw = (nseg + SPW - 1) / SPW;
+    const int nseg = (g.txu + RB - 1) / RB;
+    const int nsgw = (nseg + It::SPW - 1) / It::SPW;
+    // phase B: W x over tile buffer `tile` (rows r < S), rows [yb, yb + nr) stored.  One barrier
+    // per tile: the other buffer is being filled by phase A meanwhile.
     auto phase_b = [&](const F* tile, int yb, int nr) {
         lds_barrier();
-        const auto rq_ = wxy_rsrc(Qp, zl, yb, ny, nx, zt);
-        for (int i = t; i < 64 * RG * nsgw; i += ca) {
-            const int l = i & 63, wg = i >> 6;
-            const int r = (wg % RG) * RPW + ((l >> 2) & 3) + (S >= 8 ? 4 * (l >> 5) : 0);
-            const int sg = (wg / RG) * SPW + (l & 3) + 4 * ((l >> 4) & 1) + (S >= 8 ? 0 : 8 * (l >> 5));
+        const auto rq_ = wxy_rsrc(Qp, g.zl, yb, ny, nx, zt);
+        for (int i = t; i < 64 * It::RG * nsgw; i += ca) {
+            int r, sg;
+            It::at(i, r, sg);
             if (sg >= nseg) continue;
             F out[RB];
             lds_pass_c<RB, RW, DB>(tile + k34_row(r, cwp), 1, RW + RB * sg, h, out);
             if (r < nr) {
                 // row offset per lane in voffset (a divergent soffset would be a waterfall loop)
                 const int c0 = RB * sg;
-                const unsigned vo = wxy_off<F>(wm, r, xo0 + c0);
-                if (c0 + RB <= txu) {
+                const unsigned vo = wxy_off<F>(wm, r, g.xo0 + c0);
+                if (c0 + RB <= g.txu) {
                     buf_st_n<F, RB>(out, rq_, vo, 0);
                 } else {
                     for (int e = 0; e < RB; ++e)
-                        if (c0 + e < txu) buf_st<F>(out[e], rq_, vo + e * ES, 0);
+                        if (c0 + e < g.txu) buf_st<F>(out[e], rq_, vo + e * (unsigned)sizeof(F), 0);
                 }
             }
         }
     };
-    for (int u0 = 0; u0 < nrows; u0 += NR) {
+    // the march: ring periods of NR rows unrolled (every ring slot index a compile-time constant),
+    // tiles of S rows alternating between the two buffers
+    for (int u0 = 0; u0 < g.nrows; u0 += NR) {
         bool done = false;
         [&]<int... H>(std::integer_sequence<int, H...>) {
             (
@@ -1002,41 +1104,21 @@ __global__ __launch_bounds__(512, OCC) void k_prod_wyx(const F* __restrict__ G, 
                     if (done) return;
                     constexpr int h0 = H * S;
                     F* tile = sw + (((u0 + h0) / S) & 1) * k34_tile(S, cwp);
-                    // two rows per step, their tap chains interleaved (ILP: a single chain issues
-                    // one fp64 op per dependent latency).  Row j+1's new product lands in row j's
-                    // outermost slot, so it is written after row j's first tap.
                     [&]<int... J>(std::integer_sequence<int, J...>) {
                         (
                             [&] {
                                 constexpr int j = h0 + 2 * J;  // step within the ring period
-                                constexpr int ic = j + 2 * RW + 1, ic1 = ic + 1;
-                                ring[ic % NR] = ra[ic % PD] * rb[ic % PD];
-                                const unsigned o = rowoff(u0 + ic + PD);
-                                ra[ic % PD] = buf_ld<F>(ra_, vof, o);
-                                rb[ic % PD] = buf_ld<F>(rb_, vof, o);
-                                F p1 = ra[ic1 % PD] * rb[ic1 % PD];
-                                const unsigned o1 = rowoff(u0 + ic1 + PD);
-                                ra[ic1 % PD] = buf_ld<F>(ra_, vof, o1);
-                                rb[ic1 % PD] = buf_ld<F>(rb_, vof, o1);
-                                F a0 = ring[(j + RW) % NR] * h[0];
-                                F a1 = ring[(j + 1 + RW) % NR] * h[0];
-                                a0 = a0 + (ring[j % NR] + ring[(j + 2 * RW) % NR]) * h[RW];
-                                a1 = a1 + (ring[(j + 1) % NR] + ring[(j + 1 + 2 * RW) % NR]) * h[RW];
-                                ring[ic1 % NR] = p1;  // slot of row j - RW (NR = 2 RW + 2): free now
-#pragma unroll
-                                for (int k = RW - 1; k >= 1; --k) {
-                                    a0 = a0 + (ring[(j + RW - k) % NR] + ring[(j + RW + k) % NR]) * h[k];
-                                    a1 = a1 + (ring[(j + 1 + RW - k) % NR] + ring[(j + 1 + RW + k) % NR]) * h[k];
-                                }
-                                put(tile + k34_row(j % S, cwp), a0);
-                                put(tile + k34_row((j + 1) % S, cwp), a1);
+                                F a0, a1;
+                                k34_ring_step<j, RW, false>(ring, ra, rb, ld, src, rows, u0, h, a0, a1);
+                                (tile + k34_row(j % S, cwp))[wpos] = a0;
+                                (tile + k34_row((j + 1) % S, cwp))[wpos] = a1;
                             }(),
                             ...);
                     }(std::make_integer_sequence<int, S / 2>{});
                     const int yb = u0 + h0;
-                    if constexpr (UQ) replicas(tile);
-                    phase_b(tile, y0 + yb, min(S, nrows - yb));
-                    if (yb + S >= nrows) done = true;
+                    if constexpr (UQ) k34_replicas<S>(tile, [&](int r) { return k34_row(r, cwp); }, lpad, rpad, ln, g);
+                    phase_b(tile, g.y0 + yb, min(S, g.nrows - yb));
+                    if (yb + S >= g.nrows) done = true;
                 }(),
                 ...);
         }(std::make_integer_sequence<int, NR / S>{});
@@ -1049,8 +1131,9 @@ __global__ __launch_bounds__(512, OCC) void k_prod_wyx(const F* __restrict__ G, 
 // tile — and waves 8..15 consumers — phase B (W x + stores) of the PREVIOUS tile, so the
 // producers' gradient loads and the consumers' LDS reads / stores overlap each other's
 // arithmetic instead of alternating in lockstep.  One barrier per tile, two tile buffers:
-// producers write tile t + 1 while consumers read tile t.  Same arithmetic and order as
-// k_prod_wyx (bit-identical).  128-VGPR budget (16 waves per CU): prefetch depth PD.
+// producers write tile t + 1 while consumers read tile t.  Phase-A step, edge replicas and item
+// decode are the parts k_prod_wyx uses (same arithmetic and order: bit-identical); the ring
+// prologue, the march loop and the tail store are this kernel's own copies.  128-VGPR budget (16 waves per CU): prefetch depth PD.
 // Ablation at c3 (round 2, timing-only experiment builds since removed): without the W-xy
 // stores 1.13 ms vs 1.72 — but that build had no phase-B arithmetic either (dead code without
 // its stores; checked in the device assembly in round 3), i.e. the producers alone; gradient
@@ -1059,10 +1142,7 @@ __global__ __launch_bounds__(512, OCC) void k_prod_wyx(const F* __restrict__ G, 
 // K5c itself, not its access pattern, is the cost.
 // (12-wave blocks — 4 consumer waves, 168 VGPRs, deeper prefetch, 8-row tiles — measured
 // slower: c3 1.95 vs 1.72 ms, c2 0.27 vs 0.19: the 16-wave occupancy hides more.)
-// The producers' two row chains side by side: without the two empty asm fences in phase A the
-// scheduler issued half of its ops right behind the op they depend on; with them 2 %.  Same ops,
-// same order per chain (bit-identical).  c3 K34 1.665 -> 1.631 ms, c4 equal
-// (profiles/r04/ab_k34ilp/).  The packed fp32 kernel spills with it and keeps its form.
+// The producers run the fenced phase-A step (k34_ring_step).
 // NPW: producer waves (staged columns 64 NPW), the other 16 - NPW consume.  8 + 8 suits a row
 // whose blocks stage 512 columns (c3: the whole 512-wide row, no halo); 9 + 7 lets a 1024-wide
 // row (c4) take two blocks of 512 outputs + 15 halo columns (527 staged) instead of three of 344
@@ -1073,78 +1153,50 @@ __global__ __launch_bounds__(1024) void k_prod_wyx_ws(const F* __restrict__ G, F
                                                       int nyb, int cpg, int ngroups, int yb0, int yb1, int zt) {
     constexpr int RB = 4, CWA = 64 * NPW, NCT = 1024 - CWA;  // producer threads; consumer threads
     constexpr int NR = k34_nr(RW, S);
-    constexpr unsigned ES = sizeof(F);
-    static_assert(NR % PD == 0 && NR % S == 0, "ring sizes");
+    static_assert(NR % S == 0, "ring sizes");
+    using It = K34Items<S>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     F* sw = reinterpret_cast<F*>(smem_raw);  // two W-y tiles [2][S][cwp]
     const int cwp = k34_pitch(min(tx, nx), RW);
     const int t = threadIdx.x;
     const K34Blk kbk = k34_block<NP>(nbx, nyb, cpg, ngroups);
     if (!kbk.ok) return;
-    const int bx = kbk.bx, p = kbk.p, zl = kbk.zl, yc = kbk.yc;
-    // output rows [yb0, yb1) (row-slab plans: the rank's own rows; loads still clamp at [0, ny))
-    const int y0 = yb0 + yc * nyc, nrows = min(nyc, yb1 - y0);
-    const int xo0 = bx * tx;
-    const int txu = min(tx, nx - xo0);
-    const int sxs = max(xo0 - RW, 0);
-    const int ns = min(xo0 + txu + RW, nx) - sxs;
-    const int padL = sxs - (xo0 - RW), padR = (xo0 + txu + RW) - (sxs + ns);
-    const int wa = (ns + 63) >> 6;
+    const K34Geo g = k34_geo<true>(kbk, tx, nyc, yb0, yb1, nx, RW);
+    const int wa = (g.ns + 63) >> 6;
     const bool prod = t < CWA;
     // producer waves with no staged column: every wave still takes one barrier per tile
     // (a wave-uniform test, so the whole wave takes this branch)
     if (prod && __builtin_amdgcn_readfirstlane(t >> 6) >= wa) {
-        for (int tt = 0; tt < (nrows + S - 1) / S; ++tt) lds_barrier();
+        for (int tt = 0; tt < (g.nrows + S - 1) / S; ++tt) lds_barrier();
         return;
     }
     F h[RW + 1];
 #pragma unroll
     for (int k = 0; k <= RW; ++k) h[k] = hw[k];
-    const size_t pl = (size_t)zl * ny * nx;
-    const unsigned rowb = (unsigned)nx * ES;
-    const int ntiles = (nrows + S - 1) / S;
+    const size_t pl = (size_t)g.zl * ny * nx;
+    const K34Rows<RW> rows{g.y0, ny, (unsigned)nx * (unsigned)sizeof(F)};
+    const int ntiles = (g.nrows + S - 1) / S;
     if (prod) {
-        const unsigned vof = (unsigned)clampi(sxs + t, 0, nx - 1) * ES;
+        const unsigned vof = (unsigned)clampi(g.sxs + t, 0, nx - 1) * (unsigned)sizeof(F);
         const int wv = __builtin_amdgcn_readfirstlane(t >> 6), ln = t & 63;
-        const bool lpad = padL > 0 && wv == 0;
-        const bool rpad = padR > 0 && wv == ((ns - 1) >> 6);
-        const int wpos = t < ns ? padL + t : padL + ns + padR;
-        auto replicas = [&](F* tile) {
-            if (lpad) {
-#pragma unroll
-                for (int r = 0; r < S; ++r) {
-                    F* row = tile + k34_row(r, cwp);
-                    const F e = row[padL];
-                    if (ln < padL) row[ln] = e;
-                }
-            }
-            if (rpad) {
-#pragma unroll
-                for (int r = 0; r < S; ++r) {
-                    F* row = tile + k34_row(r, cwp);
-                    const F e = row[padL + ns - 1];
-                    if (ln < padR) row[padL + ns + ln] = e;
-                }
-            }
-        };
-        constexpr unsigned long long pa = NP == 9 ? 0x311222312ull : 0x12212ull;
-        constexpr unsigned long long pb = NP == 9 ? 0x313231000ull : 0x12100ull;
-        const auto ra_ = buf_rsrc(G + (size_t)((pa >> (4 * p)) & 15u) * fs + pl);
-        const auto rb_ = buf_rsrc(G + (size_t)((pb >> (4 * p)) & 15u) * fs + pl);
-        auto rowoff = [&](int idx) { return (unsigned)clampi(y0 - RW + idx, 0, ny - 1) * rowb; };
+        const bool lpad = g.padL > 0 && wv == 0;
+        const bool rpad = g.padR > 0 && wv == ((g.ns - 1) >> 6);
+        const int wpos = t < g.ns ? g.padL + t : g.padL + g.ns + g.padR;
+        const K34Src src = k34_src<NP>(G, fs, pl, g.p);
+        auto ld = [&](const __amdgpu_buffer_rsrc_t& r, unsigned o) { return buf_ld<F>(r, vof, o); };
         F ring[NR], ra[PD], rb[PD];
 #pragma unroll
-        for (int i = 0; i <= 2 * RW; ++i) {
-            const unsigned o = rowoff(i);
-            ring[i] = buf_ld<F>(ra_, vof, o) * buf_ld<F>(rb_, vof, o);
+        for (int i = 0; i <= 2 * RW; ++i) {  // ring prologue and march as in k_prod_wyx
+            const unsigned o = rows.off(i);
+            ring[i] = ld(src.a, o) * ld(src.b, o);
         }
 #pragma unroll
         for (int i = 0; i < PD; ++i) {
-            const unsigned o = rowoff(2 * RW + 1 + i);
-            ra[(2 * RW + 1 + i) % PD] = buf_ld<F>(ra_, vof, o);
-            rb[(2 * RW + 1 + i) % PD] = buf_ld<F>(rb_, vof, o);
+            const unsigned o = rows.off(2 * RW + 1 + i);
+            ra[(2 * RW + 1 + i) % PD] = ld(src.a, o);
+            rb[(2 * RW + 1 + i) % PD] = ld(src.b, o);
         }
-        for (int u0 = 0; u0 < nrows; u0 += NR) {
+        for (int u0 = 0; u0 < g.nrows; u0 += NR) {
             bool done = false;
             [&]<int... H>(std::integer_sequence<int, H...>) {
                 (
@@ -1156,41 +1208,16 @@ __global__ __launch_bounds__(1024) void k_prod_wyx_ws(const F* __restrict__ G, F
                             (
                                 [&] {
                                     constexpr int j = h0 + 2 * J;
-                                    constexpr int ic = j + 2 * RW + 1, ic1 = ic + 1;
-                                    ring[ic % NR] = ra[ic % PD] * rb[ic % PD];
-                                    const unsigned o = rowoff(u0 + ic + PD);
-                                    ra[ic % PD] = buf_ld<F>(ra_, vof, o);
-                                    rb[ic % PD] = buf_ld<F>(rb_, vof, o);
-                                    F p1 = ra[ic1 % PD] * rb[ic1 % PD];
-                                    const unsigned o1 = rowoff(u0 + ic1 + PD);
-                                    ra[ic1 % PD] = buf_ld<F>(ra_, vof, o1);
-                                    rb[ic1 % PD] = buf_ld<F>(rb_, vof, o1);
-                                    F a0 = ring[(j + RW) % NR] * h[0];
-                                    F a1 = ring[(j + 1 + RW) % NR] * h[0];
-                                    a0 = a0 + (ring[j % NR] + ring[(j + 2 * RW) % NR]) * h[RW];
-                                    a1 = a1 + (ring[(j + 1) % NR] + ring[(j + 1 + 2 * RW) % NR]) * h[RW];
-                                    ring[ic1 % NR] = p1;
-#pragma unroll
-                                    for (int k = RW - 1; k >= 1; --k) {
-                                        // the two rows' chains side by side (the scheduler otherwise
-                                        // runs half the ops back to back on their predecessor)
-                                        F s0 = ring[(j + RW - k) % NR] + ring[(j + RW + k) % NR];
-                                        F s1 = ring[(j + 1 + RW - k) % NR] + ring[(j + 1 + RW + k) % NR];
-                                        asm volatile("" : "+v"(s0), "+v"(s1));
-                                        s0 = s0 * h[k];
-                                        s1 = s1 * h[k];
-                                        asm volatile("" : "+v"(s0), "+v"(s1));
-                                        a0 = a0 + s0;
-                                        a1 = a1 + s1;
-                                    }
+                                    F a0, a1;
+                                    k34_ring_step<j, RW, true>(ring, ra, rb, ld, src, rows, u0, h, a0, a1);
                                     tile[k34_row(j % S, cwp) + wpos] = a0;
                                     tile[k34_row((j + 1) % S, cwp) + wpos] = a1;
                                 }(),
                                 ...);
                         }(std::make_integer_sequence<int, S / 2>{});
-                        replicas(tile);
+                        k34_replicas<S>(tile, [&](int r) { return k34_row(r, cwp); }, lpad, rpad, ln, g);
                         lds_barrier();  // tile published; the consumers are done with the other buffer
-                        if (u0 + h0 + S >= nrows) done = true;
+                        if (u0 + h0 + S >= g.nrows) done = true;
                     }(),
                     ...);
             }(std::make_integer_sequence<int, NR / S>{});
@@ -1198,49 +1225,47 @@ __global__ __launch_bounds__(1024) void k_prod_wyx_ws(const F* __restrict__ G, F
         }
     } else {
         const int tb = t - CWA;
-        F* const Qp = Q + (size_t)p * fs;
+        F* const Qp = Q + (size_t)g.p * fs;
         const WxyMap wm = wxy_map<F>(nx, zt);
-        const int nseg = (txu + RB - 1) / RB;
-        constexpr int RPW = S < 8 ? S : 8, SPW = 64 / RPW;
-        constexpr int RG = S / RPW;
-        const int nsgw = (nseg + SPW - 1) / SPW;
+        const int nseg = (g.txu + RB - 1) / RB;
+        const int nsgw = (nseg + It::SPW - 1) / It::SPW;
         // 7 consumer waves (9 producers): a tile whose item groups are one more than whole rounds
         // of 7 (a 512-wide row at 4 or 8 rows: 8 groups) would make ONE wave run that group as a
         // second round (its SIMD then carries ~17 % more VALU work per tile than the others); that
         // group's 256 outputs go instead as single outputs to the first 4 consumer waves, one per
         // lane, which spreads them over 4 SIMDs (same arithmetic per output: bit-identical)
-        constexpr int NCW = NCT / 64, COLS = SPW * RB;
-        const int ngrp = RG * nsgw;
-        const bool spread = NPW != 8 && RG == 1 && ngrp % NCW == 1;
+        constexpr int NCW = NCT / 64, COLS = It::SPW * RB;
+        constexpr bool SOLO = k34_solo && sizeof(F) == 8;
+        const int ngrp = It::RG * nsgw;
+        const bool spread = NPW != 8 && It::RG == 1 && ngrp % NCW == 1;
         const int nmain = spread ? ngrp - 1 : ngrp;
         for (int tt = 0; tt < ntiles; ++tt) {
             lds_barrier();  // tile tt written
             const F* tile = sw + (tt & 1) * k34_tile(S, cwp);
-            const int yb = y0 + tt * S, nr = min(S, nrows - tt * S);
-            const auto rq_ = wxy_rsrc(Qp, zl, yb, ny, nx, zt);
-            if (spread && tb < RPW * COLS) {  // the leftover group: row tb / COLS, one column per lane
+            const int yb = g.y0 + tt * S, nr = min(S, g.nrows - tt * S);
+            const auto rq_ = wxy_rsrc(Qp, g.zl, yb, ny, nx, zt);
+            if (spread && tb < It::RPW * COLS) {  // the leftover group: row tb / COLS, one column per lane
                 const int r = tb / COLS, c0 = (ngrp - 1) * COLS + tb % COLS;
-                if (c0 < txu) {
+                if (c0 < g.txu) {
                     F o1[1];
-                    lds_pass_c<1, RW, DB, false, k34_solo && sizeof(F) == 8>(tile + k34_row(r, cwp), 1, RW + c0, h, o1);
-                    if (r < nr) buf_st<F>(o1[0], rq_, wxy_off<F>(wm, r, xo0 + c0), 0);
+                    lds_pass_c<1, RW, DB, false, SOLO>(tile + k34_row(r, cwp), 1, RW + c0, h, o1);
+                    if (r < nr) buf_st<F>(o1[0], rq_, wxy_off<F>(wm, r, g.xo0 + c0), 0);
                 }
             }
             for (int i = tb; i < 64 * nmain; i += NCT) {
-                const int l = i & 63, wg = i >> 6;
-                const int r = (wg % RG) * RPW + ((l >> 2) & 3) + (S >= 8 ? 4 * (l >> 5) : 0);
-                const int sg = (wg / RG) * SPW + (l & 3) + 4 * ((l >> 4) & 1) + (S >= 8 ? 0 : 8 * (l >> 5));
+                int r, sg;
+                It::at(i, r, sg);
                 if (sg >= nseg) continue;
                 F out[RB];
-                lds_pass_c<RB, RW, DB, false, k34_solo && sizeof(F) == 8>(tile + k34_row(r, cwp), 1, RW + RB * sg, h, out);
+                lds_pass_c<RB, RW, DB, false, SOLO>(tile + k34_row(r, cwp), 1, RW + RB * sg, h, out);
                 if (r < nr) {
                     const int c0 = RB * sg;
-                    const unsigned vo = wxy_off<F>(wm, r, xo0 + c0);
-                    if (c0 + RB <= txu) {
+                    const unsigned vo = wxy_off<F>(wm, r, g.xo0 + c0);
+                    if (c0 + RB <= g.txu) {
                         buf_st_n<F, RB>(out, rq_, vo, 0);
                     } else {
                         for (int e = 0; e < RB; ++e)
-                            if (c0 + e < txu) buf_st<F>(out[e], rq_, vo + e * ES, 0);
+                            if (c0 + e < g.txu) buf_st<F>(out[e], rq_, vo + e * (unsigned)sizeof(F), 0);
                     }
                 }
             }
@@ -1257,7 +1282,9 @@ __global__ __launch_bounds__(1024) void k_prod_wyx_ws(const F* __restrict__ G, F
 // {W-y(2p, x), W-y(2p + 1, x)} — so both phases read and write aligned float2: the
 // producer's two rows j, j + 1 of columns c, c + 1 are the pair row j / 2 at x = c, c + 1.
 // Pair pitch P2 = 1 (mod 32) float2: the consumers' 4 pairs x 4 segments of a 16-lane
-// group hit 32 distinct banks.  Ring, prefetch and tile double-buffering as k_prod_wyx_ws.
+// group hit 32 distinct banks.  Ring, prefetch and tile double-buffering as k_prod_wyx_ws:
+// k34_ring_step and k34_replicas on float2; the ring prologue, the march loop and the tail
+// store are this kernel's own copies.
 template <int NP, int RW, int S, int PD = 2, int DB = 2>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k_prod_wyx_pk(const float* __restrict__ G, float* __restrict__ Q, int ny,
                                                      int nx, size_t fs, const float* __restrict__ hw, int tx,
@@ -1266,7 +1293,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     typedef float f2 __attribute__((ext_vector_type(2)));
     constexpr int RB = 4, NPT = 256;  // outputs per consumer item; producer (= consumer) threads
     constexpr int NR = k34_nr(RW, S);
-    static_assert(NR % PD == 0 && NR % S == 0 && S % 2 == 0 && (S == 8 || S == 4), "ring sizes");
+    static_assert(NR % PD == 0 && NR % S == 0 && (S == 8 || S == 4), "ring sizes, whole row pairs");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     f2* sw = reinterpret_cast<f2*>(smem_raw);  // two tiles [2][S / 2][P2]
     const int P2 = k34_pitch(min(tx, nx), RW);
@@ -1274,60 +1301,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int t = threadIdx.x;
     const K34Blk kbk = k34_block<NP>(nbx, nyb, cpg, ngroups);
     if (!kbk.ok) return;
-    const int bx = kbk.bx, p = kbk.p, zl = kbk.zl, yc = kbk.yc;
-    const int y0 = yb0 + yc * nyc, nrows = min(nyc, yb1 - y0);
-    const int xo0 = bx * tx;
-    const int txu = min(tx, nx - xo0);
-    const int sxs = max(xo0 - RW, 0);
-    const int ns = min(xo0 + txu + RW, nx) - sxs;
-    const int padL = sxs - (xo0 - RW), padR = (xo0 + txu + RW) - (sxs + ns);
-    const int npair = (ns + 1) >> 1;  // column pairs staged
+    const K34Geo g = k34_geo<true>(kbk, tx, nyc, yb0, yb1, nx, RW);
+    const int npair = (g.ns + 1) >> 1;  // column pairs staged
     const int wa = (npair + 63) >> 6;
     const bool prod = t < NPT;
     // producer waves with no staged column pair: every wave still takes one barrier per tile
     // (a wave-uniform test, so the whole wave takes this branch)
     if (prod && __builtin_amdgcn_readfirstlane(t >> 6) >= wa) {
-        for (int tt = 0; tt < (nrows + S - 1) / S; ++tt) lds_barrier();
+        for (int tt = 0; tt < (g.nrows + S - 1) / S; ++tt) lds_barrier();
         return;
     }
     f2 h[RW + 1];
 #pragma unroll
     for (int k = 0; k <= RW; ++k) h[k] = (f2){hw[k], hw[k]};
-    const size_t pl = (size_t)zl * ny * nx;
-    const unsigned rowb = (unsigned)nx * 4u;
-    const int ntiles = (nrows + S - 1) / S;
+    const size_t pl = (size_t)g.zl * ny * nx;
+    const K34Rows<RW> rows{g.y0, ny, (unsigned)nx * 4u};
+    const int ntiles = (g.nrows + S - 1) / S;
     if (prod) {
         const int wv = __builtin_amdgcn_readfirstlane(t >> 6), ln = t & 63;
-        const bool lpad = padL > 0 && wv == 0;
-        const bool rpad = padR > 0 && wv == ((npair - 1) >> 6);
-        const int wpos = padL + 2 * t;  // tile column of this thread's first staged column
-        auto replicas = [&](f2* tile) {
-            if (lpad) {
-#pragma unroll
-                for (int q = 0; q < S / 2; ++q) {
-                    f2* row = tile + q * P2;
-                    const f2 e = row[padL];
-                    if (ln < padL) row[ln] = e;
-                }
-            }
-            if (rpad) {
-#pragma unroll
-                for (int q = 0; q < S / 2; ++q) {
-                    f2* row = tile + q * P2;
-                    const f2 e = row[padL + ns - 1];
-                    if (ln < padR) row[padL + ns + ln] = e;
-                }
-            }
-        };
-        constexpr unsigned long long pa = NP == 9 ? 0x311222312ull : 0x12212ull;
-        constexpr unsigned long long pb = NP == 9 ? 0x313231000ull : 0x12100ull;
-        const auto ra_ = buf_rsrc(G + (size_t)((pa >> (4 * p)) & 15u) * fs + pl);
-        const auto rb_ = buf_rsrc(G + (size_t)((pb >> (4 * p)) & 15u) * fs + pl);
-        auto rowoff = [&](int idx) { return (unsigned)clampi(y0 - RW + idx, 0, ny - 1) * rowb; };
+        const bool lpad = g.padL > 0 && wv == 0;
+        const bool rpad = g.padR > 0 && wv == ((npair - 1) >> 6);
+        const int wpos = g.padL + 2 * t;  // tile column of this thread's first staged column
+        const K34Src src = k34_src<NP>(G, fs, pl, g.p);
         // the column pair as ONE 8-byte load (dword-aligned buffer load): columns c, c + 1 when
         // both are inside the row, else the row's last two with the last one duplicated (the
         // clamped pair of the scalar form)
-        const int cp = sxs + 2 * t;
+        const int cp = g.sxs + 2 * t;
         const bool dup = cp > nx - 2;
         const unsigned vp = (unsigned)(dup ? nx - 2 : cp) * 4u;
         auto ld2 = [&](const __amdgpu_buffer_rsrc_t& r, unsigned o) {
@@ -1337,17 +1336,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
         };
         f2 ring[NR], ra[PD], rb[PD];
 #pragma unroll
-        for (int i = 0; i <= 2 * RW; ++i) {
-            const unsigned o = rowoff(i);
-            ring[i] = ld2(ra_, o) * ld2(rb_, o);
+        for (int i = 0; i <= 2 * RW; ++i) {  // ring prologue and march as in k_prod_wyx
+            const unsigned o = rows.off(i);
+            ring[i] = ld2(src.a, o) * ld2(src.b, o);
         }
 #pragma unroll
         for (int i = 0; i < PD; ++i) {
-            const unsigned o = rowoff(2 * RW + 1 + i);
-            ra[(2 * RW + 1 + i) % PD] = ld2(ra_, o);
-            rb[(2 * RW + 1 + i) % PD] = ld2(rb_, o);
+            const unsigned o = rows.off(2 * RW + 1 + i);
+            ra[(2 * RW + 1 + i) % PD] = ld2(src.a, o);
+            rb[(2 * RW + 1 + i) % PD] = ld2(src.b, o);
         }
-        for (int u0 = 0; u0 < nrows; u0 += NR) {
+        for (int u0 = 0; u0 < g.nrows; u0 += NR) {
             bool done = false;
             [&]<int... H>(std::integer_sequence<int, H...>) {
                 (
@@ -1359,25 +1358,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
                             (
                                 [&] {
                                     constexpr int j = h0 + 2 * J;
-                                    constexpr int ic = j + 2 * RW + 1, ic1 = ic + 1;
-                                    ring[ic % NR] = ra[ic % PD] * rb[ic % PD];
-                                    const unsigned o = rowoff(u0 + ic + PD);
-                                    ra[ic % PD] = ld2(ra_, o);
-                                    rb[ic % PD] = ld2(rb_, o);
-                                    f2 p1 = ra[ic1 % PD] * rb[ic1 % PD];
-                                    const unsigned o1 = rowoff(u0 + ic1 + PD);
-                                    ra[ic1 % PD] = ld2(ra_, o1);
-                                    rb[ic1 % PD] = ld2(rb_, o1);
-                                    f2 a0 = ring[(j + RW) % NR] * h[0];
-                                    f2 a1 = ring[(j + 1 + RW) % NR] * h[0];
-                                    a0 = a0 + (ring[j % NR] + ring[(j + 2 * RW) % NR]) * h[RW];
-                                    a1 = a1 + (ring[(j + 1) % NR] + ring[(j + 1 + 2 * RW) % NR]) * h[RW];
-                                    ring[ic1 % NR] = p1;
-#pragma unroll
-                                    for (int k = RW - 1; k >= 1; --k) {
-                                        a0 = a0 + (ring[(j + RW - k) % NR] + ring[(j + RW + k) % NR]) * h[k];
-                                        a1 = a1 + (ring[(j + 1 + RW - k) % NR] + ring[(j + 1 + RW + k) % NR]) * h[k];
-                                    }
+                                    f2 a0, a1;
+                                    k34_ring_step<j, RW, false>(ring, ra, rb, ld2, src, rows, u0, h, a0, a1);
                                     // rows j, j + 1 (pair (j % S) / 2) at columns wpos, wpos + 1
                                     // (threads past the staged pairs write nothing: wpos would
                                     // run into the next pair row)
@@ -1389,9 +1371,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
                                 }(),
                                 ...);
                         }(std::make_integer_sequence<int, S / 2>{});
-                        replicas(tile);
+                        k34_replicas<S / 2>(tile, [&](int q) { return q * P2; }, lpad, rpad, ln, g);
                         lds_barrier();  // tile published; the consumers are done with the other buffer
-                        if (u0 + h0 + S >= nrows) done = true;
+                        if (u0 + h0 + S >= g.nrows) done = true;
                     }(),
                     ...);
             }(std::make_integer_sequence<int, NR / S>{});
@@ -1399,16 +1381,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
         }
     } else {
         const int tb = t - NPT;
-        float* const Qp = Q + (size_t)p * fs;
+        float* const Qp = Q + (size_t)g.p * fs;
         const WxyMap wm = wxy_map<float>(nx, zt);
-        const int nseg = (txu + RB - 1) / RB;
+        const int nseg = (g.txu + RB - 1) / RB;
         constexpr int PP = S / 2, SPW = 64 / PP;  // pairs per tile; segments per wave item
         const int nsgw = (nseg + SPW - 1) / SPW;
         for (int tt = 0; tt < ntiles; ++tt) {
             lds_barrier();  // tile tt written
             const f2* tile = sw + (tt & 1) * TB;
-            const int yb = y0 + tt * S, nr = min(S, nrows - tt * S);
-            const auto rq_ = wxy_rsrc(Qp, zl, yb, ny, nx, zt);
+            const int yb = g.y0 + tt * S, nr = min(S, g.nrows - tt * S);
+            const auto rq_ = wxy_rsrc(Qp, g.zl, yb, ny, nx, zt);
             for (int i = tb; i < 64 * nsgw; i += NPT) {
                 const int l = i & 63, wg = i >> 6;
                 const int pr = l % PP, sg = wg * SPW + l / PP;
@@ -1423,12 +1405,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
                         float o[RB];
 #pragma unroll
                         for (int e = 0; e < RB; ++e) o[e] = e2 ? out[e].y : out[e].x;
-                        const unsigned vo = wxy_off<float>(wm, r, xo0 + c0);
-                        if (c0 + RB <= txu) {
+                        const unsigned vo = wxy_off<float>(wm, r, g.xo0 + c0);
+                        if (c0 + RB <= g.txu) {
                             buf_st_n<float, RB>(o, rq_, vo, 0);
                         } else {
                             for (int e = 0; e < RB; ++e)
-                                if (c0 + e < txu) buf_st<float>(o[e], rq_, vo + e * 4u, 0);
+                                if (c0 + e < g.txu) buf_st<float>(o[e], rq_, vo + e * 4u, 0);
                         }
                     }
                 }

@@ -255,22 +255,10 @@ DevTaps<F> dev_taps(const of3d_plan* p) {
 
 unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
-
-
-
-
 int k0_vec_width(int dtype) {
     const size_t es = dtype_size(dtype);
     return es == 1 ? 8 : (es == 8 ? 2 : 4);
 }
-
-
-
-
-
-
-
-
 
 // K34 geometry.  Two kernel families:
 //  - duplicate staging (k_prod_wyx UQ = false, 168 VGPRs): blocks of nw in {1, 2, 3, 4} waves,
@@ -307,6 +295,10 @@ int k34_setup(of3d_plan* p, int np) {
     long best_lanes = 0;
     int best_waves = 0;
     const int uq = kn.k34_uq;  // 0: duplicate staging only, 1: unique only (2: specialised, 3: packed fp32 only)
+    // a getter's instance for this plan's product count (nine products in 3D, five in 2D)
+    auto by_np = [&](auto get9, auto get5, auto... a) -> const void* { return np == 9 ? get9(a...) : get5(a...); };
+    // tile pitch of the unique-staging forms at column stride tx
+    auto pitch = [&](int tx) { return k34_pitch(std::min(tx, nx), rw); };
     auto occupancy = [&](const void* fn, int cw, size_t lds, int& waves) -> int {
         OF3D_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int nb = 0;
@@ -334,24 +326,24 @@ int k34_setup(of3d_plan* p, int np) {
         // blocks would need more than 512 staged columns (nx 1024: 2 x (512 + 15) instead of 3 x 344)
         for (int pd : {2, 4}) {
             const void* f9 = (uq != 0 && uq != 1 && uq != 3 && kn.k34_ws)
-                                 ? (np == 9 ? k34_fn_ws<F, 9>(rw, s, 9, pd) : k34_fn_ws<F, 5>(rw, s, 9, pd)) : nullptr;
+                                 ? by_np(k34_fn_ws<F, 9>, k34_fn_ws<F, 5>, rw, s, 9, pd) : nullptr;
             const int tx = f9 ? uq_stride(576) : 0, tx8 = uq_stride(512);
             if (tx && (!tx8 || (nx + tx - 1) / tx < (nx + tx8 - 1) / tx8)) {  // only where it saves blocks
-                const size_t lds = (size_t)2 * k34_tile(s, k34_pitch(std::min(tx, nx), rw)) * es;
+                const size_t lds = k34_lds(s, pitch(tx), es);
                 int w9 = 0;
                 if (lds <= 160 * 1024 && !occupancy(f9, 1024, lds, w9) && w9 >= 16)
                     p->k34_cand.push_back({f9, 576, s, tx, (nx + tx - 1) / tx, lds, 1024});
             }
         }
-        const void* fd = uq == 1 ? nullptr : (np == 9 ? k34_fn<F, 9>(rw, s, 4) : k34_fn<F, 5>(rw, s, 4));
-        const void* fu = uq == 0 ? nullptr : (np == 9 ? k34_fn_uq<F, 9>(rw, s) : k34_fn_uq<F, 5>(rw, s));
+        const void* fd = uq == 1 ? nullptr : by_np(k34_fn<F, 9>, k34_fn<F, 5>, rw, s, 4);
+        const void* fu = uq == 0 ? nullptr : by_np(k34_fn_uq<F, 9>, k34_fn_uq<F, 5>, rw, s);
         for (int nw : {1, 2, 3, 4, 8}) {  // launch bound 512
             const int cw = 64 * nw;
             if (fd && nw <= 4) {  // duplicate staging
                 const int tx = (cw - 2 * rw) & ~3;  // whole phase-B items
                 if (tx >= 8) {
                     const int nbx = (nx + tx - 1) / tx;
-                    const size_t lds = (size_t)2 * k34_tile(s, cw + 1) * es;  // two W-y tiles
+                    const size_t lds = k34_lds(s, cw + 1, es);
                     int waves = 0;
                     if (lds <= 160 * 1024 && !occupancy(fd, cw, lds, waves) && waves > 0) {
                         const long lanes = (long)(nbx - 1) * cw + 64 * ((nx - (nbx - 1) * tx + 2 * rw + 63) / 64);
@@ -373,27 +365,23 @@ int k34_setup(of3d_plan* p, int np) {
                 const int tx = uq_stride(cw);
                 if (tx) {
                     const int nbx = (nx + tx - 1) / tx;
-                    const size_t lds = (size_t)2 * k34_tile(s, k34_pitch(std::min(tx, nx), rw)) * es;
+                    const size_t lds = k34_lds(s, pitch(tx), es);
                     int waves = 0;
                     if (lds <= 160 * 1024 && !occupancy(fu, cw, lds, waves) && waves >= nw)
                         p->k34_cand.push_back({fu, cw, s, tx, nbx, lds});
                     // the wave-specialised form of the same geometry (8 producer + 8 consumer waves)
-                    const void* fw =
-                (nw == 8 && kn.k34_ws) ? (np == 9 ? k34_fn_ws<F, 9>(rw, s, 8, 2) : k34_fn_ws<F, 5>(rw, s, 8, 2)) : nullptr;
+                    const void* fw = (nw == 8 && kn.k34_ws) ? by_np(k34_fn_ws<F, 9>, k34_fn_ws<F, 5>, rw, s, 8, 2) : nullptr;
                     int wsw = 0;
                     if (fw && lds <= 160 * 1024 && !occupancy(fw, 2 * cw, lds, wsw) && wsw >= 2 * nw)
                         p->k34_cand.push_back({fw, cw, s, tx, nbx, lds, 2 * cw});
                     // ... with 4 rows of gradient prefetch (fp64 radii <= 15, 4-row tiles)
-                    const void* fw4 = (nw == 8 && kn.k34_ws)
-                                          ? (np == 9 ? k34_fn_ws<F, 9>(rw, s, 8, 4) : k34_fn_ws<F, 5>(rw, s, 8, 4))
-                                          : nullptr;
+                    const void* fw4 = (nw == 8 && kn.k34_ws) ? by_np(k34_fn_ws<F, 9>, k34_fn_ws<F, 5>, rw, s, 8, 4) : nullptr;
                     if (fw4 && lds <= 160 * 1024 && !occupancy(fw4, 2 * cw, lds, wsw) && wsw >= 2 * nw)
                         p->k34_cand.push_back({fw4, cw, s, tx, nbx, lds, 2 * cw});
                     // fp32: the packed form (column pairs / row pairs on float2, 8-wave blocks)
                     if constexpr (sizeof(F) == 4) {
-                        const void* fp =
-                            (nw == 8 && kn.k34_pk) ? (np == 9 ? k34_fn_pk<9>(rw, s) : k34_fn_pk<5>(rw, s)) : nullptr;
-                        const size_t lpk = (size_t)s * k34_pitch(std::min(tx, nx), rw) * 8;
+                        const void* fp = (nw == 8 && kn.k34_pk) ? by_np(k34_fn_pk<9>, k34_fn_pk<5>, rw, s) : nullptr;
+                        const size_t lpk = k34_lds(s, pitch(tx), es, true);
                         int pkw = 0;
                         if (fp && lpk <= 160 * 1024 && !occupancy(fp, cw, lpk, pkw) && pkw >= nw)
                             p->k34_cand.push_back({fp, cw, s, tx, nbx, lpk, cw});
