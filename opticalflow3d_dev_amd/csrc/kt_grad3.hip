@@ -26,12 +26,14 @@ const void* k12_fn(int dtype, int rd, int rs, bool deep) {
 #undef OF3D_K12
 }
 
-// dynamic LDS bytes of the K12 instance for (dtype, rd) (0: none)
+// dynamic LDS bytes of the instance k12_fn returns for (dtype, rd, deep) (0: none): the deep size
+// only where k12_fn has a deep instance
 template <typename F>
 size_t k12_lds(int dtype, int rd, bool deep) {
 #define OF3D_K12L(T)                                                  \
     if (rd == 3) return (size_t)k12_lds_bytes<T, F, 3>();             \
-    if (rd == 6 && deep) return (size_t)k12_lds_bytes<T, F, 6, true>(); \
+    if constexpr (sizeof(F) == 8)                                     \
+        if (rd == 6 && deep) return (size_t)k12_lds_bytes<T, F, 6, true>(); \
     if (rd == 6) return (size_t)k12_lds_bytes<T, F, 6>();             \
     if (rd == 9) return (size_t)k12_lds_bytes<T, F, 9>();             \
     return 0;

@@ -11,7 +11,7 @@ using namespace of3dk;
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-size_t dtype_size(int dt) {
+constexpr size_t dtype_size(int dt) {
     switch (dt) {
         case OF3D_U8: return 1;
         case OF3D_U16:
@@ -37,6 +37,37 @@ int symmetry(const double* w, int r) {
 const char* kStageNames[] = {"grad_xy", "grad_z", "prod_wy", "wx", "wz_solve"};
 constexpr int kStages = 5;
 constexpr int kMaxChunks = 16;  // overlap mode: most z chunks per execution
+constexpr size_t kLdsMax = 160 * 1024;  // LDS bytes a workgroup can have
+
+// The window a pre-formed dt0 belongs to: the frames it was formed from (by address), their
+// dtype and plane origin, and the output planes of the call it is for.
+struct Dt0Tag {
+    bool valid = false;
+    const void* frames[kMaxT] = {};
+    int dtype = 0;
+    int64_t fz0 = 0, zo0 = 0, zo1 = 0;
+    bool matches(const void* const* d_frames, int nwin, int dt, int64_t f0, int64_t o0, int64_t o1) const {
+        bool hit = valid && dtype == dt && fz0 == f0 && zo0 == o0 && zo1 == o1;
+        for (int i = 0; hit && i < nwin; ++i) hit = frames[i] == d_frames[i];
+        return hit;
+    }
+    void set(const void* const* d_frames, int nwin, int dt, int64_t f0, int64_t o0, int64_t o1) {
+        valid = true;
+        for (int i = 0; i < nwin; ++i) frames[i] = d_frames[i];
+        dtype = dt, fz0 = f0, zo0 = o0, zo1 = o1;
+    }
+};
+
+// LDS bytes of the runtime-radius tiles (K1 .. K5) for element size e
+struct RrLds {
+    size_t k1 = 0, k2 = 0, k3 = 0, k4 = 0, k5 = 0;
+};
+RrLds rr_lds(int rd, int rs, int rw, size_t e) {
+    return {(size_t)(2 * (K1_TY + 2 * rd) + 3 * K1_TY) * 64 * e, (size_t)(K2_ZC + 2 * std::max(rd, rs)) * 64 * e,
+            (size_t)(K3_STEP + 2 * rw) * 64 * e,
+            (size_t)K4_ROWS * (((K4_TX + 2 * k4_halo(rw)) | 1) + (K4_TX + 1)) * e,
+            (size_t)2 * (k5_geom(rw).g * k5_geom(rw).r + 2 * rw) * 64 * e};
+}
 
 }  // namespace
 
@@ -130,8 +161,8 @@ struct of3d_plan {
     void* Y = nullptr;          // 9 fields
     size_t fs = 0;        // field stride (elements)
     hipStream_t stream = nullptr;
-    size_t k1_lds = 0, k2_lds = 0, k3_lds = 0, k4_lds = 0, k5_lds = 0;
-    int k5_nb = 0;       // LDS-DMA K5 buffers (0: register-staged K5)
+    RrLds lds;           // runtime-radius tiles (set_attrs_t)
+    int k5_nb = 0;      // LDS-DMA K5 buffers (0: register-staged K5)
     size_t k5d_lds = 0;
     bool general = false;  // radii beyond the tiled kernels' limits: the general-radius path
     // K5c (compile-time-radius W z + solve); nullptr: k_wz_solve_dma / k_wz_solve
@@ -143,21 +174,13 @@ struct of3d_plan {
     // [y][x / 32][z][32] with this many planes (cap_planes)
     int wxy_zt = 0;
     // frame pipelining (of3d_plan_execute_next): the dt0 a previous call formed for these frames
-    bool pipe_valid = false;
-    const void* pipe_frames[kMaxT] = {};
-    int64_t pipe_fz0 = 0, pipe_zo0 = 0, pipe_zo1 = 0;
-    int pipe_dtype = 0;
+    Dt0Tag pipe;
     bool pipe_k12 = false;  // the producing call's flow (dt0 in Y4 with K12, else Y0)
     // K0 batching (of3d_plan_execute_ahead): dt0 slots Y4 .. Y4 + kDtSlots - 1 (K12 flow, whose
     // workspace leaves Y4..Y8 free), each tagged with the window it was formed for; the call
     // that uses a slot consumes it, and any other call drops them all
     static constexpr int kDtSlots = 5;  // Y4 .. Y8
-    struct DtSlot {
-        bool valid = false;
-        const void* frames[kMaxT] = {};
-        int dtype = 0;
-        int64_t fz0 = 0, zo0 = 0, zo1 = 0;
-    } dts[kDtSlots];
+    Dt0Tag dts[kDtSlots];
     int k5c_nw = 4;       // K5c waves per block (8: 128-plane blocks)
     int64_t ya = 0, yb = 0;  // output rows [ya, yb) (of3d_plan_set_rows; default all)
     unsigned used = 0;       // kernel families launched so far (KU_* bits, of3d_plan_kernels)
@@ -255,9 +278,37 @@ DevTaps<F> dev_taps(const of3d_plan* p) {
 
 unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
-int k0_vec_width(int dtype) {
+// blocks of a 256-thread grid-stride kernel over n elements, at most cap
+unsigned grid1d(size_t n, size_t cap) { return (unsigned)std::min<size_t>((n + 255) / 256, cap); }
+
+size_t elem_size(const of3d_plan* p) { return p->fp32 ? sizeof(float) : sizeof(double); }
+
+int bad_out_range(const of3d_plan* p, int64_t zo0, int64_t zo1) {
+    return (zo0 < 0 || zo1 > p->nz || zo0 >= zo1) ? fail("of3d: bad output plane range") : 0;
+}
+
+constexpr int k0_vec_width(int dtype) {
     const size_t es = dtype_size(dtype);
     return es == 1 ? 8 : (es == 8 ? 2 : 4);
+}
+static_assert(K0Vec<uint16_t>::V == k0_vec_width(OF3D_U16), "K5c's next-frame K0 groups as the vectorised K0 does");
+
+// Whether `count` frames can take the vectorised K0 layout over n elements from element off0 on:
+// whole groups of V = k0_vec_width voxels, every frame pointer V elements aligned
+bool k0_vec_ok(const void* const* frames, int count, int dtype, size_t off0, size_t n) {
+    const size_t V = k0_vec_width(dtype), vb = V * dtype_size(dtype);
+    bool ok = off0 % V == 0 && n % V == 0;
+    for (int i = 0; ok && i < count; ++i) ok = frames[i] && (uintptr_t)frames[i] % vb == 0;
+    return ok;
+}
+
+// The scalar K0 (any rt, any alignment): dt0 of n elements from element off0 of every frame on;
+// fstride: the frames' common element stride where they are equally spaced (0: the pointer table)
+template <typename F>
+hipError_t launch_k0(const Frames& fr, int dtype, long long fstride, size_t off0, size_t n, int rt, const F* ht, F* D0,
+                     hipStream_t st) {
+    void* args[] = {(void*)&fr, (void*)&fstride, (void*)&off0, (void*)&n, (void*)&rt, (void*)&ht, (void*)&D0};
+    return hipLaunchKernel(k0_kernel_dt<F>(dtype), dim3(grid1d(n, 256 * 16)), dim3(256), args, 0, st);
 }
 
 // K34 geometry.  Two kernel families:
@@ -331,7 +382,7 @@ int k34_setup(of3d_plan* p, int np) {
             if (tx && (!tx8 || (nx + tx - 1) / tx < (nx + tx8 - 1) / tx8)) {  // only where it saves blocks
                 const size_t lds = k34_lds(s, pitch(tx), es);
                 int w9 = 0;
-                if (lds <= 160 * 1024 && !occupancy(f9, 1024, lds, w9) && w9 >= 16)
+                if (lds <= kLdsMax && !occupancy(f9, 1024, lds, w9) && w9 >= 16)
                     p->k34_cand.push_back({f9, 576, s, tx, (nx + tx - 1) / tx, lds, 1024});
             }
         }
@@ -345,7 +396,7 @@ int k34_setup(of3d_plan* p, int np) {
                     const int nbx = (nx + tx - 1) / tx;
                     const size_t lds = k34_lds(s, cw + 1, es);
                     int waves = 0;
-                    if (lds <= 160 * 1024 && !occupancy(fd, cw, lds, waves) && waves > 0) {
+                    if (lds <= kLdsMax && !occupancy(fd, cw, lds, waves) && waves > 0) {
                         const long lanes = (long)(nbx - 1) * cw + 64 * ((nx - (nbx - 1) * tx + 2 * rw + 63) / 64);
                         const bool ok = waves >= 8, best_ok = best_waves >= 8;
                         if (ok) p->k34_cand.push_back({fd, cw, s, tx, nbx, lds});
@@ -367,23 +418,23 @@ int k34_setup(of3d_plan* p, int np) {
                     const int nbx = (nx + tx - 1) / tx;
                     const size_t lds = k34_lds(s, pitch(tx), es);
                     int waves = 0;
-                    if (lds <= 160 * 1024 && !occupancy(fu, cw, lds, waves) && waves >= nw)
+                    if (lds <= kLdsMax && !occupancy(fu, cw, lds, waves) && waves >= nw)
                         p->k34_cand.push_back({fu, cw, s, tx, nbx, lds});
                     // the wave-specialised form of the same geometry (8 producer + 8 consumer waves)
                     const void* fw = (nw == 8 && kn.k34_ws) ? by_np(k34_fn_ws<F, 9>, k34_fn_ws<F, 5>, rw, s, 8, 2) : nullptr;
                     int wsw = 0;
-                    if (fw && lds <= 160 * 1024 && !occupancy(fw, 2 * cw, lds, wsw) && wsw >= 2 * nw)
+                    if (fw && lds <= kLdsMax && !occupancy(fw, 2 * cw, lds, wsw) && wsw >= 2 * nw)
                         p->k34_cand.push_back({fw, cw, s, tx, nbx, lds, 2 * cw});
                     // ... with 4 rows of gradient prefetch (fp64 radii <= 15, 4-row tiles)
                     const void* fw4 = (nw == 8 && kn.k34_ws) ? by_np(k34_fn_ws<F, 9>, k34_fn_ws<F, 5>, rw, s, 8, 4) : nullptr;
-                    if (fw4 && lds <= 160 * 1024 && !occupancy(fw4, 2 * cw, lds, wsw) && wsw >= 2 * nw)
+                    if (fw4 && lds <= kLdsMax && !occupancy(fw4, 2 * cw, lds, wsw) && wsw >= 2 * nw)
                         p->k34_cand.push_back({fw4, cw, s, tx, nbx, lds, 2 * cw});
                     // fp32: the packed form (column pairs / row pairs on float2, 8-wave blocks)
                     if constexpr (sizeof(F) == 4) {
                         const void* fp = (nw == 8 && kn.k34_pk) ? by_np(k34_fn_pk<9>, k34_fn_pk<5>, rw, s) : nullptr;
                         const size_t lpk = k34_lds(s, pitch(tx), es, true);
                         int pkw = 0;
-                        if (fp && lpk <= 160 * 1024 && !occupancy(fp, cw, lpk, pkw) && pkw >= nw)
+                        if (fp && lpk <= kLdsMax && !occupancy(fp, cw, lpk, pkw) && pkw >= nw)
                             p->k34_cand.push_back({fp, cw, s, tx, nbx, lpk, cw});
                     }
                 }
@@ -399,9 +450,9 @@ int k34_setup(of3d_plan* p, int np) {
     }
     if (!p->k34.fn && !p->k34_cand.empty()) p->k34 = p->k34_cand.front();
     for (const auto& k : p->k34_cand)
-        OF3D_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        OF3D_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     if (p->k34.fn)
-        OF3D_HIP(hipFuncSetAttribute(p->k34.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        OF3D_HIP(hipFuncSetAttribute(p->k34.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     if (kn.verbose && p->k34.fn)
         fprintf(stderr, "of3d: K34 cw=%d s=%d tx=%d nbx=%d lds=%zu lanes=%ld waves/CU=%d\n", p->k34.cw, p->k34.s,
                 p->k34.tx, p->k34.nbx, p->k34.lds, best_lanes, best_waves);
@@ -433,13 +484,17 @@ int k5c_setup(of3d_plan* p) {
     int nw = p->kn.k5c_nw;
     if (nw == 8) r = 8;  // the 8-wave instances are R 8 only (k5c_fn): grid and LDS follow r
     size_t buf = (size_t)k5c_groups<F>(p->rw, r, nw) * 1024;
-    int nb = nw == 8 ? (3 * buf <= 160 * 1024 ? 3 : 0) : (2 * 3 * buf <= 160 * 1024 ? 3 : 2);  // 4 waves: two blocks per CU
-    const void* fn = nb ? (p->rel64 ? k5c_fn<F, double>(p->rw, nb, r, nw) : k5c_fn<F, float>(p->rw, nb, r, nw)) : nullptr;
+    int nb = nw == 8 ? (3 * buf <= kLdsMax ? 3 : 0) : (2 * 3 * buf <= kLdsMax ? 3 : 2);  // 4 waves: two blocks per CU
+    // the instance for the plan's rel type (rt0 > 0: with the next frame's K0)
+    auto pick = [&](int rt0) {
+        return p->rel64 ? k5c_fn<F, double>(p->rw, nb, r, nw, rt0) : k5c_fn<F, float>(p->rw, nb, r, nw, rt0);
+    };
+    const void* fn = nb ? pick(0) : nullptr;
     if (!fn && nw == 8) {  // no 8-wave instance: the 4-wave one
         nw = 4;
         buf = (size_t)k5c_groups<F>(p->rw, r, nw) * 1024;
-        nb = 2 * 3 * buf <= 160 * 1024 ? 3 : 2;
-        fn = p->rel64 ? k5c_fn<F, double>(p->rw, nb, r, nw) : k5c_fn<F, float>(p->rw, nb, r, nw);
+        nb = 2 * 3 * buf <= kLdsMax ? 3 : 2;
+        fn = pick(0);
     }
     if (!fn) return 0;
     p->k5c_nw = nw;
@@ -448,9 +503,8 @@ int k5c_setup(of3d_plan* p) {
     OF3D_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->k5c_lds));
     p->k5c = fn;
     // the same geometry with the next frame's K0 after the solve (uint16 frames; OF3D_PIPE=0: off)
-    p->k5c_next = nullptr;
     if (p->kn.pipe) {
-        const void* fx = p->rel64 ? k5c_fn<F, double>(p->rw, nb, r, nw, p->rt) : k5c_fn<F, float>(p->rw, nb, r, nw, p->rt);
+        const void* fx = pick(p->rt);
         if (fx) {
             OF3D_HIP(hipFuncSetAttribute(fx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->k5c_lds));
             p->k5c_next = fx;
@@ -534,8 +588,10 @@ int k34_tune(of3d_plan* p) {
     const size_t nfill = (size_t)(p->ndim == 3 ? 4 : 3) * p->fs;
     hipLaunchKernelGGL(k_fill_tune<F>, dim3(2048), dim3(256), 0, p->stream, G, nfill);
     OF3D_HIP(hipGetLastError());
-    for (size_t i = 0; i < nc; ++i)  // warm every candidate (code load, caches)
-        OF3D_HIP(launch_k34(p->k34_cand[i], (const F*)G, P, ng, nf, (int)p->ny, (int)p->nx, p->fs, hw, p->stream, p->wxy_zt));
+    auto launch = [&](size_t i) {  // candidate i over the whole workspace
+        return launch_k34(p->k34_cand[i], (const F*)G, P, ng, nf, (int)p->ny, (int)p->nx, p->fs, hw, p->stream, p->wxy_zt);
+    };
+    for (size_t i = 0; i < nc; ++i) OF3D_HIP(launch(i));  // warm every candidate (code load, caches)
     // best of three, the candidates interleaved round-robin (clock drift over the tune hits
     // every candidate alike); each sample two launches back to back, timed together (a single
     // launch after a synchronisation ran up to 5 % off the sustained time of a series: round 5,
@@ -543,10 +599,9 @@ int k34_tune(of3d_plan* p) {
     std::vector<float> ms(nc, 1e30f);
     for (int rep = 0; rep < 3; ++rep) {
         for (size_t i = 0; i < nc; ++i) {
-            OF3D_HIP(launch_k34(p->k34_cand[i], (const F*)G, P, ng, nf, (int)p->ny, (int)p->nx, p->fs, hw, p->stream, p->wxy_zt));
+            OF3D_HIP(launch(i));
             OF3D_HIP(hipEventRecord(e0, p->stream));
-            for (int k = 0; k < 2; ++k)
-                OF3D_HIP(launch_k34(p->k34_cand[i], (const F*)G, P, ng, nf, (int)p->ny, (int)p->nx, p->fs, hw, p->stream, p->wxy_zt));
+            for (int k = 0; k < 2; ++k) OF3D_HIP(launch(i));
             OF3D_HIP(hipEventRecord(e1, p->stream));
             OF3D_HIP(hipEventSynchronize(e1));
             float m = 0.f;
@@ -573,24 +628,18 @@ int k34_tune(of3d_plan* p) {
 
 template <typename F>
 int set_attrs_t(of3d_plan* p) {
-    const size_t e = sizeof(F);
-    p->k1_lds = (size_t)(2 * (K1_TY + 2 * p->rd) + 3 * K1_TY) * 64 * e;
-    p->k2_lds = (size_t)(K2_ZC + 2 * std::max(p->rd, p->rs)) * 64 * e;
-    p->k3_lds = (size_t)(K3_STEP + 2 * p->rw) * 64 * e;
-    p->k4_lds = (size_t)K4_ROWS * (((K4_TX + 2 * k4_halo(p->rw)) | 1) + (K4_TX + 1)) * e;
-    p->k5_lds = (size_t)2 * (k5_geom(p->rw).g * k5_geom(p->rw).r + 2 * p->rw) * 64 * e;
-    const size_t lim = 160 * 1024;
-    if (p->k3_lds > lim || p->k4_lds > lim || p->k5_lds > lim) return fail("of3d: wSig too large for the LDS tiles");
+    const RrLds l = p->lds = rr_lds(p->rd, p->rs, p->rw, sizeof(F));
+    if (l.k3 > kLdsMax || l.k4 > kLdsMax || l.k5 > kLdsMax) return fail("of3d: wSig too large for the LDS tiles");
     auto attr = [&](const void* k, size_t b) -> int {
         OF3D_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b));
         return 0;
     };
     int rc = 0;
-    for (int dt = OF3D_U8; dt <= OF3D_F64; ++dt) rc |= attr(k1_kernel_dt<F>(dt, p->rd), p->k1_lds);
-    rc |= attr((const void*)k_grad_z<F>, p->k2_lds);
-    rc |= attr(k3_kernel<F>(9, p->rw), p->k3_lds) | attr(k3_kernel<F>(5, p->rw), p->k3_lds);
-    rc |= attr(k4_kernel<F>(9, p->rw), p->k4_lds) | attr(k4_kernel<F>(5, p->rw), p->k4_lds);
-    rc |= attr(k5_kernel<F, float>(p->rw), p->k5_lds) | attr(k5_kernel<F, double>(p->rw), p->k5_lds);
+    for (int dt = OF3D_U8; dt <= OF3D_F64; ++dt) rc |= attr(k1_kernel_dt<F>(dt, p->rd), l.k1);
+    rc |= attr((const void*)k_grad_z<F>, l.k2);
+    rc |= attr(k3_kernel<F>(9, p->rw), l.k3) | attr(k3_kernel<F>(5, p->rw), l.k3);
+    rc |= attr(k4_kernel<F>(9, p->rw), l.k4) | attr(k4_kernel<F>(5, p->rw), l.k4);
+    rc |= attr(k5_kernel<F, float>(p->rw), l.k5) | attr(k5_kernel<F, double>(p->rw), l.k5);
     constexpr int epl = 16 / (int)sizeof(F);
     p->k5_nb = (p->nx % epl == 0) ? k5_dma_nb<F>(p->rw) : 0;
     if (p->k5_nb) {
@@ -601,7 +650,7 @@ int set_attrs_t(of3d_plan* p) {
     if (rc) return -1;
     for (int dt : {OF3D_U8, OF3D_U16, OF3D_F32}) {
         if (const void* f = k1c_fn<F>(dt, p->rd, p->rs))
-            OF3D_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            OF3D_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
         for (bool deep : {false, true})
             if (const void* f = k12_fn<F>(dt, p->rd, p->rs, deep))
                 OF3D_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -619,12 +668,8 @@ int set_attrs_t(of3d_plan* p) {
 bool needs_general(const of3d_plan* p) {
     if (p->kn.general) return true;
     if (p->rd > 24 || p->rs > kMaxR || p->rw > kMaxR || p->rs > p->rd) return true;
-    const size_t e = p->fp32 ? 4 : 8, lim = 160 * 1024;
-    const size_t k3 = (size_t)(K3_STEP + 2 * p->rw) * 64 * e;
-    const size_t k4 = (size_t)K4_ROWS * (((K4_TX + 2 * k4_halo(p->rw)) | 1) + (K4_TX + 1)) * e;
-    const size_t k5 = (size_t)2 * (k5_geom(p->rw).g * k5_geom(p->rw).r + 2 * p->rw) * 64 * e;
-    const size_t k2 = (size_t)(K2_ZC + 2 * std::max(p->rd, p->rs)) * 64 * e;
-    return k3 > lim || k4 > lim || k5 > lim || k2 > lim;
+    const RrLds l = rr_lds(p->rd, p->rs, p->rw, elem_size(p));
+    return l.k3 > kLdsMax || l.k4 > kLdsMax || l.k5 > kLdsMax || l.k2 > kLdsMax;
 }
 
 int set_attrs(of3d_plan* p) {
@@ -669,7 +714,7 @@ int run_general(of3d_plan* p, const Frames& fr, int dtype, int64_t frame_z0, con
     F* X = (F*)p->X;
     F* Y = (F*)p->Y;
     const DevTaps<F> tp = dev_taps<F>(p);
-    auto grid = [&](size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 64)); };
+    auto grid = [&](size_t n) { return dim3(grid1d(n, 256 * 64)); };
     const int zb0 = (int)R.zb0, zb1 = (int)R.zb1, zg0 = (int)R.zg0, zg1 = (int)R.zg1, zo0 = (int)R.zo0,
               zo1 = (int)R.zo1;
     auto pass = [&](const F* in, int in_z0, F* out, int out_z0, int q0, int q1, int axis, const F* h, int r, int anti,
@@ -683,13 +728,8 @@ int run_general(of3d_plan* p, const Frames& fr, int dtype, int64_t frame_z0, con
     if (mark(0)) return -1;
     // dt0 (the streaming K0 for any rt) and the centre frame as F, planes [zb0, zb1)
     {
-        size_t off0 = (size_t)(zb0 - frame_z0) * plane, n = (size_t)(zb1 - zb0) * plane;
-        long long fstride = 0;
-        int rt_arg = p->rt;
-        F* D0 = Y;
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
-        void* args[] = {(void*)&fr, (void*)&fstride, (void*)&off0, (void*)&n, (void*)&rt_arg, (void*)&tp.t, (void*)&D0};
-        OF3D_HIP(hipLaunchKernel(k0_kernel_dt<F>(dtype), dim3(blocks), dim3(256), args, 0, st));
+        const size_t off0 = (size_t)(zb0 - frame_z0) * plane, n = (size_t)(zb1 - zb0) * plane;
+        OF3D_HIP(launch_k0<F>(fr, dtype, 0, off0, n, p->rt, tp.t, Y, st));
         const void* Ic = (const char*)fr.p[p->rt] + off0 * es;
         F* If = Y + fs;
         switch (dtype) {
@@ -761,8 +801,7 @@ int run_general(of3d_plan* p, const Frames& fr, int dtype, int64_t frame_z0, con
                                (float*)rel);
     } else {
         const size_t n = (size_t)(zo1 - zo0) * plane;
-        hipLaunchKernelGGL(k_solve2d<F>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 64)), dim3(256), 0, st,
-                           (const F*)Pp, fs, n, vx, vy, (F*)rel);
+        hipLaunchKernelGGL(k_solve2d<F>, grid(n), dim3(256), 0, st, (const F*)Pp, fs, n, vx, vy, (F*)rel);
     }
     OF3D_HIP(hipGetLastError());
     return mark(5);
@@ -790,7 +829,7 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
     F* vz = (F*)vz_;
     F* X = (F*)p->X;
     F* Y = (F*)p->Y;
-    if (zo0 < 0 || zo1 > p->nz || zo0 >= zo1) return fail("of3d: bad output plane range");
+    if (bad_out_range(p, zo0, zo1)) return -1;
     const Ranges R = ranges(p, zo0, zo1);
     if (R.zb1 - R.zb0 > p->cap_planes) return fail("of3d: output range exceeds the plan's workspace");
     if (frame_z0 > R.zb0) return fail("of3d: frames do not hold the stencil halo planes");
@@ -808,35 +847,29 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
     const size_t es = dtype_size(dtype);
     const int nwin = 2 * p->rt + 1;
     const int nf = d3 ? 9 : 5;
+    // the call's input planes [zb0, zb1) as elements of a frame
+    const size_t in_off = (size_t)(R.zb0 - frame_z0) * plane, in_n = (size_t)(R.zb1 - R.zb0) * plane;
     // frame pipelining: this call's dt0 was formed by the previous of3d_plan_execute_next call
     // (inside its K5c) for exactly these frames and planes -> no K0 launch here
-    bool skip_k0 = pipe && p->pipe_valid && p->pipe_dtype == dtype && p->pipe_fz0 == frame_z0 &&
-                   p->pipe_zo0 == zo0 && p->pipe_zo1 == zo1;
-    for (int i = 0; skip_k0 && i < nwin; ++i) skip_k0 = p->pipe_frames[i] == d_frames[i];
-    p->pipe_valid = false;
+    bool skip_k0 = pipe && p->pipe.matches(d_frames, nwin, dtype, frame_z0, zo0, zo1);
+    p->pipe.valid = false;
     // ... and this call's K5c forms the next frame's dt0 (serial schedule, uint16 frames, the
     // vectorised K0 layout: every frame 8-byte aligned at plane zb0, whole groups of 4 voxels)
     K0Next<F> k0n{};
-    bool fuse_next = false;
     // (the fused W kernel keeps W-xy in X; with the K3 + K4 fallback K5c reads Y, where dt0 goes)
-    if (d_next && pipe && p->k5c_next && p->k34.fn && dtype == OF3D_U16 && !p->general && p->zchunk <= 0) {
-        const size_t off0 = (size_t)(R.zb0 - frame_z0) * plane, n = (size_t)(R.zb1 - R.zb0) * plane;
-        constexpr int V = K0Vec<uint16_t>::V;
-        fuse_next = off0 % V == 0 && n % V == 0;
-        for (int i = 0; fuse_next && i < nwin; ++i)
-            fuse_next = d_next[i] && ((uintptr_t)d_next[i] % (V * sizeof(uint16_t))) == 0;
-        if (fuse_next) {
-            for (int i = 0; i < nwin; ++i) k0n.fr.p[i] = d_next[i];
-            k0n.off0 = off0;
-            k0n.ngroups = n / V;
-            k0n.ht = tp.t;
-        }
+    bool fuse_next = d_next && pipe && p->k5c_next && p->k34.fn && dtype == OF3D_U16 && !p->general &&
+                     p->zchunk <= 0 && k0_vec_ok(d_next, nwin, dtype, in_off, in_n);
+    if (fuse_next) {
+        for (int i = 0; i < nwin; ++i) k0n.fr.p[i] = d_next[i];
+        k0n.off0 = in_off;
+        k0n.ngroups = in_n / k0_vec_width(dtype);
+        k0n.ht = tp.t;
     }
     // K12 (fused gradient y/x/z passes, 3D): dt0 then lives in Y4 (K12 writes G = Y0..3
     // while other blocks still read dt0 planes), the pre-z fields B are never formed
     // (LDS-DMA staging: 16-byte rows and planes of dt0 and of the centre frame)
     const bool k12_al = (nx * sizeof(F)) % 16 == 0 && (nx * es) % 16 == 0 &&
-                        ((uintptr_t)d_frames[p->rt] + (size_t)(R.zb0 - frame_z0) * plane * es) % 16 == 0;
+                        ((uintptr_t)d_frames[p->rt] + in_off * es) % 16 == 0;
     // K12 pays where its blocks can march >= 32 planes and still fill the GPU: fp64 (one 12-wave
     // block per CU), one round of 32-plane marches on every CU — c2 (256^2 x 64: 256 blocks) K0
     // + K12 0.110 ms vs K0 + K1c + K2c 0.142, frame 0.377 vs 0.420 (round 5; with 16-plane
@@ -858,25 +891,16 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
     Frames frm{};
     // (the fused W kernel writes W-xy to X; the K3 + K4 fallback writes it to Y over the slots)
     if (ahead >= 0 && d3 && k12 && p->k34.fn && p->zchunk <= 0 && !p->general) {
-        for (int sl = 0; sl < of3d_plan::kDtSlots && !skip_k0; ++sl) {
-            auto& d = p->dts[sl];
-            bool hit = d.valid && d.dtype == dtype && d.fz0 == frame_z0 && d.zo0 == zo0 && d.zo1 == zo1;
-            for (int i = 0; hit && i < nwin; ++i) hit = d.frames[i] == d_frames[i];
-            if (hit) skip_k0 = true, dslot = sl, d.valid = false;  // consumed
-        }
+        for (int sl = 0; sl < of3d_plan::kDtSlots && !skip_k0; ++sl)
+            if (p->dts[sl].matches(d_frames, nwin, dtype, frame_z0, zo0, zo1))
+                skip_k0 = true, dslot = sl, p->dts[sl].valid = false;  // consumed
         const int m = std::min(ahead, of3d_plan::kDtSlots - 1) + 1;
         if (!skip_k0)
             for (auto& d : p->dts) d.valid = false;
-        if (!skip_k0 && m >= 2) {
-            const int V = k0_vec_width(dtype);
-            const size_t off0 = (size_t)(R.zb0 - frame_z0) * plane, n = (size_t)(R.zb1 - R.zb0) * plane;
-            bool vec = off0 % V == 0 && n % V == 0;
-            for (int i = 0; vec && i < nwin + m - 1; ++i) {
-                vec = d_frames[i] && ((uintptr_t)d_frames[i] % ((size_t)V * es)) == 0;
-                frm.p[i] = d_frames[i];
-            }
-            k0m_k = vec ? k0m_fn<F>(dtype, p->rt, m) : nullptr;
+        if (!skip_k0 && m >= 2 && k0_vec_ok(d_frames, nwin + m - 1, dtype, in_off, in_n)) {
+            k0m_k = k0m_fn<F>(dtype, p->rt, m);
             if (k0m_k) k0m = m;
+            for (int i = 0; i < nwin + m - 1; ++i) frm.p[i] = d_frames[i];
         }
     } else {
         for (auto& d : p->dts) d.valid = false;
@@ -900,44 +924,37 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
             size_t off0 = (size_t)(b0 - frame_z0) * plane, ng = (size_t)nb * plane / k0_vec_width(dtype);
             F* D0 = Y + 4 * fs + (size_t)(b0 - R.zb0) * plane;
             size_t dstride = fs;
-            const unsigned blocks = (unsigned)std::min<size_t>((ng + 255) / 256, 256 * 32);
             void* margs[] = {(void*)&frm, (void*)&off0, (void*)&ng, (void*)&tp.t, (void*)&D0, (void*)&dstride};
-            OF3D_HIP(hipLaunchKernel(k0m_k, dim3(blocks), dim3(256), margs, 0, st));
+            OF3D_HIP(hipLaunchKernel(k0m_k, dim3(grid1d(ng, 256 * 32)), dim3(256), margs, 0, st));
             p->used |= KU_K0M;
             p->last_k0m = k0m;
         } else if (!skip_k0) {  // (else: dt0 formed by an earlier call: K5c's next / a batched K0)
-            long long fstride = 0;
-            if (nwin > 1) {
-                const long long d = (const char*)d_frames[1] - (const char*)d_frames[0];
-                bool eq = d > 0 && d % (long long)es == 0;
-                for (int i = 2; eq && i < nwin; ++i) eq = ((const char*)d_frames[i] - (const char*)d_frames[i - 1]) == d;
-                if (eq) fstride = d / (long long)es;
-            }
             size_t off0 = (size_t)(b0 - frame_z0) * plane, n = (size_t)nb * plane;
             int rt_arg = p->rt;
             F* D0 = D0b + (size_t)(b0 - R.zb0) * plane;
-            const int V = k0_vec_width(dtype);
-            const size_t vb = (size_t)V * es;
-            bool vec = off0 % V == 0 && n % V == 0;
-            for (int i = 0; vec && i < nwin; ++i) vec = ((uintptr_t)d_frames[i] % vb) == 0;
-            if (vec) {
-                size_t ng = n / V;
-                const unsigned blocks = (unsigned)std::min<size_t>((ng + 255) / 256, 256 * 32);
+            if (k0_vec_ok(d_frames, nwin, dtype, off0, n)) {
+                size_t ng = n / k0_vec_width(dtype);
+                const dim3 blocks(grid1d(ng, 256 * 32));
                 void* args[] = {(void*)&fr, (void*)&off0, (void*)&ng, (void*)&rt_arg, (void*)&tp.t, (void*)&D0};
                 const void* k0 = p->kn.k0c ? k0c_fn<F>(dtype, p->rt) : nullptr;
                 if (k0) {
                     void* cargs[] = {(void*)&fr, (void*)&off0, (void*)&ng, (void*)&tp.t, (void*)&D0};
-                    OF3D_HIP(hipLaunchKernel(k0, dim3(blocks), dim3(256), cargs, 0, st));
+                    OF3D_HIP(hipLaunchKernel(k0, blocks, dim3(256), cargs, 0, st));
                     p->used |= KU_K0C;
                 } else {
-                    OF3D_HIP(hipLaunchKernel(k0v_kernel_dt<F>(dtype), dim3(blocks), dim3(256), args, 0, st));
+                    OF3D_HIP(hipLaunchKernel(k0v_kernel_dt<F>(dtype), blocks, dim3(256), args, 0, st));
                     p->used |= KU_K0;
                 }
             } else {
-                const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
-                void* args[] = {(void*)&fr, (void*)&fstride, (void*)&off0, (void*)&n, (void*)&rt_arg, (void*)&tp.t,
-                                (void*)&D0};
-                OF3D_HIP(hipLaunchKernel(k0_kernel_dt<F>(dtype), dim3(blocks), dim3(256), args, 0, st));
+                // equally spaced frames (one allocation): the kernel walks them by their stride
+                long long fstride = 0;
+                if (nwin > 1) {
+                    const long long d = (const char*)d_frames[1] - (const char*)d_frames[0];
+                    bool eq = d > 0 && d % (long long)es == 0;
+                    for (int i = 2; eq && i < nwin; ++i) eq = ((const char*)d_frames[i] - (const char*)d_frames[i - 1]) == d;
+                    if (eq) fstride = d / (long long)es;
+                }
+                OF3D_HIP(launch_k0<F>(fr, dtype, fstride, off0, n, p->rt, tp.t, D0, st));
                 p->used |= KU_K0;
             }
         }
@@ -971,7 +988,7 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
             OF3D_HIP(hipLaunchKernel(k1c, dim3(blocks), dim3(cw), cargs, lds, st));
             p->used |= KU_K1C;
         } else {
-            OF3D_HIP(hipLaunchKernel(k1_kernel_dt<F>(dtype, p->rd), g, dim3(64, 4), args, p->k1_lds, st));
+            OF3D_HIP(hipLaunchKernel(k1_kernel_dt<F>(dtype, p->rd), g, dim3(64, 4), args, p->lds.k1, st));
             p->used |= KU_K1;
         }
         return 0;
@@ -1040,7 +1057,7 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
             p->used |= KU_K2C;
         } else {
             dim3 g(cdiv(nx, 64), ny, cdiv(ng, K2_ZC) * 4);
-            hipLaunchKernelGGL(k_grad_z<F>, g, dim3(64, 4), p->k2_lds, st, Bc, zb0, Go, zg0, ngz, nzz, ny, nx, fs, tp);
+            hipLaunchKernelGGL(k_grad_z<F>, g, dim3(64, 4), p->lds.k2, st, Bc, zb0, Go, zg0, ngz, nzz, ny, nx, fs, tp);
             OF3D_HIP(hipGetLastError());
             p->used |= KU_K2;
         }
@@ -1056,18 +1073,17 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
         p->used |= p->k34.nthr ? (p->k34.nthr == p->k34.cw ? KU_K34PK : KU_K34WS) : KU_K34;
         return 0;
     };
-    auto k3k4 = [&](hipStream_t st) -> int {  // fallback: W y and W x as two kernels (whole range)
+    // fallback: products + W y (k3) and W x (k4) as two kernels (whole range)
+    auto k3 = [&](hipStream_t st) -> int {
         const int ng = (int)(R.zg1 - R.zg0);
         F* P = Pb;
         const F* G = Gb;
-        {
-            dim3 g(cdiv(nx, 64), 1, ng * nf);
-            int rw_arg = p->rw;
-            void* args[] = {(void*)&G, (void*)&P, (void*)&ny, (void*)&nx, (void*)&fs, (void*)&tp.w, (void*)&tp.wr,
-                            (void*)&rw_arg};
-            OF3D_HIP(hipLaunchKernel(k3_kernel<F>(nf, p->rw), g, dim3(64, 4), args, p->k3_lds, st));
-            p->used |= KU_K3;
-        }
+        dim3 g(cdiv(nx, 64), 1, ng * nf);
+        int rw_arg = p->rw;
+        void* args[] = {(void*)&G, (void*)&P, (void*)&ny, (void*)&nx, (void*)&fs, (void*)&tp.w, (void*)&tp.wr,
+                        (void*)&rw_arg};
+        OF3D_HIP(hipLaunchKernel(k3_kernel<F>(nf, p->rw), g, dim3(64, 4), args, p->lds.k3, st));
+        p->used |= KU_K3;
         return 0;
     };
     auto k4 = [&](hipStream_t st) -> int {
@@ -1078,7 +1094,7 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
         F* Q = Qb;
         void* args[] = {(void*)&Pc, (void*)&Q, (void*)&ny, (void*)&nx, (void*)&fs, (void*)&tp.w, (void*)&tp.wr,
                         (void*)&rw_arg};
-        OF3D_HIP(hipLaunchKernel(k4_kernel<F>(nf, p->rw), g, dim3(64, 4), args, p->k4_lds, st));
+        OF3D_HIP(hipLaunchKernel(k4_kernel<F>(nf, p->rw), g, dim3(64, 4), args, p->lds.k4, st));
         p->used |= KU_K4;
         return 0;
     };
@@ -1115,14 +1131,14 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
                 p->used |= KU_K5DMA;
             } else {
                 const void* k = p->rel64 ? k5_kernel<F, double>(p->rw) : k5_kernel<F, float>(p->rw);
-                OF3D_HIP(hipLaunchKernel(k, g, dim3(64, kg.g), args, p->k5_lds, st));
+                OF3D_HIP(hipLaunchKernel(k, g, dim3(64, kg.g), args, p->lds.k5, st));
                 p->used |= KU_K5;
             }
         } else {
             // (2D: planes [o0, o1) of a batch of independent frames)
             const size_t n = (size_t)(o1 - o0) * plane;  // (64-bit: a batch may exceed 2^31 pixels)
-            hipLaunchKernelGGL(k_solve2d<F>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 64)), dim3(256), 0,
-                               st, (const F*)Qb + (size_t)(o0 - R.zg0) * plane, fs, n, ovx, ovy, (F*)orel);
+            hipLaunchKernelGGL(k_solve2d<F>, dim3(grid1d(n, 256 * 64)), dim3(256), 0, st,
+                               (const F*)Qb + (size_t)(o0 - R.zg0) * plane, fs, n, ovx, ovy, (F*)orel);
             p->used |= KU_SOLVE2D;
         }
         OF3D_HIP(hipGetLastError());
@@ -1133,18 +1149,23 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
     const int slot = p->timing_slots ? (int)(p->tcount % p->timing_slots) : 0;
     hipEvent_t* evs = p->host_ev ? p->ev : (p->timing_slots ? &p->tev[(size_t)slot * p->tev_per_slot] : nullptr);
     const unsigned tmask = p->host_ev ? (1u << kStages) - 1 : p->timing_mask;
+    // boundary i opens stage i and closes stage i-1; untimed stages get no events
+    // (every event is a barrier packet between kernels: a few microseconds each)
+    const unsigned bmask = tmask | (tmask << 1);
+    auto mark = [&](int i) -> int {
+        if (evs && ((bmask >> i) & 1u)) OF3D_HIP(hipEventRecord(evs[i], s));
+        return 0;
+    };
+    // a timed execution fills its slot of the ring: the chunks timed (overlap mode, one stage) or 0
+    auto count_timed = [&](int chunks) {
+        if (p->host_ev || !p->timing_slots) return;
+        p->tchunks[slot] = chunks;
+        ++p->tcount;
+    };
     if (p->general) {
         p->used |= KU_GENERAL;
-        const unsigned bmask = tmask | (tmask << 1);
-        auto mark = [&](int i) -> int {
-            if (evs && ((bmask >> i) & 1u)) OF3D_HIP(hipEventRecord(evs[i], s));
-            return 0;
-        };
         if (run_general<F>(p, fr, dtype, frame_z0, R, vx, vy, vz, rel, s, mark)) return -1;
-        if (!p->host_ev && p->timing_slots) {
-            p->tchunks[slot] = 0;
-            ++p->tcount;
-        }
+        count_timed(0);
         p->stages_run = kStages;
         return 0;
     }
@@ -1157,41 +1178,19 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
         if (nch < 2) nch = 1;
     }
     if (nch > 1) fuse_next = false, k0m = 0;  // (zchunk > 0 already excluded both; the invariant)
-    if (nch == 1) {
-        // serial: boundary i opens stage i and closes stage i-1; untimed stages get no events
-        // (every event is a barrier packet between kernels: a few microseconds each)
-        const unsigned bmask = tmask | (tmask << 1);
-        auto mark = [&](int i) -> int {
-            if (evs && ((bmask >> i) & 1u)) OF3D_HIP(hipEventRecord(evs[i], s));
-            return 0;
-        };
+    if (nch == 1) {  // serial
         if (mark(0) || k01(R.zb0, R.zb1, s) || mark(1) || k2(R.zg0, R.zg1, s) || mark(2)) return -1;
         if (p->k34.fn) {
             if (k34(R.zg0, R.zg1, s) || mark(3)) return -1;  // "prod_wy" holds W x too; "wx" stays empty
         } else {
-            if (k3k4(s) || mark(3) || k4(s)) return -1;
+            if (k3(s) || mark(3) || k4(s)) return -1;
         }
         if (mark(4) || k5(R.zo0, R.zo1, R.zg1, s) || mark(5)) return -1;
-        if (!p->host_ev && p->timing_slots) {
-            p->tchunks[slot] = 0;
-            ++p->tcount;
-        }
-        for (int j = 1; j < k0m; ++j) {  // the batched windows the next calls may skip K0 for
-            auto& d = p->dts[j];
-            d.valid = true;
-            for (int i = 0; i < nwin; ++i) d.frames[i] = d_frames[j + i];
-            d.dtype = dtype;
-            d.fz0 = frame_z0;
-            d.zo0 = zo0;
-            d.zo1 = zo1;
-        }
+        count_timed(0);
+        // the batched windows the next calls may skip K0 for
+        for (int j = 1; j < k0m; ++j) p->dts[j].set(d_frames + j, nwin, dtype, frame_z0, zo0, zo1);
         if (fuse_next && p->k5c && d3) {  // the next call may skip its K0
-            p->pipe_valid = true;
-            for (int i = 0; i < nwin; ++i) p->pipe_frames[i] = d_next[i];
-            p->pipe_fz0 = frame_z0;
-            p->pipe_zo0 = zo0;
-            p->pipe_zo1 = zo1;
-            p->pipe_dtype = dtype;
+            p->pipe.set(d_next, nwin, dtype, frame_z0, zo0, zo1);
             p->pipe_k12 = k12 != nullptr;
         }
     } else {
@@ -1223,10 +1222,7 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
         }
         OF3D_HIP(hipEventRecord(p->ev_join, s2));
         OF3D_HIP(hipStreamWaitEvent(s, p->ev_join, 0));
-        if (!p->host_ev && p->timing_slots) {
-            p->tchunks[slot] = one_stage ? nch : 0;
-            ++p->tcount;
-        }
+        count_timed(one_stage ? nch : 0);
     }
     p->stages_run = kStages;
     return 0;
@@ -1252,11 +1248,13 @@ void plan_free(of3d_plan* p);
 // 2^31 bytes for the largest S of any K34 candidate the autotune may pick (an fp64 plan
 // of nz = nx = 4096, ny = 64 would span 2 GiB per 16-row tile, and stores past it are dropped by the
 // descriptor's range check without an error).  Plans past it keep the plain planes.
-bool wxy_tile_fits(const of3d_plan* p) {
+int k34_smax(const of3d_plan* p) {  // the largest tile height of the pick and the candidates
     int smax = p->k34.s;
     for (const auto& k : p->k34_cand) smax = std::max(smax, k.s);
-    const size_t es = p->fp32 ? sizeof(float) : sizeof(double);
-    return (size_t)smax * (size_t)p->nx * (size_t)p->cap_planes * es <= 0x7fffffffu;
+    return smax;
+}
+bool wxy_tile_fits(const of3d_plan* p) {
+    return (size_t)k34_smax(p) * (size_t)p->nx * (size_t)p->cap_planes * elem_size(p) <= 0x7fffffffu;
 }
 
 int plan_create(of3d_plan** out, int ndim, int64_t nz, int64_t ny, int64_t nx, const of3d_taps* taps, int mode,
@@ -1308,7 +1306,7 @@ int plan_create(of3d_plan** out, int ndim, int64_t nz, int64_t ny, int64_t nx, c
         OF3D_HIP(hipMalloc(&p->d_taps32, h32.size() * sizeof(float)));
         OF3D_HIP(hipMemcpy(p->d_taps32, h32.data(), h32.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    const size_t es = p->fp32 ? sizeof(float) : sizeof(double);
+    const size_t es = elem_size(p.get());
     OF3D_HIP(hipMalloc(&p->X, 9 * p->fs * es));
     OF3D_HIP(hipMalloc(&p->Y, 9 * p->fs * es));
     OF3D_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
@@ -1459,7 +1457,6 @@ int host_flow(int ndim, const void* images, int dtype, int64_t nt, int64_t nz, i
         p->d_out_bytes = out_bytes;
     }
     hipStream_t s = p->stream;
-    hipEvent_t e0 = p->ev[0], e1 = p->ev[1];
     const void* dptr[kMaxT];
     // distinct frames needed, uploaded once each
     std::vector<int64_t> src(nwin);
@@ -1487,8 +1484,6 @@ int host_flow(int ndim, const void* images, int dtype, int64_t nt, int64_t nz, i
         (void)hipEventElapsedTime(&m, p->ev[i], p->ev[i + 1]);
         p->stage_ms[i] = m;
     }
-    (void)e0;
-    (void)e1;
     const auto t2 = std::chrono::steady_clock::now();
     OF3D_HIP(hipMemcpyAsync(vx, dvx, vox * sizeof(double), hipMemcpyDeviceToHost, s));
     OF3D_HIP(hipMemcpyAsync(vy, dvy, vox * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1504,6 +1499,25 @@ int host_flow(int ndim, const void* images, int dtype, int64_t nt, int64_t nz, i
         perf->ms_total = ms(t0, t3);
     }
     return 0;
+}
+
+// Head of the three execute entry points: the argument checks, then the plan's device.  (Their
+// `stream` is a hipStream_t; NULL: the device's null stream, HIP's convention.)
+int exec_begin(of3d_plan* p, const void* const* d_frames, void* vx, void* vy, void* vz, void* rel, int n_ahead = 0) {
+    if (!p || !d_frames || !vx || !vy || !rel || (p->ndim == 3 && !vz)) return fail("of3d: null argument");
+    if (n_ahead < 0) return fail("of3d: n_ahead out of range");
+    OF3D_HIP(hipSetDevice(p->device));
+    return 0;
+}
+
+// A string result into the caller's buffer (n bytes, NUL-terminated, cut to fit): the full length
+int copy_out(char* buf, size_t n, const std::string& out) {
+    if (buf && n) {
+        const size_t k = std::min(n - 1, out.size());
+        memcpy(buf, out.data(), k);
+        buf[k] = 0;
+    }
+    return (int)out.size();
 }
 
 }  // namespace
@@ -1578,12 +1592,12 @@ int of3d_plan_destroy(of3d_plan* plan) {
 }
 
 size_t of3d_plan_workspace_bytes(const of3d_plan* p) {
-    return p ? 18 * p->fs * (p->fp32 ? sizeof(float) : sizeof(double)) : 0;
+    return p ? 18 * p->fs * elem_size(p) : 0;
 }
 
 int of3d_plan_input_range(const of3d_plan* p, int64_t zo0, int64_t zo1, int64_t* zi0, int64_t* zi1) {
     if (!p || !zi0 || !zi1) return fail("of3d: null argument");
-    if (zo0 < 0 || zo1 > p->nz || zo0 >= zo1) return fail("of3d: bad output plane range");
+    if (bad_out_range(p, zo0, zo1)) return -1;
     const Ranges r = ranges(p, zo0, zo1);
     *zi0 = r.zb0;
     *zi1 = r.zb1;
@@ -1592,29 +1606,22 @@ int of3d_plan_input_range(const of3d_plan* p, int64_t zo0, int64_t zo1, int64_t*
 
 int of3d_plan_execute(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0, int64_t zo0, int64_t zo1,
                       void* vx, void* vy, void* vz, void* rel, void* stream) {
-    if (!p || !d_frames || !vx || !vy || !rel || (p->ndim == 3 && !vz)) return fail("of3d: null argument");
-    OF3D_HIP(hipSetDevice(p->device));
-    hipStream_t s = (hipStream_t)stream;  // NULL: the device's null stream (HIP's convention)
-    return run(p, d_frames, dtype, frame_z0, zo0, zo1, vx, vy, vz, rel, s);
+    if (exec_begin(p, d_frames, vx, vy, vz, rel)) return -1;
+    return run(p, d_frames, dtype, frame_z0, zo0, zo1, vx, vy, vz, rel, (hipStream_t)stream);
 }
 
 int of3d_plan_execute_next(of3d_plan* p, const void* const* d_frames, const void* const* d_frames_next, int dtype,
                            int64_t frame_z0, int64_t zo0, int64_t zo1, void* vx, void* vy, void* vz, void* rel,
                            void* stream) {
-    if (!p || !d_frames || !vx || !vy || !rel || (p->ndim == 3 && !vz)) return fail("of3d: null argument");
-    OF3D_HIP(hipSetDevice(p->device));
-    hipStream_t s = (hipStream_t)stream;  // NULL: the device's null stream (HIP's convention)
-    return run(p, d_frames, dtype, frame_z0, zo0, zo1, vx, vy, vz, rel, s, d_frames_next, true);
+    if (exec_begin(p, d_frames, vx, vy, vz, rel)) return -1;
+    return run(p, d_frames, dtype, frame_z0, zo0, zo1, vx, vy, vz, rel, (hipStream_t)stream, d_frames_next, true);
 }
 
 int of3d_plan_execute_ahead(of3d_plan* p, const void* const* d_frames, int n_ahead, int dtype, int64_t frame_z0,
                             int64_t zo0, int64_t zo1, void* vx, void* vy, void* vz, void* rel, void* stream) {
-    if (!p || !d_frames || !vx || !vy || !rel || (p->ndim == 3 && !vz)) return fail("of3d: null argument");
-    if (n_ahead < 0) return fail("of3d: n_ahead out of range");
+    if (exec_begin(p, d_frames, vx, vy, vz, rel, n_ahead)) return -1;
     n_ahead = std::min(n_ahead, kMaxT - (2 * p->rt + 1));  // frames past kMaxT are not batched
-    OF3D_HIP(hipSetDevice(p->device));
-    hipStream_t s = (hipStream_t)stream;  // NULL: the device's null stream (HIP's convention)
-    return run(p, d_frames, dtype, frame_z0, zo0, zo1, vx, vy, vz, rel, s, nullptr, false, n_ahead);
+    return run(p, d_frames, dtype, frame_z0, zo0, zo1, vx, vy, vz, rel, (hipStream_t)stream, nullptr, false, n_ahead);
 }
 
 int of3d_plan_set_timing(of3d_plan* p, int slots) {
@@ -1695,18 +1702,11 @@ int of3d_plan_kernels(const of3d_plan* p, char* buf, size_t n) {
     std::string out;
     for (size_t i = 0; i < sizeof(kKernelNames) / sizeof(kKernelNames[0]); ++i)
         if ((p->used >> i) & 1u) out += (out.empty() ? "" : ",") + std::string(kKernelNames[i]);
-    if (buf && n) {
-        const size_t k = std::min(n - 1, out.size());
-        memcpy(buf, out.data(), k);
-        buf[k] = 0;
-    }
-    return (int)out.size();
+    return copy_out(buf, n, out);
 }
 
 int of3d_plan_geometry(const of3d_plan* p, char* buf, size_t n) {
     if (!p) return fail("of3d: null plan");
-    int smax = p->k34.s;
-    for (const auto& k : p->k34_cand) smax = std::max(smax, k.s);
     // the runtime-radius kernels' rungs for the plan's radii, from the functions their getters
     // switch on (zeros on the general path, which launches none of them)
     const bool rr = !p->general;
@@ -1726,16 +1726,10 @@ int of3d_plan_geometry(const of3d_plan* p, char* buf, size_t n) {
              "\"runtime_radius\": %s}",
              p->ndim, (long long)p->nz, (long long)p->ny, (long long)p->nx, (int)p->fp32, (int)p->general,
              (long long)p->cap_planes, p->wxy_zt, p->k34.cw, p->k34.s, p->k34.tx, p->k34.nbx,
-             p->k34.nthr ? p->k34.nthr : p->k34.cw, p->k34.lds, p->k34_cand.size(), smax, p->k5c ? p->k5c_r : 0,
+             p->k34.nthr ? p->k34.nthr : p->k34.cw, p->k34.lds, p->k34_cand.size(), k34_smax(p), p->k5c ? p->k5c_r : 0,
              p->k5c ? p->k5c_nw : 0, p->k5c_lds, p->last_k12_zc, p->last_k12_gx, p->last_k12_gy, p->last_k12_deep, p->last_k0m,
              p->ncu, rrs);
-    const std::string out(tmp);
-    if (buf && n) {
-        const size_t k = std::min(n - 1, out.size());
-        memcpy(buf, out.data(), k);
-        buf[k] = 0;
-    }
-    return (int)out.size();
+    return copy_out(buf, n, tmp);
 }
 
 int of3d_plan_set_overlap(of3d_plan* p, int64_t chunk_planes) {
@@ -1796,7 +1790,7 @@ int of3d_flow_stats(const void* vx, const void* vy, const void* vz, const void* 
     if (!vx || !vy || !rel || !out_vx || !out_vy || !magnitude || !theta) return fail("of3d: null argument");
     if (vz && (!out_vz || !phi)) return fail("of3d: null argument");
     hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 256 * 32);
+    const unsigned blocks = grid1d((size_t)n, 256 * 32);
     auto launch = [&](auto vt, auto rt) {
         using VT = decltype(vt);
         using RT = decltype(rt);
@@ -1817,7 +1811,7 @@ int of3d_rel3d(const double* tensor, int64_t n, void* rel, int rel_f64, void* st
     if (n == 0) return 0;
     if (!tensor || !rel) return fail("of3d: null argument");
     hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 256 * 32);
+    const unsigned blocks = grid1d((size_t)n, 256 * 32);
     if (rel_f64)
         hipLaunchKernelGGL(k_rel3d<double>, dim3(blocks), dim3(256), 0, s, tensor, (size_t)n, (double*)rel);
     else

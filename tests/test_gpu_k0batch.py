@@ -102,6 +102,37 @@ def test_batching_off_paths(env, monkeypatch):
         plan.close()
 
 
+def test_misaligned_lookahead_frame_forms_no_batch():
+    """A lookahead frame that is 2-byte aligned only cannot take the vectorised K0 layout: no
+    batch forms (the window's own aligned frames still run the vectorised K0), and once that
+    frame is inside a window the scalar K0 runs.  It is never the centre frame of windows 0..4,
+    so the fused gradient kernel's 16-byte check holds throughout.  Every output exact."""
+    import torch
+
+    s, t, w = 2, 2, 5
+    nwin = 2 * radii(s, t, w)[2] + 1
+    stack, frames = _series(nwin + 4, s, t, w, 16)
+    n = NZ * NY * NX
+    buf = torch.empty(n + 1, dtype=torch.int16, device="cuda")
+    buf[1:].copy_(frames[nwin].reshape(-1))
+    frames[nwin] = buf[1:]  # the first lookahead frame, one element into its buffer
+    assert frames[nwin].data_ptr() % 4 == 2
+    plan = _lib.Plan(3, NZ, NY, NX, make_taps(s, t, w), device=0)
+    try:
+        for k in range(5):
+            got = _call(plan, frames, k, nwin, min(3, 4 - k), torch.float64, torch.float32)
+            for a, b in zip(got, calc_flow3D(stack[k:k + nwin], s, t, w)):
+                assert bits_equal(a, b), k
+            ks = plan.kernels()
+            assert "k_tderiv_multi" not in ks, (k, ks)
+            if k == 0:
+                assert "k_tderiv_c" in ks and "k_tderiv" not in ks, ks
+            else:  # the misaligned frame is inside windows 1..4
+                assert "k_tderiv" in ks, (k, ks)
+    finally:
+        plan.close()
+
+
 def test_out_of_order_and_plain_calls():
     """Batched windows used out of order, a plain call dropping the batch, a window whose
     frames are not the batch's (other pointers), the same window twice: all exact."""

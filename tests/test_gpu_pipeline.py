@@ -100,6 +100,36 @@ def test_pipelining_off_with_k34_fallback(env, monkeypatch):
         plan.close()
 
 
+def test_misaligned_next_frame_is_not_fused():
+    """A next window whose newest frame is 2-byte aligned only cannot take the vectorised K0
+    layout: K5c does not form its dt0 (no k_wz_solve_c_next launch), and both windows equal a
+    second plan's plain execution.  (Control: the same plan fuses the aligned series.)"""
+    import torch
+
+    s, t, w = 2, 2, 5
+    shape = (16, 32, 40)
+    stack, wins, rt = _series((13 + 3,) + shape, s, t, w, 6)
+    old = wins[1][-1]  # the newest frame of window 1, one element into its buffer
+    buf = torch.empty(old.numel() + 1, dtype=torch.int16, device="cuda")
+    buf[1:].copy_(old.reshape(-1))
+    assert buf[1:].data_ptr() % 4 == 2
+    mis = [[buf[1:] if f is old else f for f in wv] for wv in wins]
+    plan = _lib.Plan(3, *shape, make_taps(s, t, w), device=0)
+    plain_plan = _lib.Plan(3, *shape, make_taps(s, t, w), device=0)
+    try:
+        got = _run(plan, mis, None, (0, 16), shape, torch.float64, [(0, 1, True), (1, 2, True)])
+        assert "k_wz_solve_c_next" not in plan.kernels(), plan.kernels()
+        want = _run(plain_plan, mis, None, (0, 16), shape, torch.float64, [(0, None, False), (1, None, False)])
+        for k, (g, wv) in enumerate(zip(got, want)):
+            for a, b in zip(g, wv):
+                assert bits_equal(a, b), k
+        _run(plan, wins, None, (0, 16), shape, torch.float64, [(0, 1, True)])
+        assert "k_wz_solve_c_next" in plan.kernels(), plan.kernels()
+    finally:
+        plan.close()
+        plain_plan.close()
+
+
 def test_break_in_series_recomputes():
     """execute_next(A, next=B) then a call for other frames (C): the pending dt0 (for B) must
     not be used; then B after C: recomputed too."""
