@@ -533,6 +533,57 @@ int of3d_flow_pair(const void* d_vx0, const void* d_vy0, const void* d_vz0, cons
                    double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const int* nbins4,
                    const double* const* edges4, void* d_result, void* workspace, void* stream);
 
+/* Quiver samples of the frame summary: per box the vectors that the reference's figure scripts
+ * hand to quiver / quiver3 — every gap-th voxel of the ROI whose masked velocity is not NaN
+ * (example_analysis_script.m:64-66,121-135, plot_figure4_Movies.m:121-143, plot_figure5.m:119-156,
+ * plot_FigureS2_dt.m:99-143, plot_figure3_ChannelCompare.m:181) — as an ordered list, so that a
+ * summary-only series (no field downloads) can still be drawn.  Fields, d_rel, dtypes, dims,
+ * d_thresh, scales and rois as of3d_flow_summary's; d_keep NULL: the mask factor is
+ * rel > *d_thresh, else bit r of d_keep for box r, as of3d_flow_summary_masked (d_rel and d_thresh
+ * may then be NULL; word 0 of the result is NaN without a d_thresh).  gap3: host int64[3] =
+ * gz gy gx, each >= 1.  capacity: host int64[n_roi], each >= 0.  For every box r independently:
+ *   lattice  the voxels (z0 + i*gz, y0 + j*gy, x0 + k*gx) inside the box — anchored at the box
+ *            origin, as y1:gap:y2 is in the scripts; n_lattice of them;
+ *   valid    of3d_flow_summary's predicate: every component v * mask factor, an exact zero ->
+ *            NaN, (v*scale)/tscale (vz with zscale); valid <=> the magnitude is not NaN;
+ *   output   the valid lattice voxels in C order (z, then y, then x ascending): the voxel's
+ *            linear index in the whole volume and its three physical velocities as float64 (vz 0.0
+ *            in 2D) — for a numpy user f[z0:z1:gz, y0:y1:gy, x0:x1:gx][valid] of each field;
+ *   capacity n_valid is always the full count, n_stored = min(n_valid, capacity[r]), the stored
+ *            records are the first n_stored in that order; nothing is written past the block.
+ * 2D: d_vz == NULL and nz == 1 (a d_vz with nz == 1 is an error).
+ *
+ * Result (device, of3d_quiver_result_bytes(n_roi, capacity) bytes, 8-byte words):
+ *   word 0        the threshold as float64
+ *   words 1..5    n_roi, gz, gy, gx, has_vz (int64)
+ *   then per box, 4 words: n_lattice, n_valid, n_stored, the word offset of the box's block
+ *   then per box its block, 4 * capacity[r] words: capacity[r] linear indices (int64), then as
+ *   many vx, vy and vz (float64).  The words of an array past n_stored are unspecified.
+ * Three launches on `stream`: (1) per box sum_workgroups(lattice points, lattice rows) workgroups
+ * — a function of the box and the gap alone —, each over a contiguous run of lattice rows, split
+ * into one contiguous sub-run per wave; a wave walks its sub-run 64 consecutive lattice points
+ * per step and adds up the population count of the 64-bit ballot of `valid`; one count per wave
+ * goes to the workspace.  (2) One workgroup per box scans the wave counts (exclusive, in
+ * workgroup-then-wave order = C order) and writes the header.  (3) The walk of (1) again, by the
+ * same device function: a lane's record index is its wave's base + the valid lanes below it;
+ * records below the capacity are stored by plain stores.  No atomics of any kind: a record's
+ * place and value are fixed by the inputs alone, so equal inputs give equal bits on every run,
+ * and a box's counts and records do not depend on the other boxes.
+ * `workspace`: device memory of of3d_quiver_workspace_bytes(rois, n_roi, gap3) bytes, one word per
+ * wave of every workgroup; host arithmetic only.  Both *_bytes functions return 0 (and
+ * of3d_last_error's text) on a refusal: a null pointer, an invalid box, more than 16 boxes, a gap
+ * below 1, a negative capacity, a workgroup share of 2^31 lattice points or more.  Enqueued on
+ * `stream`; no host copy, no host synchronisation, no workgroup waits for another. */
+#define OF3D_QUIVER_HEAD_WORDS 6
+#define OF3D_QUIVER_ROI_WORDS 4
+size_t of3d_quiver_result_bytes(int n_roi, const int64_t* capacity);
+size_t of3d_quiver_workspace_bytes(const int64_t* rois, int n_roi, const int64_t* gap3);
+int of3d_quiver_sample(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32, int rel_f64,
+                       int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                       double tscale, const int64_t* rois, int n_roi, const int64_t* gap3, const int64_t* capacity,
+                       const uint16_t* d_keep /* NULL: rel > *d_thresh */, void* d_result, void* workspace,
+                       void* stream);
+
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order
  * x2 y2 z2 xy xz yz (calc_flow.py:352-354's matrix (x2 xy xz / xy y2 yz /

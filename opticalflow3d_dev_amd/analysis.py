@@ -467,6 +467,108 @@ class _WhistCall(_BoxCall):
         return out
 
 
+@dataclasses.dataclass
+class QuiverSpec:
+    """The vectors of a quiver plot of every ROI, asked of quiver_sample / FlowStream(quiver=) /
+    process_flow(quiver=): what the figure scripts hand to quiver / quiver3
+    (plot_figure4_Movies.m:121-143: every gap-th voxel of the ROI whose masked velocity is not NaN).
+
+    gap: an int (every axis), or (gz, gy, gx) — (gy, gx) in 2D — each >= 1; the lattice is
+    anchored at each ROI's origin.  max_vectors: the records kept per ROI at most (the first ones
+    in C order; n_valid still counts all of them), >= 0."""
+    gap: object = 2
+    max_vectors: int = 65536
+
+    def resolve(self, ndim):
+        """Validated ((gz, gy, gx), max_vectors) for an ndim-D volume (2D: gz = 1); ValueError on
+        a bad value."""
+        is_int = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        g = self.gap
+        if is_int(g):
+            g = (g,) * ndim
+        else:
+            try:
+                g = tuple(g)
+            except TypeError:
+                raise ValueError(f"quiver: gap {self.gap!r} is not an integer or {ndim} integers") from None
+        if len(g) != ndim or not all(is_int(v) for v in g):
+            raise ValueError(f"quiver: gap {self.gap!r} is not an integer or {ndim} integers for a {ndim}D volume")
+        if min(g) < 1:
+            raise ValueError(f"quiver: gap {self.gap!r} must be at least 1 on every axis")
+        m = self.max_vectors
+        if not is_int(m) or m < 0:
+            raise ValueError(f"quiver: max_vectors {m!r} is not a non-negative integer")
+        g = tuple(int(v) for v in g)
+        return (g if ndim == 3 else (1,) + g), int(m)
+
+
+def _quiver_entry(zyx, v, ndim, n_lattice, n_valid):
+    """One ROI's entry of a quiver sample from its stored volume coordinates (int64 (n, 3)) and
+    physical velocities (float64 (n, 3)): with them magnitude, theta and (3D) phi, formed here on
+    the host with example_analysis_script.ipynb cell 6's expressions."""
+    vx, vy, vz = v[:, 0], v[:, 1], v[:, 2]
+    out = {"zyx": zyx, "v": v, "n_lattice": int(n_lattice), "n_valid": int(n_valid),
+           "truncated": int(n_valid) > len(zyx)}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if ndim == 3:
+            out["magnitude"] = np.sqrt(np.power(vx, 2) + np.power(vy, 2) + np.power(vz, 2))
+            out["phi"] = np.arctan(vz / np.sqrt(np.power(vx, 2) + np.power(vy, 2)))
+        else:
+            out["magnitude"] = np.sqrt(np.power(vx, 2) + np.power(vy, 2))
+        out["theta"] = np.arctan2(vy, vx)
+    return out
+
+
+class _QuiverCall(_BoxCall):
+    """of3d_quiver_sample bound to boxes and a device: the capacities, sizes, the workspace and
+    the decoding."""
+
+    def __init__(self, boxes, dims, rel_f64, quiver, ndim, scales, device):
+        super().__init__(boxes, dims, rel_f64)
+        self.ndim = int(ndim)
+        self.gap, self.max_vectors = quiver.resolve(self.ndim)
+        self.scales = tuple(float(v) for v in scales)
+        ext = self.boxes[:, 1::2] - self.boxes[:, 0::2]
+        self.n_lattice = np.prod((ext - 1) // np.array(self.gap, dtype=np.int64) + 1, axis=1).astype(np.int64)
+        self.capacity = np.ascontiguousarray(np.minimum(self.n_lattice, self.max_vectors), dtype=np.int64)
+        I = ctypes.POINTER(ctypes.c_int64)
+        self.gap_arr = (ctypes.c_int64 * 3)(*self.gap)
+        self.cap_arr = self.capacity.ctypes.data_as(I)
+        self.ws = self._workspace(self.lib.of3d_quiver_workspace_bytes(self.roi_arr, len(self.boxes), self.gap_arr),
+                                  device)
+        self.result_bytes = self.lib.of3d_quiver_result_bytes(len(self.boxes), self.cap_arr)
+        if self.result_bytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+
+    def new_result(self, device):
+        import torch
+
+        return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
+
+    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+        """The count, scan and emit kernels on `stream` (device pointers)."""
+        _lib.check(self.lib.of3d_quiver_sample(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
+                                               thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
+                                               self.gap_arr, self.cap_arr, keep_ptr or None, result_ptr,
+                                               self.ws.data_ptr(), stream or None))
+
+    def decode(self, words):
+        """The result words (host int64 array) as the per-ROI list of quiver_sample."""
+        words = np.ascontiguousarray(words, dtype=np.int64)
+        n_roi = len(self.boxes)
+        assert words[1] == n_roi and tuple(words[2:5]) == self.gap and words[5] == (self.ndim == 3), words[:6]
+        out = []
+        for r in range(n_roi):
+            n_lattice, n_valid, n_stored, off = (int(v) for v in words[6 + 4 * r:10 + 4 * r])
+            cap = int(self.capacity[r])
+            assert n_lattice == self.n_lattice[r] and n_stored == min(n_valid, cap), (r, n_lattice, n_valid, n_stored)
+            block = words[off:off + 4 * cap].reshape(4, cap)
+            v = np.ascontiguousarray(block[1:, :n_stored].T).view(np.float64)
+            zyx = np.stack(np.unravel_index(block[0, :n_stored], self.dims), axis=1).astype(np.int64).reshape(-1, 3)
+            out.append(_quiver_entry(zyx, v, self.ndim, n_lattice, n_valid))
+        return out
+
+
 def _pair_options(floor, combine):
     """Validated (floor, combine code) of the joint mask; ValueError on a bad value."""
     if not isinstance(combine, str) or combine not in COMBINE:
@@ -579,13 +681,17 @@ class _PairCall(_BoxCall):
 
 
 class _SummaryCall(_BoxCall):
-    """One resolved spec bound to a device: sizes, workspaces and the kernel launches."""
+    """One resolved spec bound to a device: sizes, workspaces and the kernel launches.  quiver
+    (a QuiverSpec): also of3d_quiver_sample over the same boxes, threshold and opened mask, into
+    a result block of its own (self.quiver: the _QuiverCall; enqueue's quiver_ptr)."""
 
-    def __init__(self, spec, shape, rel_dtype, device):
+    def __init__(self, spec, shape, rel_dtype, device, quiver=None):
         import torch
 
         self.spec, self.shape = spec, tuple(int(v) for v in shape)
         boxes, nbins, edges = spec.resolve(shape)
+        if quiver is not None:
+            quiver.resolve(len(self.shape))  # a bad request fails before anything is allocated
         self.min_size, self.connectivity = spec.opening(len(self.shape))
         super().__init__(boxes, self.shape if len(self.shape) == 3 else (1,) + self.shape,
                          rel_dtype == torch.float64)
@@ -608,6 +714,10 @@ class _SummaryCall(_BoxCall):
             self.whist = _WhistCall(self.boxes, self.dims, self.rel_f64, wnbins, wedges,
                                     (spec.xyscale, spec.zscale, spec.tscale), device)
             self.result_bytes += self.whist.result_bytes
+        self.quiver = None
+        if quiver is not None:
+            self.quiver = _QuiverCall(self.boxes, self.dims, self.rel_f64, quiver, len(self.shape),
+                                      (spec.xyscale, spec.zscale, spec.tscale), device)
         self.open =_OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
                               device) if self.min_size else None
         self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
@@ -621,8 +731,11 @@ class _SummaryCall(_BoxCall):
 
         return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
 
-    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream):
-        """Quantile + summary kernels on `stream` (device pointers; vz 0/None for 2D)."""
+    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream, quiver_ptr=None):
+        """Quantile + summary kernels on `stream` (device pointers; vz 0/None for 2D); with a
+        quiver request, its kernels after them into the block at quiver_ptr."""
+        if (self.quiver is None) != (quiver_ptr is None):
+            raise ValueError("summary: quiver_ptr goes with a quiver request, and only with one")
         lo, hi, gamma = self.ranks
         lib, s = self.lib, self.spec
         _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), self.thresh.data_ptr(),
@@ -643,6 +756,9 @@ class _SummaryCall(_BoxCall):
             self.whist.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
                                self.open.keep.data_ptr() if self.open is not None else None,
                                result_ptr + self.whist_off, stream)
+        if self.quiver is not None:
+            self.quiver.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+                                self.open.keep.data_ptr() if self.open is not None else None, quiver_ptr, stream)
 
     def decode(self, words):
         """The result words (host int64 array) as flow_summary's dict."""
@@ -951,6 +1067,113 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
                  tx.dtype == torch.float32, res.data_ptr(), torch.cuda.current_stream(tx.device).cuda_stream)
     return call.decode(res.cpu().numpy())
+
+
+# ---------------------------------------------------------------------------
+# Quiver samples (csrc/kt_quiver.hip): the vector lists the figure scripts hand to quiver /
+# quiver3 (example_analysis_script.m:64-66,121-135, plot_figure4_Movies.m:121-143,
+# plot_figure5.m:119-156, plot_FigureS2_dt.m:99-143, plot_figure3_ChannelCompare.m:181) —
+# every gap-th voxel of a ROI whose masked velocity is not NaN — compacted on the device in C
+# order, so that a series run with save_fields=False can still be drawn.  Rendering stays with
+# the caller.
+# ---------------------------------------------------------------------------
+def quiver_sample(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, gap=2, rois=None,
+                  min_size=0, connectivity=None, threshold=None, max_vectors=65536, device=None):
+    """The quiver vectors of one frame, per ROI: the voxels of the gap lattice
+    ``[z0:z1:gz, y0:y1:gy, x0:x1:gx]`` of every ROI whose masked physical velocity is not NaN
+    (flow_summary's validity), in C order, by of3d_quiver_sample; only the lists leave the device.
+
+    Inputs, scales, rois, min_size and connectivity as flow_summary (numpy arrays or torch
+    tensors, vz None for 2D; ROI 0 is the whole volume); gap and max_vectors as QuiverSpec.  The
+    threshold is the rel_percentile-th percentile of rel (percentile_threshold_device) unless
+    `threshold` (a Python float, used as one element of rel's dtype) is given; min_size >= 1
+    opens every ROI's mask first (reliability_mask).
+    Returns a dict: threshold, rois (n_roi, 6), gap (gz, gy, gx) and samples, a list with one
+    dict per ROI: zyx (int64 (n, 3), volume coordinates; z = 0 in 2D), v (float64 (n, 3): vx,
+    vy, vz in physical units, vz 0.0 in 2D), magnitude, theta and (3D) phi (float64 (n,), formed
+    on the host from v with the notebook's expressions), n_lattice, n_valid (the full count) and
+    truncated (n_valid > n = min(n_valid, n_lattice, max_vectors): only the first n in C order
+    are held).  For each field f in physical units, v's column equals
+    ``f[z0:z1:gz, y0:y1:gy, x0:x1:gx][valid]`` bit for bit.
+    Bit-reproducible: the same inputs give the same bits, in the same order, on every run."""
+    import torch
+
+    host = isinstance(vx, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    shape = tuple(int(v) for v in vx.shape)
+    if len(shape) != (3 if vz is not None else 2):
+        raise ValueError("quiver_sample needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+    spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
+    boxes = spec.resolve(shape)[0]
+    min_size, connectivity = spec.opening(len(shape))
+    request = QuiverSpec(gap=gap, max_vectors=max_vectors)
+    request.resolve(len(shape))
+    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
+    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
+    dims = shape if len(shape) == 3 else (1,) + shape
+    rel_f64 = tr.dtype == torch.float64
+    call = _QuiverCall(boxes, dims, rel_f64, request, len(shape), (xyscale, zscale, tscale), tx.device)
+    opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tx.device) if min_size else None
+    with torch.cuda.device(tx.device):
+        stream = torch.cuda.current_stream(tx.device).cuda_stream
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
+        if opening is not None:
+            counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tx.device)
+            opening.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(), stream)
+        res = call.new_result(tx.device)
+        call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
+                     tx.dtype == torch.float32, thresh.data_ptr(),
+                     opening.keep.data_ptr() if opening is not None else None, res.data_ptr(), stream)
+        words = res.cpu().numpy()
+    return {"threshold": _np_dtype(tr).type(words[:1].view(np.float64)[0]), "rois": boxes.copy(),
+            "gap": call.gap, "samples": call.decode(words)}
+
+
+_SPLIT_COLUMNS = {"vx": 0, "vy": 1, "vz": 2}
+
+
+def quiver_split(sample, quantity, edges):
+    """The figure scripts' colour slices of one ROI's quiver sample (plot_figure4_Movies.m:132-142:
+    one quiver call per slice ``(c >= e(j)) & (c < e(j+1))``): a list of len(edges) - 1 index
+    arrays into the sample's records.  quantity: "vx" | "vy" | "vz" | "magnitude" | "theta" |
+    "phi"; edges: ascending, left-closed slices, so a last edge of inf takes everything from the
+    edge before it.  Host only."""
+    if quantity in _SPLIT_COLUMNS:
+        c = np.asarray(sample["v"])[:, _SPLIT_COLUMNS[quantity]]
+    elif quantity in ("magnitude", "theta", "phi") and quantity in sample:
+        c = np.asarray(sample[quantity])
+    else:
+        raise ValueError(f"quiver: unknown quantity {quantity!r} of this sample (one of {QUANTITIES})")
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim != 1 or e.size < 2 or np.any(np.isnan(e)) or not np.all(e[1:] >= e[:-1]):
+        raise ValueError("quiver: edges must be a 1-D ascending array of at least 2 values without NaN")
+    return [np.flatnonzero((c >= e[j]) & (c < e[j + 1])) for j in range(e.size - 1)]
+
+
+def write_quiver(path, sample):
+    """One frame's quiver sample (quiver_sample's dict) as an npz: gap (int64 (3,)), rois,
+    threshold and per ROI r zyx_<r>, v_<r>, n_valid_<r>, n_lattice_<r>; the derived quantities are
+    not stored (read_quiver forms them again)."""
+    arrays = {"gap": np.asarray(sample["gap"], dtype=np.int64), "rois": np.asarray(sample["rois"], dtype=np.int64),
+              "threshold": np.asarray(sample["threshold"])}
+    for r, s in enumerate(sample["samples"]):
+        arrays[f"zyx_{r}"] = np.asarray(s["zyx"], dtype=np.int64).reshape(-1, 3)
+        arrays[f"v_{r}"] = np.asarray(s["v"], dtype=np.float64).reshape(-1, 3)
+        arrays[f"n_valid_{r}"] = np.int64(s["n_valid"])
+        arrays[f"n_lattice_{r}"] = np.int64(s["n_lattice"])
+    np.savez(path, **arrays)
+
+
+def read_quiver(path, ndim=3):
+    """write_quiver's file as quiver_sample's dict (ndim 2: no phi, a 2-term magnitude)."""
+    with np.load(path) as f:
+        rois = f["rois"]
+        out = {"threshold": f["threshold"][()], "rois": rois, "gap": tuple(int(v) for v in f["gap"]), "samples": []}
+        for r in range(len(rois)):
+            out["samples"].append(_quiver_entry(f[f"zyx_{r}"], f[f"v_{r}"], ndim, f[f"n_lattice_{r}"],
+                                                f[f"n_valid_{r}"]))
+    return out
 
 
 CSV_COLUMNS = ("frame", "roi", "z0", "z1", "y0", "y1", "x0", "x1", "threshold", "n_valid", "n_voxels",

@@ -186,7 +186,8 @@ def _dist_context():
 
 
 def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSig=3, tSig=1, wSig=4,
-                 precision="fp64", matlab_output=False, parallel="auto", summary=None, save_fields=True):
+                 precision="fp64", matlab_output=False, parallel="auto", summary=None, save_fields=True,
+                 quiver=None):
     """Parse a TIFF time lapse, run the flow per output frame, write TIFFs.
 
     Mirrors calc_flow.py:362-625: same checks and messages, the same
@@ -209,9 +210,13 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     projected onto them (analysis.CSV_AXES_COLUMNS; counts_axis* / edges_axis* in the npz).  A
     spec with weighted_bins adds the magnitude-weighted histograms to the npz (wedges_<name>,
     weights_<name> float64 of shape (frames, n_roi, nbins)); the CSV is unchanged.  The
-    stdout lines are the same in every mode.  Single process, device-ring path only: with
-    several ranks, or a window that differs from the temporal taps, a summary raises
-    ValueError.
+    stdout lines are the same in every mode.  quiver=analysis.QuiverSpec (needs a summary): the
+    quiver vectors of every ROI — every gap-th voxel with a non-NaN masked velocity, the
+    summary's mask — are compacted on the device (analysis.quiver_sample) and written per saved
+    frame as ``<imNameSave>_quiver_t%04d.npz`` (gap, rois, threshold and per ROI r zyx_<r>, v_<r>,
+    n_valid_<r>, n_lattice_<r>: analysis.write_quiver); without it no file differs.  Single
+    process, device-ring path only: with several ranks, or a window that differs from the
+    temporal taps, a summary raises ValueError.
 
     Several GPUs (one process per GPU, torch.distributed initialised, e.g. by
     ``shard.init_distributed()`` under torchrun): the reference's own parallel axis
@@ -277,6 +282,8 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     rank, world = _dist_context()
     if not save_fields and summary is None:
         raise ValueError("save_fields=False needs a summary")
+    if quiver is not None and summary is None:
+        raise ValueError("quiver needs a summary")
     if summary is not None and world > 1:
         raise ValueError("summary: sharded summaries (several ranks) are not supported")
     if summary is not None and NtChunk != 2 * math.ceil(3 * tSig) + 1:
@@ -354,7 +361,7 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
         h0, h1 = frame_blocks(nOut, rank, world) if nOut > 0 else (0, 0)
         if h1 > h0 and NtChunk == 2 * rt + 1:
             _process_stream(load_frame, (h0, h1), NtChunk, NtSlice, spatialDimensions, xyzSig, tSig, wSig, prefix,
-                            names, precision, writer, summary=summary, save_fields=save_fields)
+                            names, precision, writer, summary=summary, save_fields=save_fields, quiver=quiver)
         else:  # window and temporal taps disagree (non-integer 6*tSig+1): one upload per window
             for hh in range(h0, h1):
                 loopStart = datetime.now()
@@ -401,14 +408,15 @@ class _Shape:
 
 
 def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig, wSig, prefix, names,
-                    precision="fp64", write_fn=None, summary=None, save_fields=True):
+                    precision="fp64", write_fn=None, summary=None, save_fields=True, quiver=None):
     """process_flow's loop on a device-resident frame ring (stream.py): one
     frame read + upload per output frame; compute, download and TIFF writing
     of consecutive frames overlap.  Files and stdout lines are the reference's
     (both lines of a frame are printed once its files are written).
     out_range = (h0, h1): the windows starting at frames h0 .. h1 - 1 (a rank's block).
     summary (a SummarySpec): each frame's device-side summary is collected and written as
-    <prefix>_summary.csv / _summary_hist.npz at the end; save_fields=False: no TIFFs."""
+    <prefix>_summary.csv / _summary_hist.npz at the end; save_fields=False: no TIFFs.  quiver (a
+    QuiverSpec): each frame's quiver vectors are written as <prefix>_quiver_t%04d.npz."""
     from concurrent.futures import ThreadPoolExecutor
 
     from .stream import FlowStream, Writer
@@ -420,7 +428,7 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
         _check_args(_Shape((NtChunk,) + first.shape), ndim + 1, tSig, MSG_NDIM_3D if ndim == 3 else MSG_NDIM_2D)
     dt = first.dtype.newbyteorder('=') if first.dtype.byteorder not in ('=', '|') else first.dtype
     fs = FlowStream(ndim, first.shape, dt, xyzSig, tSig, wSig, precision=precision,
-                    rel_fp64=write_fn is not None and ndim == 3, summary=summary, fields=save_fields)
+                    rel_fp64=write_fn is not None and ndim == 3, summary=summary, fields=save_fields, quiver=quiver)
     frames, summaries = [], []
 
     def finish(frame, start, start_str, pending):
@@ -429,6 +437,13 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
             if summary is not None:
                 frames.append(frame)
                 summaries.append(pending.summary())
+            if quiver is not None:
+                from .analysis import write_quiver
+
+                s = summaries[-1]
+                write_quiver(prefix + '_quiver_t' + str(frame).zfill(4) + '.npz',
+                             {"threshold": s["threshold"], "rois": s["rois"], "gap": fs.summary.quiver.gap,
+                              "samples": pending.quiver()})
             if save_fields:
                 _write_frame(prefix, names, frame, pending.result(), pool, write_fn)
         finally:
