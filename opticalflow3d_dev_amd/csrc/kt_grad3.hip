@@ -1,6 +1,9 @@
 // kt_grad3.hip — K12 (fused gradient y/x/z passes) instances and their getter (kernels.hpp).
-#include "of3d_dev.hpp"
+#include <cstdint>
+
+#include "../../include/of3d.h"
 #include "kernels.hpp"
+#include "of3d_k12.hpp"
 
 namespace of3dk {
 

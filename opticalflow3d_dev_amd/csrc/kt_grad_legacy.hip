@@ -1,6 +1,10 @@
 // kt_grad_legacy.hip — kernel instances and their getters (see kernels.hpp).
-#include "of3d_dev.hpp"
+#include <cstdint>
+
+#include "../../include/of3d.h"
 #include "kernels.hpp"
+#include "of3d_grad.hpp"
+#include "of3d_k0.hpp"
 
 namespace of3dk {
 

@@ -1,6 +1,6 @@
 // kt_prod_legacy.hip — kernel instances and their getters (see kernels.hpp).
-#include "of3d_dev.hpp"
 #include "kernels.hpp"
+#include "of3d_k34.hpp"
 
 namespace of3dk {
 

@@ -1,6 +1,6 @@
 // kt_solve_legacy.hip — kernel instances and their getters (see kernels.hpp).
-#include "of3d_dev.hpp"
 #include "kernels.hpp"
+#include "of3d_k5.hpp"
 
 namespace of3dk {
 

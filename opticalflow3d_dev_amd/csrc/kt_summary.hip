@@ -210,7 +210,7 @@ int quantile_launch(const void* a, int64_t n, int64_t lo, int64_t hi, double gam
 // ---------------------------------------------------------------------------
 // Frame summary.  Grid (kSumMaxBlocks, n_roi); workgroup b of a box walks rows
 // [b*R/nb, (b+1)*R/nb) of the box's R = dz*dy rows, nb = a function of the box size alone.
-// Per voxel k_flow_stats' arithmetic (of3d_dev.hpp); sums in registers, a fixed shuffle tree
+// Per voxel k_flow_stats' arithmetic (of3d_general.hpp); sums in registers, a fixed shuffle tree
 // over the lanes, the waves' partials added in wave order, one workspace slot per workgroup;
 // k_sum_final adds a box's slots in index order.  Counts and histograms: LDS integer atomics,
 // then 64-bit integer atomics into the (zeroed) result.  No floating-point atomics: the same

@@ -1,11 +1,53 @@
 // of3d_host.hip — host side of libof3d: plans, the stage pipeline, the C-ABI (include/of3d.h).
-// Device code: of3d_dev.hpp; kernel instances behind getters in kt_*.hip (kernels.hpp).
-#include "of3d_dev.hpp"
+// Device code: the family headers of3d_*.hpp (this unit launches kernels or computes geometry of
+// every family); kernel instances behind getters in kt_*.hip (kernels.hpp).
+#include <hip/hip_runtime.h>
+#include <hsa/hsa.h>
+#include <hsa/hsa_ext_amd.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <tuple>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "../../include/of3d.h"
 #include "kernels.hpp"
+#include "of3d_common.hpp"
+#include "of3d_general.hpp"
+#include "of3d_grad.hpp"
+#include "of3d_k0.hpp"
+#include "of3d_k12.hpp"
+#include "of3d_k34.hpp"
+#include "of3d_k5.hpp"
+#include "of3d_solve.hpp"
 
 namespace {
 
 using namespace of3dk;
+
+// of3d_last_error's message: the library's only copy (other units record through of3dk::set_error)
+thread_local std::string g_err;
+
+int fail(const std::string& msg) {
+    g_err = msg;
+    return -1;
+}
+
+#define OF3D_HIP(call)                                                                    \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
 
 
 // ---------------------------------------------------------------------------
@@ -170,7 +212,7 @@ struct of3d_plan {
     size_t k5c_lds = 0;
     int k5c_r = 8;  // planes per z-group (8: 64-plane blocks, 2 per CU; 4: 32-plane blocks, 3 per CU)
     const void* k5c_next = nullptr;  // K5c that also forms the next frame's dt0 (frame pipelining)
-    // W-xy hand-off layout (K34 -> K5c, csrc/of3d_dev.hpp wxy_rsrc): 0 plain planes, else z-tiled
+    // W-xy hand-off layout (K34 -> K5c, csrc/of3d_k34.hpp wxy_rsrc): 0 plain planes, else z-tiled
     // [y][x / 32][z][32] with this many planes (cap_planes)
     int wxy_zt = 0;
     // frame pipelining (of3d_plan_execute_next): the dt0 a previous call formed for these frames
@@ -1067,7 +1109,7 @@ int run_t(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0
         if (q1 <= q0) return 0;
         const int ng = (int)(q1 - q0);
         const size_t o = (size_t)(q0 - R.zg0) * plane;
-        // (z-tiled W-xy: plane q0 starts 32 elements per plane in, csrc/of3d_dev.hpp wxy_rsrc)
+        // (z-tiled W-xy: plane q0 starts 32 elements per plane in, csrc/of3d_k34.hpp wxy_rsrc)
         const size_t op = p->wxy_zt ? (size_t)(q0 - R.zg0) * 32 : o;
         OF3D_HIP(launch_k34(p->k34, Gb + o, Pb + op, ng, nf, ny, nx, fs, tp.w, st, p->wxy_zt, (int)p->ya, (int)p->yb));
         p->used |= p->k34.nthr ? (p->k34.nthr == p->k34.cw ? KU_K34PK : KU_K34WS) : KU_K34;
@@ -1244,7 +1286,7 @@ int run(of3d_plan* p, const void* const* d_frames, int dtype, int64_t frame_z0, 
 void plan_free(of3d_plan* p);
 
 // The z-tiled W-xy layout addresses a K34 tile of S rows through ONE buffer descriptor with 32-bit
-// byte offsets (csrc/of3d_dev.hpp wxy_rsrc / wxy_off): S * nx * cap_planes elements must stay below
+// byte offsets (csrc/of3d_k34.hpp wxy_rsrc / wxy_off): S * nx * cap_planes elements must stay below
 // 2^31 bytes for the largest S of any K34 candidate the autotune may pick (an fp64 plan
 // of nz = nx = 4096, ny = 64 would span 2 GiB per 16-row tile, and stores past it are dropped by the
 // descriptor's range check without an error).  Plans past it keep the plain planes.

@@ -1,4 +1,4 @@
-"""The device's smallest-eigenvalue formula (csrc/of3d_dev.hpp eigmin3 / eigmin3_deflate),
+"""The device's smallest-eigenvalue formula (csrc/of3d_solve.hpp eigmin3 / eigmin3_deflate),
 restated in numpy by tools/eig_poly.py, against fp64 eigvalsh — CPU only.
 
 3D rel is LAPACK cgeev in complex64 in the reference (calc_flow.py:352-357) and double

@@ -213,7 +213,7 @@ def test_c3_fp32_plans_vs_oracle_and_candidates(c3):
 def test_more_than_64_planes_small_xy_vs_oracle(variant):
     """13 x 200 x 41 x 48 (sigma 2, tau 2, omega 5): four K5c z chunks, and a block grid whose
     size is not a multiple of 8 z-chunk sets, so the XCD remap's tail branch runs
-    (csrc/of3d_dev.hpp k5c_block); the whole volume against the oracle."""
+    (csrc/of3d_k5.hpp k5c_block); the whole volume against the oracle."""
     import torch
 
     img = np.random.default_rng(64).integers(0, 4096, size=(13, 200, 41, 48)).astype(np.uint16)

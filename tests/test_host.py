@@ -223,7 +223,7 @@ def test_percentile_threshold_matches_numpy(dtype):
 
 
 def test_eigenvalue_polynomial_pinned_to_its_generator():
-    """The device eigenvalue's cos((2/3) acos u) polynomial (csrc/of3d_dev.hpp,
+    """The device eigenvalue's cos((2/3) acos u) polynomial (csrc/of3d_solve.hpp,
     cos_two_thirds_acos) carries exactly the coefficients tools/eig_poly.py fits, its error is
     at fp64 rounding level, and the eigenvalue formula built on it matches the acos form it
     replaced against eigvalsh (both limited by the r ~ 1 square-root conditioning)."""
@@ -234,7 +234,7 @@ def test_eigenvalue_polynomial_pinned_to_its_generator():
     sys.path.insert(0, os.path.join(root, "tools"))
     import eig_poly
 
-    src = open(os.path.join(root, "opticalflow3d_dev_amd", "csrc", "of3d_dev.hpp")).read()
+    src = open(os.path.join(root, "opticalflow3d_dev_amd", "csrc", "of3d_solve.hpp")).read()
     body = src[src.index("double cos_two_thirds_acos(double u)"):]
     body = body[:body.index("\n}\n")]
     lits = [float(x) for x in re.findall(r"fma_sk\((?:c|-?[0-9.e+-]+), t, (-?[0-9.e+-]+)\)", body)]

@@ -1,5 +1,5 @@
 """Coefficients of cos((2/3) acos(u)) on u in [0, 1] as a polynomial in t = 2u - 1 (the
-eigenvalue's trigonometric step in csrc/of3d_dev.hpp: cos_two_thirds_acos), and a check of
+eigenvalue's trigonometric step in csrc/of3d_solve.hpp: cos_two_thirds_acos), and a check of
 the eigenvalue formula that uses it against the acos form and numpy's eigvalsh.
 
     python tools/eig_poly.py          # prints the coefficients and the comparison
@@ -26,7 +26,7 @@ def horner(m, t):
 
 
 def deflate(aq, bq, cq, d, e, f, w):
-    """csrc/of3d_dev.hpp eigmin3_deflate: the smaller eigenvalue of the near-degenerate pair of
+    """csrc/of3d_solve.hpp eigmin3_deflate: the smaller eigenvalue of the near-degenerate pair of
     B = (T - qI) / p from the 2x2 block on the plane orthogonal to lambda_max's eigenvector
     (scaled: entries O(1) whatever the tensor's magnitude; the caller multiplies by p)."""
     mu = 2 * (1 - (2 / 9) * w)

@@ -1,4 +1,4 @@
-// Microbenchmark: the data movement of K5c (csrc/of3d_dev.hpp k_wz_solve_c) alone, for two
+// Microbenchmark: the data movement of K5c (csrc/of3d_k5.hpp k_wz_solve_c) alone, for two
 // layouts of the W-xy workspace, at configs[2] (c3) size: 9 fields of 128 x 512 x 512 fp64.
 //   plain : [field][z][y][x]            — a block's window row (32 columns) is 256 B, rows a plane apart
 //   tiled : [field][y][x / 32][z][32]   — a block's 106-plane window is one contiguous 26.5 KiB run
