@@ -345,6 +345,32 @@ int of3d_mask_open(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64
                    const int64_t* rois, int n_roi, int64_t min_size, int connectivity, uint16_t* d_keep,
                    int64_t* d_counts, void* workspace, void* stream);
 
+/* The largest connected component of the reliability mask on the device: what the reference's
+ * plot_figure2_movie.ipynb cell 1 does with
+ *   labels_mask = measure.label(relMask); regions.sort(key=lambda x: x.area, reverse=True)
+ * and zeroing every region but the first ("some cells have a small piece of another cell in the
+ * FOV").  Arguments, M_r, its components and the connectivities are of3d_mask_open's (26 and 8 are
+ * measure.label's full connectivity); there is no min_size, because the sizes are not known
+ * beforehand.  For every box r independently keep_r is the one component of M_r with the most
+ * voxels; among components of equal size the one with the smallest root, i.e. the one that holds
+ * the smallest linear index of the box — the lowest label of a raster-order labelling, which is
+ * what the script's stable sort keeps.  An empty M_r keeps nothing.
+ * d_keep and d_counts have of3d_mask_open's layout: bit r of one uint16 per voxel (cleared on the
+ * stream first), int64[n_roi][4] = n_mask, n_components, n_components_kept (0 or 1), n_kept; so
+ * d_keep feeds of3d_flow_summary_masked, of3d_mask_axes, of3d_flow_whist, of3d_quiver_sample and
+ * of3d_flow_contract unchanged.
+ * The init, merge and count phases are of3d_mask_open's kernels.  Then every root offers the key
+ * (size << 32) | (0xFFFFFFFF - root) to one 64-bit word of the box by an integer atomicMax — the
+ * maximum does not depend on the order of the offers — and a last phase sets bit r where the
+ * voxel's label is the winner.  A box has fewer than 2^32 - 1 voxels, so a size fits the key's
+ * upper half.  `workspace`: of3d_mask_largest_workspace_bytes(rois, n_roi) bytes — of3d_mask_open's
+ * plus one word per box; 0 for invalid boxes.  Enqueued on `stream`; no host synchronisation, no
+ * workgroup waits for another. */
+size_t of3d_mask_largest_workspace_bytes(const int64_t* rois, int n_roi);
+int of3d_mask_largest(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64_t nx, const void* d_thresh,
+                      const int64_t* rois, int n_roi, int connectivity, uint16_t* d_keep, int64_t* d_counts,
+                      void* workspace, void* stream);
+
 /* of3d_flow_summary with the mask factor of a voxel in box r taken from bit r of d_keep
  * (of3d_mask_open's output) instead of rel > *d_thresh: the figure scripts' statistics over the
  * opened mask.  Word 0 of the result is still *d_thresh; the result layout, the workgroup
@@ -583,6 +609,65 @@ int of3d_quiver_sample(const void* d_vx, const void* d_vy, const void* d_vz, con
                        double tscale, const int64_t* rois, int n_roi, const int64_t* gap3, const int64_t* capacity,
                        const uint16_t* d_keep /* NULL: rel > *d_thresh */, void* d_result, void* workspace,
                        void* stream);
+
+/* Contractility: the flow with respect to the centroid of the mask, on the device — the
+ * reference's figure 2 / movie S2 (plot_figure2_movie.ipynb cell 1: com = center_of_mass(relMask),
+ * normalc = -(pos - com) / |pos - com| in physical units, vnorm = v / |v|,
+ * degrees(arccos(vecdot(vnorm, normalc)))): 0 degrees is a velocity straight towards the centroid
+ * (contracting), 180 straight away from it.  Fields, d_rel, dtypes, dims, d_thresh, scales, rois
+ * and validity as of3d_flow_summary's; d_keep as of3d_flow_whist's (NULL: rel > *d_thresh; else bit
+ * r of d_keep for box r — of3d_mask_largest's output for the figure —, and d_rel / d_thresh may
+ * then be NULL).  2D: d_vz == NULL and nz == 1 (a d_vz with nz == 1 is an error); every z term is
+ * dropped.  For every box r independently:
+ *   1. the mask M_r of of3d_mask_axes step 1 (the mask, not the valid voxels) and its unsigned
+ *      64-bit sums n, Sx, Sy, Sz of the box-local integer coordinates, by of3d_mask_axes' own
+ *      moment pass; the centroid c = S / n in box-local index coordinates, one float64 division of
+ *      two integers exact in float64 — scipy.ndimage.center_of_mass of the integer mask, bit for
+ *      bit.  n == 0: NaN, and no voxel then has an angle.
+ *   2. the centre used: c, or center_given (host, 3 finite doubles x y z, box-local, the same for
+ *      every box; kernel arguments).  Step 1 is reported either way.  The centre is written into
+ *      the result on the device and read from there by the reduction, later on the same stream.
+ *   3. per valid voxel at box-local integer coordinates (kx, ky, kz), with (vx, vy, vz) its masked
+ *      physical velocity, plain multiplies and adds in this order (no FMA):
+ *        dx = kx*xyscale - c.x*xyscale   dy = ky*xyscale - c.y*xyscale   dz = kz*zscale - c.z*zscale
+ *        nd = sqrt((dx*dx + dy*dy) + dz*dz)      speed = sqrt((vx*vx + vy*vy) + vz*vz)
+ *        dot = ((vx/speed)*(-dx/nd) + (vy/speed)*(-dy/nd)) + (vz/speed)*(-dz/nd)
+ *        angle = acos(min(max(dot, -1), 1)) * (180/pi)          inward = speed * dot
+ *      inward is the physical velocity component towards the centre.  The voxel with nd == 0 (the
+ *      centre's own) has a NaN direction: it counts in n_valid, not in n_angle.
+ * Not reproduced of the notebook: numpy's arccos returns NaN where rounding leaves |dot| a last
+ * bit above 1; here dot is clamped first, so such a voxel has exactly 0 or 180 degrees (and
+ * counts in n_angle and the sums; dot itself is summed unclamped).
+ *
+ * Result (device, of3d_flow_contract_result_bytes(n_roi, nbins2) bytes, 8-byte words, zeroed on
+ * the stream first), per box OF3D_CONTRACT_ROI_WORDS + sum(nbins2) words:
+ *    0..3    uint64 n, Sx, Sy, Sz
+ *    4..6    float64 centroid x y z, box-local (add the box origin for volume coordinates)
+ *    7..9    float64 the centre used x y z, box-local
+ *   10..12   int64 n_valid, n_angle, n_inward (voxels with dot > 0)
+ *   13..16   float64 sums over the voxels with an angle: angle, dot, inward, speed
+ *   17..     uint64 histogram counts of angle (degrees), then inward (nbins2[q] words each;
+ *            np.histogram semantics, at most 256 bins, edges2: host double*[2]; all 0 is legal)
+ * Deterministic under of3d_flow_summary's contract: its workgroup partition and walk, the sums in
+ * registers, a fixed shuffle tree over the lanes, the waves in wave order into the workgroup's own
+ * workspace slot, a second kernel adding a box's slots in index order; counts and histograms by
+ * integer atomics; no floating-point atomic.  Equal inputs give equal bits on every run, and a
+ * box's words do not depend on the other boxes.
+ * `workspace`: device memory of of3d_flow_contract_workspace_bytes(rois, n_roi, nbins2) bytes (the
+ * moment pass's block and workspace, the edges, one slot of 4 float64 per workgroup of every
+ * box); host arithmetic only, 0 (and of3d_last_error's text) for an invalid box, more than 16
+ * boxes, more than 256 bins, a workgroup share of 2^31 voxels or more, or a box whose sums could
+ * pass 2^63 (of3d_mask_axes_workspace_bytes' rule).  Enqueued on `stream`; no host copy, no host
+ * synchronisation, no workgroup waits for another. */
+#define OF3D_CONTRACT_QUANTITIES 2 /* histograms: 0 angle, 1 inward */
+#define OF3D_CONTRACT_ROI_WORDS 17
+size_t of3d_flow_contract_result_bytes(int n_roi, const int* nbins2);
+size_t of3d_flow_contract_workspace_bytes(const int64_t* rois, int n_roi, const int* nbins2);
+int of3d_flow_contract(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32, int rel_f64,
+                       int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                       double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep,
+                       const double* center_given, const int* nbins2, const double* const* edges2, void* d_result,
+                       void* workspace, void* stream);
 
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order

@@ -6,8 +6,9 @@ Drop-in for the hot path of ScientistRachel/OpticalFlow3D_dev
 ``libof3d.so`` (C-ABI: include/of3d.h).
 """
 
-from .analysis import (QuiverSpec, SummarySpec, channel_compare, flow_statistics, flow_summary,  # noqa: F401
-                       joint_reliability_mask, percentile_threshold, percentile_threshold_device, principal_axes,
+from .analysis import (ContractSpec, QuiverSpec, SummarySpec, centroid_angle, channel_compare,  # noqa: F401
+                       contractility, flow_statistics, flow_summary, joint_reliability_mask,
+                       largest_component_mask, percentile_threshold, percentile_threshold_device, principal_axes,
                        quiver_sample, quiver_split, reliability_mask)
 from .calc_flow import calc_flow, calc_flow2D, calc_flow2D_fp32, calc_flow3D, calc_flow3D_fp32, process_flow  # noqa: F401
 from .taps import make_taps, radii  # noqa: F401
@@ -15,4 +16,5 @@ from .taps import make_taps, radii  # noqa: F401
 __all__ = ["calc_flow", "calc_flow2D", "calc_flow3D", "process_flow", "calc_flow2D_fp32", "calc_flow3D_fp32",
            "make_taps", "radii", "SummarySpec", "flow_statistics", "flow_summary", "percentile_threshold",
            "percentile_threshold_device", "reliability_mask", "principal_axes", "joint_reliability_mask",
-           "channel_compare", "QuiverSpec", "quiver_sample", "quiver_split"]
+           "channel_compare", "QuiverSpec", "quiver_sample", "quiver_split", "ContractSpec", "contractility",
+           "largest_component_mask", "centroid_angle"]

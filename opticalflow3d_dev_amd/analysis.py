@@ -153,6 +153,11 @@ PAIR_SUMS = ("sum_dot", "sum_cosine", "sum_mag0_mag1", "sum_mag0_sq", "sum_mag1_
              "sum_cos_dtheta", "sum_diff")
 _PAIR_HEAD = 26  # a box's result words before its histograms (include/of3d.h)
 COMBINE = {"or": 0, "and": 1}  # of3d_mask_open_pair's combine
+# of3d_flow_contract (csrc/kt_contract.hip): the flow against the direction to the mask's centroid
+# (figure 2 / movie S2, plot_figure2_movie.ipynb cell 1)
+CONTRACT_QUANTITIES = ("angle", "inward")
+CONTRACT_SUMS = ("sum_angle", "sum_dot", "sum_inward", "sum_speed")
+_CT_HEAD = 17  # a box's result words before its histograms (include/of3d.h)
 
 
 def percentile_threshold_device(rel, percentile, out=None):
@@ -569,6 +574,147 @@ class _QuiverCall(_BoxCall):
         return out
 
 
+@dataclasses.dataclass
+class ContractSpec:
+    """The contractility of every ROI, asked of contractility / FlowStream(contract=) /
+    process_flow(contract=): the centroid of the ROI's mask and, over its valid voxels, the angle
+    between the flow and the direction to that centroid (plot_figure2_movie.ipynb cell 1; 0
+    degrees: straight towards the centroid, 180: straight away).
+
+    mask: "largest" — the figure's route: rel > threshold, then the largest connected component
+    of every ROI's cropped mask (largest_component_mask) — or "summary": the mask the summary
+    itself reduces over (the threshold mask, or its opening when the SummarySpec has min_size >= 1).
+    connectivity ("largest" only): 6, 18 or 26 in 3D (default 26), 4 or 8 in 2D (default 8).
+    center: "mask" — every ROI's own centroid — or (x, y, z) ((x, y) in 2D) to measure from
+    instead, in each ROI's own index coordinates (the notebook's crop-local com: a centroid this
+    module reports, minus the ROI's origin), the same for every ROI; e.g. an earlier frame's, to
+    hold the centre still along a movie.  The mask's own centroid is reported either way.
+    bins: "angle" (degrees) and / or "inward" (the physical velocity component towards the
+    centre) -> ascending bin edges (at most 256 bins), np.histogram semantics."""
+    mask: str = "largest"
+    connectivity: int | None = None
+    center: object = "mask"
+    bins: dict | None = None
+
+    def resolve(self, ndim):
+        """Validated (mask, connectivity, given, nbins [2], edges [2 arrays or None]) for an
+        ndim-D volume: given = None for "mask" or the 3 float64 values x y z (z = 0 in 2D);
+        ValueError on a bad value."""
+        if self.mask not in ("largest", "summary"):
+            raise ValueError(f"contract: mask {self.mask!r} is not 'largest' or 'summary'")
+        allowed = CONNECTIVITIES[ndim]
+        c = allowed[-1] if self.connectivity is None else self.connectivity
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c not in allowed:
+            raise ValueError(f"contract: connectivity {c!r} is not one of {allowed} for a {ndim}D volume")
+        if self.mask == "summary" and self.connectivity is not None:
+            raise ValueError("contract: connectivity goes with mask='largest' (the summary's mask has its own)")
+        given = None
+        if isinstance(self.center, str):
+            if self.center != "mask":
+                raise ValueError(f"contract: center {self.center!r} is not 'mask' or {ndim} coordinates")
+        else:
+            try:
+                given = np.ascontiguousarray(self.center, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"contract: center {self.center!r} is not 'mask' or {ndim} coordinates") from None
+            if given.shape != (ndim,):
+                raise ValueError(f"contract: center must be {ndim} coordinates (x, y{', z' if ndim == 3 else ''}), "
+                                 f"got shape {given.shape}")
+            if not np.all(np.isfinite(given)):
+                raise ValueError("contract: center must be finite")
+            given = np.concatenate([given, np.zeros(3 - ndim)])
+        nbins, edges = [0] * 2, [None] * 2
+        for name, e in (self.bins or {}).items():
+            if name not in CONTRACT_QUANTITIES:
+                raise ValueError(f"contract: unknown histogram quantity {name!r} (one of {CONTRACT_QUANTITIES})")
+            q = CONTRACT_QUANTITIES.index(name)
+            edges[q] = SummarySpec._bin_edges(e, "contract " + name)
+            nbins[q] = edges[q].size - 1
+        return self.mask, int(c), given, nbins, edges
+
+
+class _LargestCall(_BoxCall):
+    """of3d_mask_largest bound to boxes and a device: the keep volume and the workspace,
+    allocated once."""
+
+    def __init__(self, boxes, dims, rel_f64, connectivity, device):
+        import torch
+
+        super().__init__(boxes, dims, rel_f64)
+        self.connectivity = int(connectivity)
+        self.ws = self._workspace(self.lib.of3d_mask_largest_workspace_bytes(self.roi_arr, len(self.boxes)), device)
+        self.keep = torch.empty(self.dims, dtype=torch.uint16, device=device)
+
+    def enqueue(self, rel, thresh_ptr, counts_ptr, stream):
+        _lib.check(self.lib.of3d_mask_largest(rel, self.rel_f64, *self.dims, thresh_ptr, self.roi_arr,
+                                              len(self.boxes), self.connectivity, self.keep.data_ptr(), counts_ptr,
+                                              self.ws.data_ptr(), stream or None))
+
+
+class _ContractCall(_BoxCall):
+    """of3d_flow_contract bound to boxes and a device, with of3d_mask_largest in front of it for
+    mask="largest": sizes, the workspaces and the decoding.  The result block: the contract
+    words, then ("largest") of3d_mask_largest's 4 counts per box."""
+
+    def __init__(self, boxes, dims, rel_f64, request, ndim, scales, device):
+        super().__init__(boxes, dims, rel_f64)
+        self.mask, connectivity, self.given, nbins, edges = request.resolve(int(ndim))
+        self._bind_bins(nbins, edges)
+        self.scales = tuple(float(v) for v in scales)
+        self.given_arr = (self.given.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+                          if self.given is not None else None)
+        self.ws = self._workspace(
+            self.lib.of3d_flow_contract_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr), device)
+        self.contract_bytes = self.lib.of3d_flow_contract_result_bytes(len(self.boxes), self.nb_arr)
+        self.largest = (_LargestCall(self.boxes, self.dims, self.rel_f64, connectivity, device)
+                        if self.mask == "largest" else None)
+        self.result_bytes = self.contract_bytes + (32 * len(self.boxes) if self.largest is not None else 0)
+
+    def new_result(self, device):
+        import torch
+
+        return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
+
+    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+        """("largest") the labelling and selection, then the moment, centre, reduction and final
+        kernels on `stream` (device pointers); keep_ptr: the summary's mask for mask="summary"."""
+        if self.largest is not None:
+            self.largest.enqueue(rel, thresh_ptr, result_ptr + self.contract_bytes, stream)
+            keep_ptr = self.largest.keep.data_ptr()
+        _lib.check(self.lib.of3d_flow_contract(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
+                                               thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
+                                               keep_ptr or None, self.given_arr, self.nb_arr, self.edge_arr,
+                                               result_ptr, self.ws.data_ptr(), stream or None))
+
+    def decode(self, words):
+        """The result words (host int64 array) as contractility's dict but for the threshold."""
+        words = np.ascontiguousarray(words, dtype=np.int64)
+        n_roi, ntot = len(self.boxes), sum(self.nbins)
+        body = words[:n_roi * (_CT_HEAD + ntot)].reshape(n_roi, _CT_HEAD + ntot)
+        f = lambda a, b: np.ascontiguousarray(body[:, a:b]).view(np.float64)
+        origin = self.boxes[:, [4, 2, 0]].astype(np.float64)  # x y z
+        out = {"rois": self.boxes.copy(), "moments": np.ascontiguousarray(body[:, :4]).view(np.uint64),
+               "centroid": origin + f(4, 7), "center_used": origin + f(7, 10),
+               "n_valid": body[:, 10].copy(), "n_angle": body[:, 11].copy(), "n_inward": body[:, 12].copy()}
+        if self.largest is not None:
+            counts = words[self.contract_bytes // 8:][:4 * n_roi].reshape(n_roi, 4)
+            out["n_mask"], out["n_components"], out["n_kept"] = (counts[:, i].copy() for i in (0, 1, 3))
+        else:  # no labelling of this request's own: the mask reduced over, as it came
+            out["n_mask"] = out["n_kept"] = body[:, 0].copy()
+            out["n_components"] = np.full(n_roi, -1, dtype=np.int64)
+        sums = f(13, 17)
+        na = out["n_angle"].astype(np.float64)
+        na[na == 0] = np.nan  # no voxel with an angle: NaN means, no division warnings
+        for i, k in enumerate(CONTRACT_SUMS):
+            out[k] = sums[:, i].copy()
+            out["mean_" + k[4:]] = sums[:, i] / na
+        out["inward_fraction"] = out["n_inward"] / na
+        out["hist"], out["edges"] = {}, {}
+        _decode_hists(body, _CT_HEAD, CONTRACT_QUANTITIES, self.nbins, self.edges, np.uint64, out["hist"],
+                      out["edges"])
+        return out
+
+
 def _pair_options(floor, combine):
     """Validated (floor, combine code) of the joint mask; ValueError on a bad value."""
     if not isinstance(combine, str) or combine not in COMBINE:
@@ -683,15 +829,19 @@ class _PairCall(_BoxCall):
 class _SummaryCall(_BoxCall):
     """One resolved spec bound to a device: sizes, workspaces and the kernel launches.  quiver
     (a QuiverSpec): also of3d_quiver_sample over the same boxes, threshold and opened mask, into
-    a result block of its own (self.quiver: the _QuiverCall; enqueue's quiver_ptr)."""
+    a result block of its own (self.quiver: the _QuiverCall; enqueue's quiver_ptr).  contract (a
+    ContractSpec): likewise of3d_flow_contract (self.contract: the _ContractCall; contract_ptr);
+    the quiver keeps the summary's mask whatever the contract's."""
 
-    def __init__(self, spec, shape, rel_dtype, device, quiver=None):
+    def __init__(self, spec, shape, rel_dtype, device, quiver=None, contract=None):
         import torch
 
         self.spec, self.shape = spec, tuple(int(v) for v in shape)
         boxes, nbins, edges = spec.resolve(shape)
         if quiver is not None:
             quiver.resolve(len(self.shape))  # a bad request fails before anything is allocated
+        if contract is not None:
+            contract.resolve(len(self.shape))
         self.min_size, self.connectivity = spec.opening(len(self.shape))
         super().__init__(boxes, self.shape if len(self.shape) == 3 else (1,) + self.shape,
                          rel_dtype == torch.float64)
@@ -718,6 +868,10 @@ class _SummaryCall(_BoxCall):
         if quiver is not None:
             self.quiver = _QuiverCall(self.boxes, self.dims, self.rel_f64, quiver, len(self.shape),
                                       (spec.xyscale, spec.zscale, spec.tscale), device)
+        self.contract = None
+        if contract is not None:
+            self.contract = _ContractCall(self.boxes, self.dims, self.rel_f64, contract, len(self.shape),
+                                          (spec.xyscale, spec.zscale, spec.tscale), device)
         self.open =_OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
                               device) if self.min_size else None
         self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
@@ -731,11 +885,14 @@ class _SummaryCall(_BoxCall):
 
         return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
 
-    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream, quiver_ptr=None):
+    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream, quiver_ptr=None, contract_ptr=None):
         """Quantile + summary kernels on `stream` (device pointers; vz 0/None for 2D); with a
-        quiver request, its kernels after them into the block at quiver_ptr."""
+        quiver request, its kernels after them into the block at quiver_ptr; with a contract
+        request, its kernels after those into the block at contract_ptr."""
         if (self.quiver is None) != (quiver_ptr is None):
             raise ValueError("summary: quiver_ptr goes with a quiver request, and only with one")
+        if (self.contract is None) != (contract_ptr is None):
+            raise ValueError("summary: contract_ptr goes with a contract request, and only with one")
         lo, hi, gamma = self.ranks
         lib, s = self.lib, self.spec
         _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), self.thresh.data_ptr(),
@@ -759,6 +916,10 @@ class _SummaryCall(_BoxCall):
         if self.quiver is not None:
             self.quiver.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
                                 self.open.keep.data_ptr() if self.open is not None else None, quiver_ptr, stream)
+        if self.contract is not None:
+            self.contract.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+                                  self.open.keep.data_ptr() if self.open is not None else None, contract_ptr,
+                                  stream)
 
     def decode(self, words):
         """The result words (host int64 array) as flow_summary's dict."""
@@ -1174,6 +1335,152 @@ def read_quiver(path, ndim=3):
             out["samples"].append(_quiver_entry(f[f"zyx_{r}"], f[f"v_{r}"], ndim, f[f"n_lattice_{r}"],
                                                 f[f"n_valid_{r}"]))
     return out
+
+
+# ---------------------------------------------------------------------------
+# Contractility (csrc/kt_contract.hip, csrc/kt_ccl.hip: of3d_mask_largest): figure 2 / movie S2
+# of the reference (plot_figure2_movie.ipynb cell 1) — the largest connected component of the
+# cropped reliability mask, its centre of mass, and per voxel the angle between the flow and the
+# direction to that centre — on the resident fields, so that a series run with
+# save_fields=False still yields the figure's distributions.
+# ---------------------------------------------------------------------------
+def largest_component_mask(rel, rel_percentile=90, threshold=None, connectivity=None, rois=None, device=None):
+    """The largest connected component of the reliability mask of one frame, per ROI: the
+    notebook's measure.label / sort by area / zero all but the first, on the device
+    (of3d_mask_largest).  Among components of equal size the one holding the smallest linear
+    index of the ROI is kept (the lowest label of a raster-order labelling, what the notebook's
+    stable sort keeps); an empty mask keeps nothing.
+
+    Arguments but min_size as reliability_mask's, and so is the returned dict: keep (uint16,
+    rel's shape; bit r set where the voxel lies in box r and in that box's largest component),
+    mask (r -> that bit plane as bool), rois, threshold and per ROI n_mask, n_components,
+    n_components_kept (0 or 1), n_kept (int64)."""
+    import torch
+
+    host = isinstance(rel, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    tr = _to_device(rel, host, dev)
+    if tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rel must be float32 or float64")
+    if tr.dim() not in (2, 3):
+        raise ValueError("largest_component_mask needs a (nz, ny, nx) or (ny, nx) field")
+    boxes = SummarySpec(rois=rois, rel_percentile=rel_percentile).resolve(tuple(tr.shape))[0]
+    connectivity = ContractSpec(connectivity=connectivity).resolve(tr.dim())[1]
+    dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
+    call = _LargestCall(boxes, dims, tr.dtype == torch.float64, connectivity, tr.device)
+    with torch.cuda.device(tr.device):
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
+        counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tr.device)
+        call.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(),
+                     torch.cuda.current_stream(tr.device).cuda_stream)
+        out = _mask_dict(call.keep.view(tr.shape), host, boxes, counts)
+        out["threshold"] = _np_dtype(tr).type(thresh.cpu().numpy()[0])
+    return out
+
+
+def contractility(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, spec=None,
+                  device=None):
+    """One frame's contractility per ROI (ROI 0 is the whole volume, `rois` follow), reduced on
+    the device to a few hundred bytes: the mask's centroid and, over the valid voxels (the masked
+    velocity's magnitude is not NaN, flow_summary's validity), the angle in degrees between the
+    physical velocity and the direction from the voxel to the centre, by of3d_flow_contract.
+
+    Inputs and scales as flow_summary (numpy arrays or torch tensors, vz None for 2D); spec: a
+    ContractSpec (default: the largest component, its own centroid, no histograms; mask="summary"
+    is the threshold mask here).  Returns a dict of numpy values: threshold, rois and per ROI
+    centroid and center_used (x y z, volume coordinates; NaN for an empty mask), moments (uint64
+    n, Sx, Sy, Sz of the mask in the ROI's own coordinates), n_mask, n_components, n_kept (the
+    labelling's counts; with mask="summary" n_mask = n_kept = the mask reduced over and
+    n_components = -1), n_valid, n_angle (the valid voxels with a direction: all but the centre's
+    own voxel), n_inward (cosine > 0), the raw sums sum_angle, sum_dot, sum_inward, sum_speed over
+    the voxels with an angle, mean_angle, mean_dot, mean_inward, mean_speed (formed here from the
+    sums; NaN where n_angle == 0), inward_fraction = n_inward / n_angle, and hist[name]
+    (n_roi, nbins) uint64 with edges[name] for every quantity in spec.bins.
+    A cosine that rounding left a last bit beyond +-1 gives exactly 0 or 180 degrees where the
+    notebook's arccos gives NaN.  Bit-reproducible: the same inputs give the same bits on every run."""
+    import torch
+
+    host = isinstance(vx, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    shape = tuple(int(v) for v in vx.shape)
+    if len(shape) != (3 if vz is not None else 2):
+        raise ValueError("contractility needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+    boxes = SummarySpec(rois=rois, rel_percentile=rel_percentile).resolve(shape)[0]
+    spec = ContractSpec() if spec is None else spec
+    spec.resolve(len(shape))
+    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
+    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
+    dims = shape if len(shape) == 3 else (1,) + shape
+    call = _ContractCall(boxes, dims, tr.dtype == torch.float64, spec, len(shape), (xyscale, zscale, tscale),
+                         tx.device)
+    with torch.cuda.device(tx.device):
+        stream = torch.cuda.current_stream(tx.device).cuda_stream
+        thresh = _thresholds_device([tr], rel_percentile, None)
+        res = call.new_result(tx.device)
+        call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
+                     tx.dtype == torch.float32, thresh.data_ptr(), None, res.data_ptr(), stream)
+        out = call.decode(res.cpu().numpy())
+        out["threshold"] = _np_dtype(tr).type(thresh.cpu().numpy()[0])
+    return out
+
+
+def centroid_angle(sample, center, xyscale, zscale):
+    """The movie's quiver colour: for the records of one ROI's quiver sample (an entry of
+    quiver_sample's ``samples``) the angle in degrees between each vector and the direction to
+    `center` (x, y, z in volume coordinates, e.g. contractility's center_used of that ROI; z is
+    ignored for a 2D sample), with the notebook's numpy expressions — NaN where arccos gives
+    NaN.  Host only: the lists are small."""
+    zyx = np.asarray(sample["zyx"], dtype=np.float64).reshape(-1, 3)
+    v = np.asarray(sample["v"], dtype=np.float64).reshape(-1, 3)
+    cx, cy, cz = (float(c) for c in center)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dxc = zyx[:, 2] * xyscale - cx * xyscale
+        dyc = zyx[:, 1] * xyscale - cy * xyscale
+        dzc = zyx[:, 0] * zscale - cz * zscale if "phi" in sample else np.zeros(len(zyx))
+        normalc = np.stack([-dxc, -dyc, -dzc], axis=-1)
+        normalc = normalc / np.linalg.norm(normalc, axis=-1, keepdims=True)
+        speed = np.sqrt(np.power(v[:, 0], 2) + np.power(v[:, 1], 2) + np.power(v[:, 2], 2))
+        vnorm = v / speed[:, None]
+        return np.degrees(np.arccos(np.sum(vnorm * normalc, axis=-1)))
+
+
+CONTRACT_CSV_INT_COLUMNS = ("frame", "roi", "z0", "z1", "y0", "y1", "x0", "x1", "n_mask", "n_components", "n_kept",
+                            "n_valid", "n_angle", "n_inward")
+CONTRACT_CSV_COLUMNS = CONTRACT_CSV_INT_COLUMNS + (
+    "centroid_x", "centroid_y", "centroid_z", "center_x", "center_y", "center_z", "mean_angle", "mean_dot",
+    "mean_inward", "mean_speed", "inward_fraction") + CONTRACT_SUMS
+
+
+def write_contract(prefix, frames, results):
+    """<prefix>_contract.csv (one row per frame and ROI, CONTRACT_CSV_COLUMNS; floats as repr, so
+    they read back exactly) and <prefix>_contract_hist.npz (frames, edges_<name>, counts_<name> of
+    shape (frames, n_roi, nbins)) from contractility dicts of consecutive frames."""
+    with open(prefix + "_contract.csv", "w", newline="") as f:
+        f.write(",".join(CONTRACT_CSV_COLUMNS) + "\n")
+        for frame, c in zip(frames, results):
+            for r in range(len(c["rois"])):
+                row = [int(frame), r] + [int(v) for v in c["rois"][r]]
+                row += [int(c[k][r]) for k in CONTRACT_CSV_INT_COLUMNS[8:]]
+                floats = list(c["centroid"][r]) + list(c["center_used"][r])
+                floats += [c[k][r] for k in CONTRACT_CSV_COLUMNS[len(CONTRACT_CSV_INT_COLUMNS) + 6:]]
+                f.write(",".join(str(v) for v in row + [repr(float(v)) for v in floats]) + "\n")
+    arrays = {"frames": np.asarray(list(frames), dtype=np.int64)}
+    if results:
+        for name, e in results[0]["edges"].items():
+            arrays["edges_" + name] = e
+            arrays["counts_" + name] = np.stack([c["hist"][name] for c in results])
+    np.savez(prefix + "_contract_hist.npz", **arrays)
+
+
+def read_contract_csv(path):
+    """The rows of a <prefix>_contract.csv as a dict of numpy columns (int64 / float64)."""
+    with open(path) as f:
+        cols = f.readline().strip().split(",")
+        rows = [line.strip().split(",") for line in f if line.strip()]
+    ints = set(CONTRACT_CSV_INT_COLUMNS)
+    return {c: np.array([int(r[i]) if c in ints else float(r[i]) for r in rows],
+                        dtype=np.int64 if c in ints else np.float64) for i, c in enumerate(cols)}
 
 
 CSV_COLUMNS = ("frame", "roi", "z0", "z1", "y0", "y1", "x0", "x1", "threshold", "n_valid", "n_voxels",

@@ -187,7 +187,7 @@ def _dist_context():
 
 def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSig=3, tSig=1, wSig=4,
                  precision="fp64", matlab_output=False, parallel="auto", summary=None, save_fields=True,
-                 quiver=None):
+                 quiver=None, contract=None):
     """Parse a TIFF time lapse, run the flow per output frame, write TIFFs.
 
     Mirrors calc_flow.py:362-625: same checks and messages, the same
@@ -214,7 +214,14 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     quiver vectors of every ROI — every gap-th voxel with a non-NaN masked velocity, the
     summary's mask — are compacted on the device (analysis.quiver_sample) and written per saved
     frame as ``<imNameSave>_quiver_t%04d.npz`` (gap, rois, threshold and per ROI r zyx_<r>, v_<r>,
-    n_valid_<r>, n_lattice_<r>: analysis.write_quiver); without it no file differs.  Single
+    n_valid_<r>, n_lattice_<r>: analysis.write_quiver); without it no file differs.
+    contract=analysis.ContractSpec (needs a summary): every saved frame's contractility — per ROI
+    the centroid of the mask (the largest component of the threshold mask, or the summary's mask)
+    and the angle of the flow to the direction of that centroid (analysis.contractility) — is
+    reduced on the device and written at the end as ``<imNameSave>_contract.csv`` (one row per
+    frame and ROI: analysis.CONTRACT_CSV_COLUMNS) and ``<imNameSave>_contract_hist.npz``
+    (analysis.write_contract); without it no file differs, and a quiver in the same call still
+    uses the summary's mask.  Single
     process, device-ring path only: with several ranks, or a window that differs from the
     temporal taps, a summary raises ValueError.
 
@@ -284,6 +291,8 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
         raise ValueError("save_fields=False needs a summary")
     if quiver is not None and summary is None:
         raise ValueError("quiver needs a summary")
+    if contract is not None and summary is None:
+        raise ValueError("contract needs a summary")
     if summary is not None and world > 1:
         raise ValueError("summary: sharded summaries (several ranks) are not supported")
     if summary is not None and NtChunk != 2 * math.ceil(3 * tSig) + 1:
@@ -361,7 +370,8 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
         h0, h1 = frame_blocks(nOut, rank, world) if nOut > 0 else (0, 0)
         if h1 > h0 and NtChunk == 2 * rt + 1:
             _process_stream(load_frame, (h0, h1), NtChunk, NtSlice, spatialDimensions, xyzSig, tSig, wSig, prefix,
-                            names, precision, writer, summary=summary, save_fields=save_fields, quiver=quiver)
+                            names, precision, writer, summary=summary, save_fields=save_fields, quiver=quiver,
+                            contract=contract)
         else:  # window and temporal taps disagree (non-integer 6*tSig+1): one upload per window
             for hh in range(h0, h1):
                 loopStart = datetime.now()
@@ -408,7 +418,7 @@ class _Shape:
 
 
 def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig, wSig, prefix, names,
-                    precision="fp64", write_fn=None, summary=None, save_fields=True, quiver=None):
+                    precision="fp64", write_fn=None, summary=None, save_fields=True, quiver=None, contract=None):
     """process_flow's loop on a device-resident frame ring (stream.py): one
     frame read + upload per output frame; compute, download and TIFF writing
     of consecutive frames overlap.  Files and stdout lines are the reference's
@@ -416,7 +426,9 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
     out_range = (h0, h1): the windows starting at frames h0 .. h1 - 1 (a rank's block).
     summary (a SummarySpec): each frame's device-side summary is collected and written as
     <prefix>_summary.csv / _summary_hist.npz at the end; save_fields=False: no TIFFs.  quiver (a
-    QuiverSpec): each frame's quiver vectors are written as <prefix>_quiver_t%04d.npz."""
+    QuiverSpec): each frame's quiver vectors are written as <prefix>_quiver_t%04d.npz.  contract (a
+    ContractSpec): each frame's contractility is collected and written as <prefix>_contract.csv /
+    _contract_hist.npz at the end."""
     from concurrent.futures import ThreadPoolExecutor
 
     from .stream import FlowStream, Writer
@@ -428,8 +440,9 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
         _check_args(_Shape((NtChunk,) + first.shape), ndim + 1, tSig, MSG_NDIM_3D if ndim == 3 else MSG_NDIM_2D)
     dt = first.dtype.newbyteorder('=') if first.dtype.byteorder not in ('=', '|') else first.dtype
     fs = FlowStream(ndim, first.shape, dt, xyzSig, tSig, wSig, precision=precision,
-                    rel_fp64=write_fn is not None and ndim == 3, summary=summary, fields=save_fields, quiver=quiver)
-    frames, summaries = [], []
+                    rel_fp64=write_fn is not None and ndim == 3, summary=summary, fields=save_fields, quiver=quiver,
+                    contract=contract)
+    frames, summaries, contracts = [], [], []
 
     def finish(frame, start, start_str, pending):
         print(start_str + ' - Processing frame ' + str(frame) + '...')
@@ -437,6 +450,8 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
             if summary is not None:
                 frames.append(frame)
                 summaries.append(pending.summary())
+            if contract is not None:
+                contracts.append(pending.contract())
             if quiver is not None:
                 from .analysis import write_quiver
 
@@ -472,6 +487,10 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
         from .analysis import write_summaries
 
         write_summaries(prefix, frames, summaries)
+    if contract is not None:
+        from .analysis import write_contract
+
+        write_contract(prefix, frames, contracts)
 
 
 def _process_slab(load_part, axis, vol, nOut, NtChunk, NtSlice, xyzSig, tSig, wSig, prefix, names, precision,

@@ -3,7 +3,9 @@
 // (plot_figure4_timeTraces.m:75-79, plot_figure5.m:87-88, plot_figure3_ROIfigures.m:96), per
 // ROI box, on the device; of3d_mask_open_pair: the same opening of the joint mask of two
 // channels (plot_figure3_ROIfigures.m:93-96), which differs in the foreground test of phase 1
-// alone.  Connected components by label-equivalence union-find: every
+// alone; of3d_mask_largest: the largest component alone (plot_figure2_movie.ipynb cell 1:
+// measure.label, the regions sorted by area, all but the first zeroed), which differs in what
+// follows the counting phase.  Connected components by label-equivalence union-find: every
 // component ends rooted at its smallest linear index, so the component sizes, the counts and
 // the kept mask are integers fixed by the input alone, whatever the dispatch order.
 // Stream-ordered end to end: one launch per phase, nothing returns to the host, no workgroup
@@ -265,6 +267,48 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_write(CclParams P, const u3
     }
 }
 
+// Phase 5 of of3d_mask_largest: every root offers (size << 32) | (kBg - root) to the box's word
+// `best` (zeroed on the stream).  The maximum is the largest component, among equals the one of
+// the smallest root: a function of the input alone, whatever the order of the offers.  A
+// thread keeps the largest of its own offers, a wave the largest of its lanes': one atomicMax
+// per wave that saw a root.
+__global__ __launch_bounds__(kCclThreads) void k_ccl_select(CclParams P, const u32* __restrict__ label,
+                                                            const u32* __restrict__ size, u64* __restrict__ best) {
+    u64 key = 0;  // a root's size is at least 1: 0 stands for "no root"
+    const u64 stride = (u64)gridDim.x * kCclThreads;
+    for (u64 i64 = (u64)blockIdx.x * kCclThreads + threadIdx.x; i64 < P.n; i64 += stride) {
+        const u32 i = (u32)i64;
+        if (label[i] != i) continue;
+        const u64 k = ((u64)size[i] << 32) | (u64)(kBg - i);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const u64 o = __shfl_down(key, off, 64);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0 && key) atomicMax(best, key);
+}
+
+// Phase 6 of of3d_mask_largest: bit roi of keep where the voxel's root is the winner of
+// `best`; n_components_kept (0 or 1) and n_kept (the winner's size) by one thread.
+__global__ __launch_bounds__(kCclThreads) void k_ccl_write_largest(CclParams P, const u32* __restrict__ label,
+                                                                   const u64* __restrict__ best,
+                                                                   uint16_t* __restrict__ keep,
+                                                                   u64* __restrict__ counts) {
+    const u64 b = *best;
+    if (!b) return;  // an empty mask keeps nothing; the counts stay 0
+    const u32 winner = kBg - (u32)b;
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[2] = 1, counts[3] = b >> 32;
+    const u64 stride = (u64)gridDim.x * kCclThreads;
+    for (u64 i64 = (u64)blockIdx.x * kCclThreads + threadIdx.x; i64 < P.n; i64 += stride) {
+        const u32 i = (u32)i64;
+        if (label[i] != winner) continue;
+        const size_t g = locate(P, i).g;
+        keep[g] = (uint16_t)(keep[g] | (1u << P.roi));
+    }
+}
+
 // bits of the neighbour mask for a connectivity: a neighbour belongs to it when its number of
 // non-zero offsets is at most 1 (4, 6), 2 (8, 18) or 3 (26)
 u32 neighbour_mask(int connectivity) {
@@ -295,9 +339,11 @@ int check_boxes(const int64_t* rois, int n_roi, const int64_t dims[3], int64_t* 
 
 // Everything of an opening but the argument checks of its foreground test: the phases per box,
 // phase 1 with `is_fg` (of3d_mask_open and of3d_mask_open_pair differ in nothing else).
+// largest (of3d_mask_largest): the selection and its write phase in place of phase 5.
 template <typename Fg>
 int open_launch(Fg is_fg, int64_t nz, int64_t ny, int64_t nx, const int64_t* rois, int n_roi, int64_t min_size,
-                int connectivity, uint16_t* d_keep, int64_t* d_counts, void* workspace, void* stream) {
+                int connectivity, uint16_t* d_keep, int64_t* d_counts, void* workspace, void* stream,
+                bool largest = false) {
     if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
         return of3dk::set_error("of3d: mask dims must lie in [1, 2^31)");
     if (min_size < 1) return of3dk::set_error("of3d: min_size must be at least 1");
@@ -311,6 +357,8 @@ int open_launch(Fg is_fg, int64_t nz, int64_t ny, int64_t nx, const int64_t* roi
     hipStream_t s = (hipStream_t)stream;
     u32* label = (u32*)workspace;
     u32* size = label + most;
+    u64* best = (u64*)(size + most);  // of3d_mask_largest: one word per box behind the sizes
+    if (largest) OF3DK_HIP(hipMemsetAsync(best, 0, (size_t)n_roi * sizeof(u64), s));
     OF3DK_HIP(hipMemsetAsync(d_keep, 0, (size_t)nz * ny * nx * sizeof(uint16_t), s));
     OF3DK_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_roi * 4 * sizeof(int64_t), s));
     for (int r = 0; r < n_roi; ++r) {
@@ -332,7 +380,13 @@ int open_launch(Fg is_fg, int64_t nz, int64_t ny, int64_t nx, const int64_t* roi
         // and count into the result, not one per 256 voxels)
         const dim3 walk(grid.x < (unsigned)kCclWalkBlocks ? grid.x : (unsigned)kCclWalkBlocks);
         hipLaunchKernelGGL(k_ccl_count, walk, block, 0, s, P, label, size, counts);
-        hipLaunchKernelGGL(k_ccl_write, walk, block, 0, s, P, (const u32*)label, (const u32*)size, d_keep, counts);
+        if (largest) {
+            hipLaunchKernelGGL(k_ccl_select, walk, block, 0, s, P, (const u32*)label, (const u32*)size, best + r);
+            hipLaunchKernelGGL(k_ccl_write_largest, walk, block, 0, s, P, (const u32*)label, (const u64*)(best + r),
+                               d_keep, counts);
+        } else {
+            hipLaunchKernelGGL(k_ccl_write, walk, block, 0, s, P, (const u32*)label, (const u32*)size, d_keep, counts);
+        }
     }
     OF3DK_HIP(hipGetLastError());
     return 0;
@@ -359,6 +413,23 @@ int of3d_mask_open(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64
                            min_size, connectivity, d_keep, d_counts, workspace, stream);
     return open_launch(FgSingle<float>{(const float*)d_rel, (const float*)d_thresh}, nz, ny, nx, rois, n_roi,
                        min_size, connectivity, d_keep, d_counts, workspace, stream);
+}
+
+size_t of3d_mask_largest_workspace_bytes(const int64_t* rois, int n_roi) {
+    const size_t open_bytes = of3d_mask_open_workspace_bytes(rois, n_roi);
+    return open_bytes ? open_bytes + (size_t)n_roi * sizeof(u64) : 0;
+}
+
+int of3d_mask_largest(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64_t nx, const void* d_thresh,
+                      const int64_t* rois, int n_roi, int connectivity, uint16_t* d_keep, int64_t* d_counts,
+                      void* workspace, void* stream) {
+    if (!d_rel || !d_thresh || !rois || !d_keep || !d_counts || !workspace)
+        return of3dk::set_error("of3d: null argument");
+    if (rel_f64)
+        return open_launch(FgSingle<double>{(const double*)d_rel, (const double*)d_thresh}, nz, ny, nx, rois, n_roi,
+                           1, connectivity, d_keep, d_counts, workspace, stream, true);
+    return open_launch(FgSingle<float>{(const float*)d_rel, (const float*)d_thresh}, nz, ny, nx, rois, n_roi, 1,
+                       connectivity, d_keep, d_counts, workspace, stream, true);
 }
 
 int of3d_mask_open_pair(const void* d_rel0, const void* d_thresh0, const void* d_rel1, const void* d_thresh1,

@@ -55,7 +55,7 @@ class FlowStream:
 
     def __init__(self, ndim, vol_shape, dtype, xyzSig, tSig, wSig, device=None, depth=3, d2h="dma",
                  d2h_blocks=64, precision="fp64", rel_fp64=False, zslab=None, lookahead=None, k0_batch=None,
-                 summary=None, fields=True, quiver=None):
+                 summary=None, fields=True, quiver=None, contract=None):
         """summary=analysis.SummarySpec: submit() enqueues the percentile select and the summary
         kernels (csrc/kt_summary.hip) on the compute stream right after the plan's kernels, on the
         device outputs of that buffer set, and the copy of the few-kilobyte result to a pinned
@@ -67,7 +67,12 @@ class FlowStream:
         in the same result words.  quiver=analysis.QuiverSpec (needs a summary): the quiver
         vectors of every ROI (csrc/kt_quiver.hip) follow the summary's kernels, with its threshold
         and opened mask, into a device block and a pinned host block of their own per buffer set;
-        Pending.quiver() returns analysis.quiver_sample's per-ROI list.
+        Pending.quiver() returns analysis.quiver_sample's per-ROI list.  contract=
+        analysis.ContractSpec (needs a summary): the contractility kernels (csrc/kt_contract.hip;
+        with mask="largest" csrc/kt_ccl.hip's labelling and selection first) follow those, again
+        into a device block and a pinned host block of their own per buffer set, copied after the
+        summary words; Pending.contract() returns analysis.contractility's dict.  The quiver keeps
+        the summary's mask whatever the contract's.
 
         zslab=(rank, world, group[, axis]): this process holds one slab of every frame (3D
         only) — axis 0 (default): output planes shard.zslab_bounds(nz, rank, world); axis 1:
@@ -99,6 +104,8 @@ class FlowStream:
             raise ValueError("FlowStream: fields=False needs a summary")
         if quiver is not None and summary is None:
             raise ValueError("FlowStream: quiver needs a summary")
+        if contract is not None and summary is None:
+            raise ValueError("FlowStream: contract needs a summary")
         self.fields = bool(fields)
         self.device = _lib.device_index() if device is None else device
         self.dev = torch.device("cuda", self.device)
@@ -226,7 +233,7 @@ class FlowStream:
         if summary is not None:
             from .analysis import _SummaryCall
 
-            self.summary = _SummaryCall(summary, self.shape, rel_t, self.dev, quiver=quiver)
+            self.summary = _SummaryCall(summary, self.shape, rel_t, self.dev, quiver=quiver, contract=contract)
             self.dsum = [self.summary.new_result(self.dev) for _ in range(depth)]
             self.hsum = [torch.empty(self.summary.result_bytes // 8, dtype=torch.int64, pin_memory=True)
                          for _ in range(depth)]
@@ -234,6 +241,10 @@ class FlowStream:
                 self.dquiv = [self.summary.quiver.new_result(self.dev) for _ in range(depth)]
                 self.hquiv = [torch.empty(self.summary.quiver.result_bytes // 8, dtype=torch.int64, pin_memory=True)
                               for _ in range(depth)]
+            if contract is not None:
+                self.dcont = [self.summary.contract.new_result(self.dev) for _ in range(depth)]
+                self.hcont = [torch.empty(self.summary.contract.result_bytes // 8, dtype=torch.int64,
+                                          pin_memory=True) for _ in range(depth)]
         # row slabs without row ranges: the plan writes all rows of its sub-volume here; the own
         # rows are copied out
         self.dfull = mk(False, max(self.nblock, 1)) if self.axis == 1 and not self.rows_direct else None
@@ -366,13 +377,17 @@ class FlowStream:
             # so a later submit() that reuses this set's device outputs (after its release()) is
             # ordered behind these reads by the stream itself
             with_quiver = self.summary.quiver is not None
+            with_contract = self.summary.contract is not None
             self.summary.enqueue(dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(),
                                  self.precision == "fp32", self.dsum[b].data_ptr(), self.comp.cuda_stream,
-                                 quiver_ptr=self.dquiv[b].data_ptr() if with_quiver else None)
+                                 quiver_ptr=self.dquiv[b].data_ptr() if with_quiver else None,
+                                 contract_ptr=self.dcont[b].data_ptr() if with_contract else None)
             with torch.cuda.stream(self.comp):
                 self.hsum[b].copy_(self.dsum[b], non_blocking=True)
                 if with_quiver:
                     self.hquiv[b].copy_(self.dquiv[b], non_blocking=True)
+                if with_contract:
+                    self.hcont[b].copy_(self.dcont[b], non_blocking=True)
                 pending.sum_event = torch.cuda.Event()
                 pending.sum_event.record(self.comp)
         cev = torch.cuda.Event()
@@ -451,6 +466,17 @@ class Pending:
             raise RuntimeError("FlowStream was created without a quiver request")
         self.sum_event.synchronize()
         return self.fs.summary.quiver.decode(self.fs.hquiv[self.b].numpy().copy())
+
+    def contract(self):
+        """analysis.contractility's dict of this frame (streams created with contract=)."""
+        if self.sum_event is None or self.fs.summary.contract is None:
+            raise RuntimeError("FlowStream was created without a contract request")
+        self.sum_event.synchronize()
+        out = self.fs.summary.contract.decode(self.fs.hcont[self.b].numpy().copy())
+        words = self.fs.hsum[self.b].numpy()
+        rel_dt = np.dtype(np.float64 if self.fs.summary.rel_f64 else np.float32)
+        out["threshold"] = rel_dt.type(words[:1].view(np.float64)[0])
+        return out
 
     def result(self):
         """Host arrays: views of pinned buffers, valid until release()."""
