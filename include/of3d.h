@@ -669,6 +669,57 @@ int of3d_flow_contract(const void* d_vx, const void* d_vy, const void* d_vz, con
                        const double* center_given, const int* nbins2, const double* const* edges2, void* d_result,
                        void* workspace, void* stream);
 
+/* Spread of the flow about a centre: per box the second moments of the deviations of vx, vy, vz
+ * and the magnitude from a centre, the sums of sin / cos of phi, and the extremes — what the
+ * reference's validation figure reduces a frame to (plot_FigureS1_translation.ipynb, cell
+ * "Calculations over time": np.nanstd of vx, vy, vz and the speed, the circular standard
+ * deviation of theta and of phi, set against the translation applied to the images), and the
+ * extremes the other figures pick their colour limits from.  Fields, d_rel, dtypes, dims,
+ * d_thresh, scales, rois and validity (magnitude not NaN) as of3d_flow_summary's; d_keep as
+ * of3d_flow_whist's (NULL: rel > *d_thresh; else bit r of d_keep for box r, and d_rel / d_thresh
+ * may then be NULL).  2D: d_vz == NULL and nz == 1; every vz term is 0 and the phi sums are 0.
+ * The centre (vx, vy, vz, magnitude; physical units):
+ *   center == NULL  box r is measured about its own mean c_q = sum_q / n_valid, one float64
+ *                   division on the device from d_summary, the device result of
+ *                   of3d_flow_summary[_masked] for the same inputs (enqueued earlier on `stream`;
+ *                   summary_nbins: that call's nbins, host int[6], which place a box's words).
+ *                   Nothing returns to the host.  n_valid == 0 gives a NaN centre.
+ *   center given    host, 4 doubles, the same for every box (kernel arguments) — deviations from
+ *                   a known velocity; d_summary and summary_nbins may then be NULL.  2D: center[2]
+ *                   is taken as 0.
+ * A pass of its own because the deviations must be centred: the one-pass form E[x^2] - E[x]^2
+ * cancels where the spread is small against the mean (a near-uniform translation), and the mean
+ * exists only after the summary's final kernel.  Per valid voxel, with d = value - centre:
+ * dvx^2, dvy^2, dvz^2, dmag^2, dvx*dvy, dvx*dvz, dvy*dvz; sin(phi) = vz / mag and cos(phi) = h / mag,
+ * h = sqrt(vx^2 + vy^2) (as the summary forms sin(theta) = vy / h); the running minimum and
+ * maximum of vx, vy, vz and the magnitude.
+ *
+ * Result (device, of3d_flow_spread_result_bytes(n_roi) bytes, 8-byte words, zeroed on the stream
+ * first), per box OF3D_SPREAD_ROI_WORDS words:
+ *    0       n_valid (int64; of3d_flow_summary's for the same mask)
+ *    1..4    float64 the centre used: vx vy vz magnitude
+ *    5..11   float64 sums of dvx^2 dvy^2 dvz^2 dmag^2 dvx*dvy dvx*dvz dvy*dvz
+ *   12..13   float64 sums of sin(phi), cos(phi)
+ *   14..17   float64 minima of vx vy vz magnitude (NaN when n_valid == 0)
+ *   18..21   float64 maxima of vx vy vz magnitude (NaN when n_valid == 0)
+ * Deterministic under of3d_flow_summary's contract: its workgroup partition and walk, the sums in
+ * registers, a fixed shuffle tree over the lanes, the waves in wave order into the workgroup's own
+ * workspace slot, a second kernel adding a box's slots in index order; the extremes go through
+ * the same slots (a minimum does not depend on the order); n_valid by integer atomics; no
+ * floating-point atomic.  Equal inputs give equal bits on every run, and a box's words do not
+ * depend on the other boxes.
+ * `workspace`: device memory of of3d_flow_spread_workspace_bytes(rois, n_roi) bytes (one slot of
+ * 17 float64 per workgroup of every box); host arithmetic only, 0 (and of3d_last_error's text) for
+ * an invalid box, more than 16 boxes or a workgroup share of 2^31 voxels or more.  Enqueued on
+ * `stream`; no host copy, no host synchronisation, no workgroup waits for another. */
+#define OF3D_SPREAD_ROI_WORDS 22
+size_t of3d_flow_spread_result_bytes(int n_roi);
+size_t of3d_flow_spread_workspace_bytes(const int64_t* rois, int n_roi);
+int of3d_flow_spread(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32, int rel_f64,
+                     int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                     double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const void* d_summary,
+                     const int* summary_nbins, const double* center, void* d_result, void* workspace, void* stream);
+
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order
  * x2 y2 z2 xy xz yz (calc_flow.py:352-354's matrix (x2 xy xz / xy y2 yz /

@@ -158,6 +158,12 @@ COMBINE = {"or": 0, "and": 1}  # of3d_mask_open_pair's combine
 CONTRACT_QUANTITIES = ("angle", "inward")
 CONTRACT_SUMS = ("sum_angle", "sum_dot", "sum_inward", "sum_speed")
 _CT_HEAD = 17  # a box's result words before its histograms (include/of3d.h)
+# of3d_flow_spread (csrc/kt_spread.hip): second moments about a centre, phi sums, extremes (the
+# validation figure S1, plot_FigureS1_translation.ipynb cell "Calculations over time")
+SPREAD_COMPONENTS = ("vx", "vy", "vz", "magnitude")  # the centre's, the extremes' and the stds' order
+SPREAD_SUMS = ("ss_vx", "ss_vy", "ss_vz", "ss_magnitude", "ss_vx_vy", "ss_vx_vz", "ss_vy_vz", "sum_sin_phi",
+               "sum_cos_phi")
+_SPREAD_WORDS = 22  # a box's result words (include/of3d.h)
 
 
 def percentile_threshold_device(rel, percentile, out=None):
@@ -207,7 +213,13 @@ class SummarySpec:
     histograms (at most 256 bins; axis3 in 3D only).  None: nothing of this is computed.
     weighted_bins: quantity name -> ascending bin edges, as `bins`, for magnitude-weighted
     histograms, np.histogram(values, bins=edges, weights=magnitude) (of3d_flow_whist); the same
-    quantity may appear in both."""
+    quantity may appear in both.
+    spread: "mean" — the second moments of vx, vy, vz and the magnitude about every ROI's own
+    mean (std_*, velocity_covariance), the circular spread of theta and phi and the extremes
+    (of3d_flow_spread, a centred pass after the summary's) — or ndim + 1 finite numbers (vx, vy[,
+    vz], magnitude; physical units) to measure the deviations from instead, e.g. the translation
+    that was applied to the images (std_* is then the RMS error against it).  None: nothing of
+    this is computed."""
     rois: list | None = None
     bins: dict | None = None
     rel_percentile: float = 90
@@ -219,6 +231,7 @@ class SummarySpec:
     axes: object = None
     axes_physical: bool = False
     axis_bins: dict | None = None
+    spread: object = None  # before weighted_bins, which stays the last field
     weighted_bins: dict | None = None
 
     @staticmethod
@@ -251,6 +264,26 @@ class SummarySpec:
         """Validated (nbins [6], edges [6 arrays or None]) of weighted_bins for an ndim-D volume
         (all 0 / None without any); ValueError on a bad name or bad edges."""
         return self._quantity_bins(self.weighted_bins, ndim, "weighted ")
+
+    def spread_request(self, ndim):
+        """None without spread, else a validated 1-tuple (given,): given = None for "mean" or the
+        4 float64 values vx vy vz magnitude (vz = 0 in 2D); ValueError on a bad value."""
+        if self.spread is None:
+            return None
+        what = f"'mean' or {ndim + 1} numbers (vx, vy{', vz' if ndim == 3 else ''}, magnitude)"
+        if isinstance(self.spread, str):
+            if self.spread != "mean":
+                raise ValueError(f"summary: spread {self.spread!r} is not {what}")
+            return (None,)
+        try:
+            given = np.ascontiguousarray(self.spread, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"summary: spread {self.spread!r} is not {what}") from None
+        if given.shape != (ndim + 1,):
+            raise ValueError(f"summary: spread must be {what} for a {ndim}D volume, got shape {given.shape}")
+        if not np.all(np.isfinite(given)):
+            raise ValueError("summary: spread centre must be finite")
+        return (np.array([given[0], given[1], given[2] if ndim == 3 else 0.0, given[-1]]),)
 
     def axes_request(self, ndim):
         """None without axes, else validated (given, nbins3, edges3): given = None for "mask" or
@@ -325,6 +358,7 @@ class SummarySpec:
             raise ValueError(f"summary: at most {MAX_ROI - 1} ROIs beside the whole volume, got {len(boxes) - 1}")
         nbins, edges = self._quantity_bins(self.bins, ndim)
         self.weighted(ndim)
+        self.spread_request(ndim)
         return np.array(boxes, dtype=np.int64), nbins, edges
 
 
@@ -469,6 +503,62 @@ class _WhistCall(_BoxCall):
         out["hist_weighted"], out["edges_weighted"] = {}, {}
         _decode_hists(body, 1, QUANTITIES, self.nbins, self.edges, np.float64, out["hist_weighted"],
                       out["edges_weighted"])
+        return out
+
+
+class _SpreadCall(_BoxCall):
+    """of3d_flow_spread bound to boxes and a device: sizes, the workspace and the decoding.
+    given: None (every box about its own mean, read on the device from the summary's result) or
+    the 4 float64 values of SummarySpec.spread_request."""
+
+    def __init__(self, boxes, dims, rel_f64, given, ndim, scales, device):
+        super().__init__(boxes, dims, rel_f64)
+        self.given, self.ndim = given, int(ndim)
+        self.given_arr = given.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if given is not None else None
+        self.scales = tuple(float(v) for v in scales)
+        self.ws = self._workspace(self.lib.of3d_flow_spread_workspace_bytes(self.roi_arr, len(self.boxes)), device)
+        self.result_bytes = self.lib.of3d_flow_spread_result_bytes(len(self.boxes))
+
+    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, summary_ptr, summary_nbins, result_ptr, stream):
+        """The accumulation and final kernels on `stream` (device pointers), after the summary
+        whose result lies at summary_ptr (summary_nbins: its ctypes nbins)."""
+        _lib.check(self.lib.of3d_flow_spread(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
+                                             thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
+                                             keep_ptr or None, summary_ptr, summary_nbins, self.given_arr,
+                                             result_ptr, self.ws.data_ptr(), stream or None))
+
+    def decode(self, words, out):
+        """The block's words (host int64) added to the dict `out` (flow_summary's keys)."""
+        n_roi = len(self.boxes)
+        body = np.ascontiguousarray(words[:n_roi * _SPREAD_WORDS], dtype=np.int64).reshape(n_roi, _SPREAD_WORDS)
+        assert np.array_equal(body[:, 0], out["n_valid"]), (body[:, 0], out["n_valid"])
+        f = np.ascontiguousarray(body[:, 1:]).view(np.float64)
+        out["spread_center"] = f[:, 0:4].copy()
+        for i, k in enumerate(SPREAD_SUMS):
+            out[k] = f[:, 4 + i].copy()
+        for i, k in enumerate(SPREAD_COMPONENTS):
+            out["min_" + k], out["max_" + k] = f[:, 13 + i].copy(), f[:, 17 + i].copy()
+        nv = out["n_valid"].astype(np.float64)
+        nv[nv == 0] = np.nan  # empty box: NaN, no division warnings
+        for k in SPREAD_COMPONENTS:
+            out["std_" + k] = np.sqrt(out["ss_" + k] / nv)  # ddof 0, as np.nanstd
+        c = np.stack([out[k] for k in SPREAD_SUMS[:7]], axis=1) / nv[:, None]
+        out["velocity_covariance"] = c[:, [0, 4, 5, 4, 1, 6, 5, 6, 2]].reshape(n_roi, 3, 3)
+        n_all = out["n_voxels"].astype(np.float64)
+
+        def circular(prefix, sn, cs):
+            # the notebook's (scipy.stats.circstd's) sqrt(-2 ln R); rounding can leave R an ulp above 1
+            with np.errstate(divide="ignore"):
+                r = np.hypot(sn, cs) / nv
+                out[prefix + "_resultant"] = r
+                out[prefix + "_std"] = np.sqrt(np.maximum(0.0, -2.0 * np.log(r)))
+                # the notebook divides its sums by the array's size, NaNs included: R * n_valid / n_voxels
+                out[prefix + "_std_all"] = np.sqrt(np.maximum(0.0, -2.0 * np.log(r * nv / n_all)))
+
+        circular("theta", out["sum_sin"], out["sum_cos"])
+        if self.ndim == 3:
+            out["phi_mean"] = np.arctan2(out["sum_sin_phi"] / nv, out["sum_cos_phi"] / nv)
+            circular("phi", out["sum_sin_phi"], out["sum_cos_phi"])
         return out
 
 
@@ -864,6 +954,13 @@ class _SummaryCall(_BoxCall):
             self.whist = _WhistCall(self.boxes, self.dims, self.rel_f64, wnbins, wedges,
                                     (spec.xyscale, spec.zscale, spec.tscale), device)
             self.result_bytes += self.whist.result_bytes
+        # then (spread) of3d_flow_spread's block
+        request = spec.spread_request(len(self.shape))
+        self.spread, self.spread_off = None, self.result_bytes
+        if request is not None:
+            self.spread = _SpreadCall(self.boxes, self.dims, self.rel_f64, request[0], len(self.shape),
+                                      (spec.xyscale, spec.zscale, spec.tscale), device)
+            self.result_bytes += self.spread.result_bytes
         self.quiver = None
         if quiver is not None:
             self.quiver = _QuiverCall(self.boxes, self.dims, self.rel_f64, quiver, len(self.shape),
@@ -913,6 +1010,10 @@ class _SummaryCall(_BoxCall):
             self.whist.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
                                self.open.keep.data_ptr() if self.open is not None else None,
                                result_ptr + self.whist_off, stream)
+        if self.spread is not None:
+            self.spread.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+                                self.open.keep.data_ptr() if self.open is not None else None, result_ptr,
+                                self.nb_arr, result_ptr + self.spread_off, stream)
         if self.quiver is not None:
             self.quiver.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
                                 self.open.keep.data_ptr() if self.open is not None else None, quiver_ptr, stream)
@@ -947,6 +1048,8 @@ class _SummaryCall(_BoxCall):
             self.axes.decode(words[self.axes_off // 8:], out)
         if self.whist is not None:
             self.whist.decode(words[self.whist_off // 8:], out)
+        if self.spread is not None:
+            self.spread.decode(words[self.spread_off // 8:], out)
         return out
 
 
@@ -1186,7 +1289,7 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
 
 def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None,
                  device=None, min_size=0, connectivity=None, axes=None, axes_physical=False, axis_bins=None,
-                 weighted_bins=None):
+                 weighted_bins=None, spread=None):
     """One frame reduced on the device to a few kilobytes (one small device->host copy).
 
     Inputs as flow_statistics (numpy arrays or torch tensors, vz None for 2D).  The masking is
@@ -1211,6 +1314,17 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     The script bins -phi into phiBins: pass weighted_bins={"phi": -phiBins[::-1]} and reverse
     the bins (hist_weighted["phi"][:, ::-1]); the bins are then right-closed where discretize's
     are left-closed, which differs only for a value exactly on an edge.
+    spread ("mean", or vx, vy[, vz], magnitude to measure from; see SummarySpec): per ROI also
+    spread_center (n_roi, 4: vx vy vz magnitude, the centre used); with d = value - centre over
+    the valid voxels the raw sums ss_vx, ss_vy, ss_vz, ss_magnitude (of d^2), ss_vx_vy, ss_vx_vz,
+    ss_vy_vz (of the products), sum_sin_phi, sum_cos_phi (sin phi = vz / magnitude; 0 in 2D);
+    min_ and max_ of vx, vy, vz, magnitude; and, formed here from the sums, std_* = sqrt(ss / n)
+    (np.nanstd's, ddof 0, for "mean"; the RMS deviation for a given centre), velocity_covariance
+    (n_roi, 3, 3) = ss / n, theta_resultant R = hypot(sum_sin, sum_cos) / n, theta_std =
+    sqrt(max(0, -2 ln R)) (scipy.stats.circstd's), in 3D phi_mean, phi_resultant, phi_std likewise,
+    and theta_std_all / phi_std_all with R * n_valid / n_voxels (the validation notebook divides by
+    the array's size, NaNs included).  NaN where n_valid == 0.  By a centred pass of its own
+    (of3d_flow_spread): std << |mean| loses nothing.
     Bit-reproducible: the same inputs give the same bits on every run."""
     import torch
 
@@ -1222,7 +1336,7 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     if tx.dim() != (3 if tz is not None else 2):
         raise ValueError("flow_summary needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
     spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale, min_size, connectivity, axes,
-                       axes_physical, axis_bins, weighted_bins)
+                       axes_physical, axis_bins, weighted_bins=weighted_bins, spread=spread)
     call = _SummaryCall(spec, tuple(tx.shape), tr.dtype, tx.device)
     res = call.new_result(tx.device)
     call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
@@ -1500,6 +1614,23 @@ CSV_AXES_COLUMNS = CSV_AXES_INT_COLUMNS + (
     + tuple("sum_" + a for a in AXIS_NAMES) + tuple("mean_" + a for a in AXIS_NAMES))
 
 
+# appended when the summaries carry the spread block (SummarySpec.spread): float64 columns (the
+# phi columns NaN in 2D)
+_SPREAD_CSV_KEYS = (SPREAD_SUMS + tuple(f"{m}_{k}" for m in ("min", "max", "std") for k in SPREAD_COMPONENTS)
+                    + ("theta_resultant", "theta_std", "phi_mean", "phi_resultant", "phi_std", "theta_std_all",
+                       "phi_std_all"))
+CSV_SPREAD_COLUMNS = (tuple("spread_center_" + k for k in SPREAD_COMPONENTS) + _SPREAD_CSV_KEYS
+                      + ("vcov_xx", "vcov_yy", "vcov_zz", "vcov_xy", "vcov_xz", "vcov_yz"))
+
+
+def _spread_row(s, r):
+    """The CSV_SPREAD_COLUMNS values of ROI r of a summary dict."""
+    c = s["velocity_covariance"][r]
+    floats = list(s["spread_center"][r]) + [s[k][r] if k in s else np.nan for k in _SPREAD_CSV_KEYS]
+    floats += [c[0, 0], c[1, 1], c[2, 2], c[0, 1], c[0, 2], c[1, 2]]
+    return [repr(float(v)) for v in floats]
+
+
 def _axes_row(s, r):
     """The CSV_AXES_COLUMNS values of ROI r of a summary dict."""
     c = s["covariance"][r]
@@ -1513,14 +1644,17 @@ def _axes_row(s, r):
 def write_summaries(prefix, frames, summaries):
     """<prefix>_summary.csv (one row per frame and ROI; floats as repr, so they read back
     exactly; the columns CSV_COLUMNS, then CSV_OPEN_COLUMNS when the summaries were made with
-    min_size >= 1, then CSV_AXES_COLUMNS when they were made with axes) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
+    min_size >= 1, then CSV_AXES_COLUMNS when they were made with axes, then CSV_SPREAD_COLUMNS
+    when they were made with spread) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
     (frames, n_roi, nbins), and with weighted_bins wedges_<name>, weights_<name> float64 of that
     shape) from flow_summary dicts of consecutive frames."""
     opened = bool(summaries) and all(k in summaries[0] for k in CSV_OPEN_COLUMNS)
     with_axes = bool(summaries) and "axes_used" in summaries[0]
+    with_spread = bool(summaries) and "spread_center" in summaries[0]
     with open(prefix + "_summary.csv", "w", newline="") as f:
         f.write(",".join(CSV_COLUMNS + (CSV_OPEN_COLUMNS if opened else ())
-                         + (CSV_AXES_COLUMNS if with_axes else ())) + "\n")
+                         + (CSV_AXES_COLUMNS if with_axes else ())
+                         + (CSV_SPREAD_COLUMNS if with_spread else ())) + "\n")
         for frame, s in zip(frames, summaries):
             for r in range(len(s["rois"])):
                 row = [int(frame), r] + [int(v) for v in s["rois"][r]] + [repr(float(s["threshold"]))]
@@ -1530,6 +1664,8 @@ def write_summaries(prefix, frames, summaries):
                     row += [int(s[k][r]) for k in CSV_OPEN_COLUMNS]
                 if with_axes:
                     row += _axes_row(s, r)
+                if with_spread:
+                    row += _spread_row(s, r)
                 f.write(",".join(str(v) for v in row) + "\n")
     arrays = {"frames": np.asarray(list(frames), dtype=np.int64)}
     if summaries:

@@ -219,7 +219,8 @@ int quantile_launch(const void* a, int64_t n, int64_t lo, int64_t hi, double gam
 using of3dk::kSumThreads, of3dk::kSumWaves, of3dk::kSumMaxBlocks, of3dk::kMaxBins, of3dk::kMaxRoi;  // summary_host.hpp
 constexpr int kNSum = 8;                   // mag x y z sin cos mag*sin mag*cos
 constexpr int kNQ = OF3D_SUMMARY_QUANTITIES;
-constexpr int kHead = 8, kRoiHead = 2 + kNSum;  // result words before the boxes / before a box's histograms
+constexpr int kHead = of3dk::kSummaryHead, kRoiHead = of3dk::kSummaryRoiHead;  // result words before the boxes / before a box's histograms
+static_assert(kRoiHead == 2 + kNSum);
 constexpr size_t kSumSlotBytes = (size_t)kMaxRoi * kSumMaxBlocks * kNSum * sizeof(double);
 constexpr size_t kEdgeWords = (size_t)kNQ * (kMaxBins + 1);
 constexpr size_t kSumWsBytes = kSumSlotBytes + kEdgeWords * sizeof(double);

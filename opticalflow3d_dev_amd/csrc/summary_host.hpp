@@ -1,6 +1,6 @@
 #pragma once
 // summary_host.hpp — the host side shared by the device-side summary passes (kt_summary.hip,
-// kt_ccl.hip, kt_axes.hip, kt_whist.hip, kt_pair.hip): one statement of the box check, the
+// kt_ccl.hip, kt_axes.hip, kt_whist.hip, kt_pair.hip, kt_spread.hip): one statement of the box check, the
 // workgroup plan, the histogram plan with its edge validation, and the edge upload.  The entry
 // points keep their own order of argument checks; what a check tests and says is here.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,11 @@
 namespace of3dk {
 
 constexpr int kMaxRoi = OF3D_SUMMARY_MAX_ROI, kMaxBins = OF3D_SUMMARY_MAX_BINS;
+
+// of3d_flow_summary's result (include/of3d.h): the words before the boxes, and a box's words
+// before its histograms (n_valid, n_voxels, the eight sums).  kt_summary.hip writes by them,
+// kt_spread.hip finds a box's count and sums by them.
+constexpr int kSummaryHead = 8, kSummaryRoiHead = 10;
 
 // The workgroup partition of a box's reduction (k_sum_boxes, k_proj_boxes, k_whist_boxes, k_pair_boxes): workgroup b of nb
 // walks rows [b*R/nb, (b+1)*R/nb) of the box's R = dz*dy rows.  nb is a function of the box
@@ -49,7 +54,7 @@ inline int64_t box_extent(const int64_t* rois, int r, int a, const int64_t* dims
 // The boxes of a reduction pass as of3d_flow_summary validates them (dims NULL: against 2^31
 // alone) and their workgroups: box r's bounds, then box r's size, box by box.  nb_out[r]: the
 // workgroups of box r.  For the passes with per-workgroup workspace slots (of3d_flow_whist,
-// of3d_flow_pair) soff_out[r]: the first slot word of box r, slot_words: the sum over the boxes
+// of3d_flow_pair, of3d_flow_spread) soff_out[r]: the first slot word of box r, slot_words: the sum over the boxes
 // of workgroups * wg_words.  The three outputs may be NULL.
 inline int plan_boxes(const int64_t* rois, int n_roi, const int64_t* dims, int wg_words = 0, int* nb_out = nullptr,
                       long long* soff_out = nullptr, size_t* slot_words = nullptr) {
