@@ -720,6 +720,67 @@ int of3d_flow_spread(const void* d_vx, const void* d_vy, const void* d_vz, const
                      double tscale, const int64_t* rois, int n_roi, const uint16_t* d_keep, const void* d_summary,
                      const int* summary_nbins, const double* center, void* d_result, void* workspace, void* stream);
 
+/* Percentiles of one box of rel, selected on the device: how the reference's figure scripts form
+ * the reliability threshold,
+ *   relCrop = rel(y0:y1, x0:x1, z0:z1);  relThresh = prctile(relCrop(:), relPer);
+ * (plot_figure5.m:80-84, plot_figure5_Movie.m:81-85, plot_figure3_ROIfigures.m:70-84,
+ * plot_figure3_ChannelCompare.m:114-128), without the crop's copy: the volume is read in place.
+ * d_rel: (nz, ny, nx) float32 (float64 with rel_f64), 2D = nz 1.  box: host int64[6] = z0 z1 y0 y1
+ * x0 x1, half-open, inside the volume and not empty; NULL: the whole volume.  n_q: 1 to
+ * OF3D_SELECT_MAX percentiles, each given as of3d_quantile gives its one: host arrays lo[n_q],
+ * hi[n_q] (0-based ranks among the box's n_box voxels, 0 <= lo <= hi <= n_box - 1) and
+ * gamma[n_q] in [0, 1]; the caller's percentile definition decides them (numpy 'linear', or
+ * 'hazen' = MATLAB's prctile).  d_out: n_q device elements of rel's dtype; element k is numpy's
+ * _lerp of the two order statistics in rel's dtype, a + (b - a) * g for g < 0.5 and
+ * b - (b - a) * (1 - g) otherwise — lo == hi goes through the same expression, so an infinite
+ * value gives NaN as numpy does.  -0.0 and +0.0 are one value (+0.0 is returned).  A NaN inside
+ * the box makes every output NaN; a NaN outside it is never read.  Ranks 0 and n_box - 1 are the
+ * box's exact minimum and maximum.  d_out + k is a valid d_thresh of every pass here.
+ * Radix select over 11-bit digits (float32 3 passes, float64 6): per pass one histogram per
+ * distinct key prefix among the up to 16 ranks (the prefixes kept sorted: a voxel finds its
+ * histogram by a range reject and a binary search), LDS integer atomics flushed by 64-bit integer
+ * atomics, then one workgroup narrows every rank.  Rows of the box are walked with 16-byte loads
+ * over their aligned middle and element loads at their ends; full-width rows are joined.
+ * Deterministic: integer counts only, equal inputs give equal bits.  `workspace`: device memory
+ * of of3d_rel_select_workspace_bytes(rel_f64) bytes.  Enqueued on `stream`; no host copy, no host
+ * synchronisation, no launch shape that depends on device data. */
+#define OF3D_SELECT_MAX 8
+size_t of3d_rel_select_workspace_bytes(int rel_f64);
+int of3d_rel_select(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64_t nx, const int64_t* box, int n_q,
+                    const int64_t* lo, const int64_t* hi, const double* gamma, void* d_out, void* workspace,
+                    void* stream);
+
+/* Reliability profile: what plot_figureS3_reliability.ipynb cells 4-8 look at to choose the
+ * percentile — the thresholds at several percentiles, how many voxels each mask keeps, and the
+ * distribution of rel (plt.hist(rel.flatten(), 50)) — per box, over all voxels of the box (no
+ * mask).  d_rel, dims and rois (n_roi <= 16) as of3d_flow_summary's.  d_thresh: n_q (0 to
+ * OF3D_SELECT_MAX) device elements of rel's dtype, e.g. of3d_rel_select's output; the comparison
+ * rel > t_k is made in rel's dtype, as in every other pass.  The histogram has nbins (1 to 256)
+ * bins of (double)rel with np.histogram(values, bins=edges) semantics (last bin closed, values
+ * outside and NaN dropped); its edges come in exactly one of two ways:
+ *   edges    host, nbins + 1 strictly ascending values without NaN (kernel arguments);
+ *   d_range  two device elements lo, hi of rel's dtype (of3d_rel_select's outputs for ranks 0 and
+ *            n_box - 1): a kernel forms np.linspace(lo, hi, nbins + 1) in float64 — step =
+ *            (hi - lo) / nbins, e_i = i * step + lo (a multiply, then an add), e_nbins = hi; lo ==
+ *            hi is widened to lo - 0.5, hi + 0.5 first (np.histogram's outer edges).  A NaN or
+ *            infinite lo / hi gives NaN edges and all-zero counts, where numpy raises.
+ * Result (device, of3d_rel_profile_result_bytes(n_roi, n_q, nbins) bytes, 8-byte words, zeroed on
+ * the stream first):
+ *   word 0  n_roi    word 1  n_q    word 2  nbins   (uint64; OF3D_PROFILE_HEAD words)
+ *   then n_q words: the thresholds as float64
+ *   then nbins + 1 words: the edges used (float64)
+ *   then per box, 2 + n_q + nbins words:
+ *     0  n_voxels    1  n_nan    2..  n_above[k] = #{rel > t_k}    then hist[nbins]   (uint64)
+ * Deterministic: of3d_flow_summary's workgroup partition and walk, per-thread integer counters
+ * reduced per wave, an LDS histogram, 64-bit integer atomics; no floating-point accumulation
+ * anywhere, so equal inputs give equal bits on every run and a box's words do not depend on the
+ * other boxes.  Enqueued on `stream`; no host copy, no host synchronisation. */
+#define OF3D_PROFILE_HEAD 3
+size_t of3d_rel_profile_result_bytes(int n_roi, int n_q, int nbins);
+int of3d_rel_profile(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int64_t nx, const int64_t* rois,
+                     int n_roi, const void* d_thresh, int n_q, int nbins, const double* edges, const void* d_range,
+                     void* d_result, void* stream);
+
 /* Reliability (smallest eigenvalue) of n given symmetric 3x3 structure tensors
  * resident on the device: `tensor` is field-major [6][n] float64 in the order
  * x2 y2 z2 xy xz yz (calc_flow.py:352-354's matrix (x2 xy xz / xy y2 yz /

@@ -58,6 +58,54 @@ def _linear_ranks(n, percentile, dt):
     return lo, hi, gamma
 
 
+PERCENTILE_METHODS = ("linear", "hazen")
+SELECT_MAX = 8  # percentiles of one of3d_rel_select call (OF3D_SELECT_MAX)
+
+
+def _percentile_ranks(n, percentile, dt, method="linear"):
+    """_linear_ranks for either percentile definition: (lo, hi, gamma) of the `percentile`-th
+    percentile of n values of dtype dt.  method "linear": numpy's default.  method "hazen":
+    numpy's method='hazen', which is MATLAB's prctile — the sorted values sit at the
+    100 * (i - 0.5) / n percentiles (i = 1..n), linear in between, clamped to the extremes beyond
+    the first and the last.  numpy's arithmetic, term by term in the array's dtype
+    (_compute_virtual_index with alpha = beta = 0.5): n*q + (0.5 + q*(1 - 0.5 - 0.5)) - 1; the
+    shorter n*q - 0.5 differs from it in the last bit for some (n, percentile).  Clamped as
+    _linear_ranks clamps (vi >= n - 1: the last value, vi < 0: the first), with gamma 0 there:
+    lo == hi makes _lerp's result independent of it."""
+    if method == "linear":
+        return _linear_ranks(n, percentile, dt)
+    if method != "hazen":
+        raise ValueError(f"summary: percentile_method {method!r} is not one of {PERCENTILE_METHODS}")
+    q = np.asanyarray(np.true_divide(percentile, dt.type(100)))
+    vi = np.asanyarray(n * q + (0.5 + q * (1 - 0.5 - 0.5)) - 1)
+    if vi >= n - 1:
+        return n - 1, n - 1, np.asanyarray(0, dtype=dt)
+    if vi < 0:
+        return 0, 0, np.asanyarray(0, dtype=dt)
+    lo = int(np.floor(vi))
+    return lo, lo + 1, np.asanyarray(vi - lo, dtype=dt)
+
+
+def _check_percentiles(percentiles, what, most=SELECT_MAX):
+    """1 to `most` percentiles in [0, 100] as a list of Python floats; ValueError naming `what`."""
+    try:
+        ps = [float(p) for p in percentiles]
+    except (TypeError, ValueError):
+        raise ValueError(f"summary: {what} {percentiles!r} is not a sequence of numbers") from None
+    if not 1 <= len(ps) <= most:
+        raise ValueError(f"summary: {what} needs 1 to {most} values, got {len(ps)}")
+    for p in ps:
+        if not 0 <= p <= 100:  # a NaN fails both comparisons
+            raise ValueError(f"summary: {what} {p} outside [0, 100]")
+    return ps
+
+
+def _check_method(method):
+    if not isinstance(method, str) or method not in PERCENTILE_METHODS:
+        raise ValueError(f"summary: percentile_method {method!r} is not one of {PERCENTILE_METHODS}")
+    return method
+
+
 def _lerp(a, b, gamma, dt):
     """numpy's _lerp of two order statistics in the array's dtype."""
     diff = np.subtract(b, a)
@@ -192,6 +240,32 @@ def percentile_threshold_device(rel, percentile, out=None):
 
 
 @dataclasses.dataclass
+class RelProfileSpec:
+    """The reliability profile asked of SummarySpec(rel_profile=) (reliability_profile gives the
+    same for one frame): what plot_figureS3_reliability.ipynb cells 4-8 look at to choose the
+    percentile.  percentiles: 1 to 6 percentiles whose thresholds and kept-voxel counts are
+    reported (they take the summary's percentile_box and percentile_method).  bins: the number of
+    equal bins of the histogram of rel between the minimum and the maximum of the selection box
+    (1 to 256), as plt.hist(rel.flatten(), bins); edges: ascending edges to use instead (2 to 257
+    values), np.histogram(rel, bins=edges) semantics."""
+    percentiles: tuple = (85, 90, 95)
+    bins: int = 50
+    edges: object = None
+
+    def resolve(self):
+        """Validated (percentiles [floats], nbins, edges float64 array or None); ValueError on a
+        bad value."""
+        ps = _check_percentiles(self.percentiles, "rel_profile percentiles", SELECT_MAX - 2)
+        if self.edges is not None:
+            e = SummarySpec._bin_edges(self.edges, "rel_profile")
+            return ps, e.size - 1, e
+        b = self.bins
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 1 <= b <= MAX_BINS:
+            raise ValueError(f"summary: rel_profile bins {b!r} is not an integer in 1..{MAX_BINS}")
+        return ps, int(b), None
+
+
+@dataclasses.dataclass
 class SummarySpec:
     """What flow_summary / FlowStream(summary=) / process_flow(summary=) reduce a frame to.
 
@@ -219,7 +293,14 @@ class SummarySpec:
     (of3d_flow_spread, a centred pass after the summary's) — or ndim + 1 finite numbers (vx, vy[,
     vz], magnitude; physical units) to measure the deviations from instead, e.g. the translation
     that was applied to the images (std_* is then the RMS error against it).  None: nothing of
-    this is computed."""
+    this is computed.
+    percentile_box: one box (as a ROI's bounds) whose voxels alone form the threshold — the
+    figure scripts' ``prctile(relCrop(:), relPer)`` of the cropped rel (plot_figure5.m:80-84) —
+    read in place (of3d_rel_select); one box and one threshold for the call, whatever `rois`.
+    percentile_method: "linear" (np.percentile's default) or "hazen" (MATLAB's prctile).
+    rel_profile: a RelProfileSpec — the summary also carries rel_profile, reliability_profile's
+    dict (thresholds at several percentiles, the voxels each keeps, the histogram of rel per ROI).
+    With none of the three the threshold is of3d_quantile's of the whole volume."""
     rois: list | None = None
     bins: dict | None = None
     rel_percentile: float = 90
@@ -231,8 +312,54 @@ class SummarySpec:
     axes: object = None
     axes_physical: bool = False
     axis_bins: dict | None = None
+    percentile_box: object = None
+    percentile_method: str = "linear"
+    rel_profile: object = None
     spread: object = None  # before weighted_bins, which stays the last field
     weighted_bins: dict | None = None
+
+    @staticmethod
+    def _box(r, ndim, dims, label):
+        """One box (2 * ndim half-open bounds) validated against dims (nz, ny, nx) as 6 ints
+        (z0, z1, y0, y1, x0, x1); label: what the messages call it."""
+        r = tuple(r)
+        if len(r) != 2 * ndim:
+            raise ValueError(f"summary: {label} {r} needs {2 * ndim} bounds for a {ndim}D volume")
+        if any(int(v) != v for v in r):
+            raise ValueError(f"summary: {label} {r} has non-integer bounds")
+        r = tuple(int(v) for v in r)
+        r = r if ndim == 3 else (0, 1) + r
+        for a in range(3):
+            if not (0 <= r[2 * a] < r[2 * a + 1] <= dims[a]):
+                raise ValueError(f"summary: {label} {r} is empty or outside the volume {dims} "
+                                 f"(axis {'zyx'[a]}: need 0 <= {r[2 * a]} < {r[2 * a + 1]} <= {dims[a]})")
+        return r
+
+    def threshold_request(self, shape):
+        """How the threshold is formed: validated (box, method, profile) for a volume of `shape`
+        — box None (the whole volume) or 6 ints, method "linear" / "hazen", profile None or
+        RelProfileSpec.resolve()'s triple; ValueError on a bad value.  All None / "linear": the
+        flat select (of3d_quantile); anything else goes through of3d_rel_select."""
+        shape = tuple(int(v) for v in shape)
+        ndim = len(shape)
+        dims = shape if ndim == 3 else (1,) + shape
+        box = None
+        if self.percentile_box is not None:
+            try:
+                r = tuple(self.percentile_box)
+            except TypeError:
+                raise ValueError(f"summary: percentile_box {self.percentile_box!r} is not a box") from None
+            try:
+                box = self._box(r, ndim, dims, "percentile_box")
+            except TypeError:
+                raise ValueError(f"summary: percentile_box {r} has non-integer bounds") from None
+        method = _check_method(self.percentile_method)
+        profile = None
+        if self.rel_profile is not None:
+            if not isinstance(self.rel_profile, RelProfileSpec):
+                raise ValueError(f"summary: rel_profile {self.rel_profile!r} is not a RelProfileSpec")
+            profile = self.rel_profile.resolve()
+        return box, method, profile
 
     @staticmethod
     def _bin_edges(e, label):
@@ -342,23 +469,13 @@ class SummarySpec:
             raise ValueError(f"summary: rel_percentile {self.rel_percentile} outside [0, 100]")
         boxes = [(0, dims[0], 0, dims[1], 0, dims[2])]
         for i, r in enumerate(self.rois or ()):
-            r = tuple(r)
-            if len(r) != 2 * ndim:
-                raise ValueError(f"summary: ROI {i + 1} {r} needs {2 * ndim} bounds for a {ndim}D volume")
-            if any(int(v) != v for v in r):
-                raise ValueError(f"summary: ROI {i + 1} {r} has non-integer bounds")
-            r = tuple(int(v) for v in r)
-            r = r if ndim == 3 else (0, 1) + r
-            for a in range(3):
-                if not (0 <= r[2 * a] < r[2 * a + 1] <= dims[a]):
-                    raise ValueError(f"summary: ROI {i + 1} {r} is empty or outside the volume {dims} "
-                                     f"(axis {'zyx'[a]}: need 0 <= {r[2 * a]} < {r[2 * a + 1]} <= {dims[a]})")
-            boxes.append(r)
+            boxes.append(self._box(r, ndim, dims, f"ROI {i + 1}"))
         if len(boxes) > MAX_ROI:
             raise ValueError(f"summary: at most {MAX_ROI - 1} ROIs beside the whole volume, got {len(boxes) - 1}")
         nbins, edges = self._quantity_bins(self.bins, ndim)
         self.weighted(ndim)
         self.spread_request(ndim)
+        self.threshold_request(shape)
         return np.array(boxes, dtype=np.int64), nbins, edges
 
 
@@ -805,6 +922,77 @@ class _ContractCall(_BoxCall):
         return out
 
 
+class _SelectCall:
+    """of3d_rel_select bound to a volume, one box (None: the whole volume), percentiles and a
+    method: the ranks (relative to the box's voxel count) and the workspace, formed once."""
+
+    def __init__(self, dims, rel_f64, box, percentiles, method, device):
+        import torch
+
+        self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(int(v) for v in dims), int(rel_f64)
+        dt = np.dtype(np.float64 if rel_f64 else np.float32)
+        b = (0, self.dims[0], 0, self.dims[1], 0, self.dims[2]) if box is None else tuple(int(v) for v in box)
+        self.n_box = (b[1] - b[0]) * (b[3] - b[2]) * (b[5] - b[4])
+        ranks = [_percentile_ranks(self.n_box, p, dt, method) for p in percentiles]
+        self.n_q = len(ranks)
+        self.lo = np.array([r[0] for r in ranks], dtype=np.int64)
+        self.hi = np.array([r[1] for r in ranks], dtype=np.int64)
+        self.gamma = np.array([float(r[2]) for r in ranks], dtype=np.float64)
+        self.box = None if box is None else np.array(b, dtype=np.int64)
+        self.ws = torch.empty(self.lib.of3d_rel_select_workspace_bytes(self.rel_f64), dtype=torch.uint8,
+                              device=device)
+
+    def enqueue(self, rel, out_ptr, stream):
+        """The select's kernels on `stream`: n_q elements of rel's dtype from out_ptr."""
+        I, D = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)
+        _lib.check(self.lib.of3d_rel_select(rel, self.rel_f64, *self.dims,
+                                            self.box.ctypes.data_as(I) if self.box is not None else None, self.n_q,
+                                            self.lo.ctypes.data_as(I), self.hi.ctypes.data_as(I),
+                                            self.gamma.ctypes.data_as(D), out_ptr, self.ws.data_ptr(),
+                                            stream or None))
+
+
+class _ProfileCall(_BoxCall):
+    """of3d_rel_profile bound to boxes: sizes and the decoding.  Its thresholds are the n_p
+    percentiles' and then the selection box's minimum and maximum (percentiles 0 and 100 of the
+    same select), so that one block holds everything the profile reports; the last two also are
+    the range of the auto edges."""
+
+    def __init__(self, boxes, dims, rel_f64, percentiles, nbins, edges):
+        super().__init__(boxes, dims, rel_f64)
+        self.percentiles, self.nbins, self.edges = list(percentiles), int(nbins), edges
+        self.n_t = len(self.percentiles) + 2
+        self.result_bytes = self.lib.of3d_rel_profile_result_bytes(len(self.boxes), self.n_t, self.nbins)
+        if self.result_bytes == 0:
+            raise ValueError("of3d: bad reliability profile sizes")
+
+    def enqueue(self, rel, thresh_ptr, result_ptr, stream):
+        """thresh_ptr: n_p + 2 device elements of rel's dtype (the percentiles', then min, max)."""
+        esz = 8 if self.rel_f64 else 4
+        given = self.edges.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if self.edges is not None else None
+        range_ptr = None if self.edges is not None else thresh_ptr + (self.n_t - 2) * esz
+        _lib.check(self.lib.of3d_rel_profile(rel, self.rel_f64, *self.dims, self.roi_arr, len(self.boxes), thresh_ptr,
+                                             self.n_t, self.nbins, given, range_ptr, result_ptr, stream or None))
+
+    def decode(self, words):
+        """The block's words (host int64) as reliability_profile's dict."""
+        words = np.ascontiguousarray(words, dtype=np.int64)
+        n_roi, n_p, nb = len(self.boxes), self.n_t - 2, self.nbins
+        assert tuple(words[:3]) == (n_roi, self.n_t, nb), words[:3]
+        rel_dt = np.dtype(np.float64 if self.rel_f64 else np.float32)
+        thr = words[3:3 + self.n_t].view(np.float64).astype(rel_dt)  # exact: they were rel_dt values
+        head = 3 + self.n_t + nb + 1
+        rw = 2 + self.n_t + nb
+        body = words[head:head + n_roi * rw].reshape(n_roi, rw)
+        out = {"percentiles": np.array(self.percentiles, dtype=np.float64), "thresholds": thr[:n_p].copy(),
+               "min": thr[n_p], "max": thr[n_p + 1], "rois": self.boxes.copy(),
+               "n_voxels": body[:, 0].copy(), "n_nan": body[:, 1].copy(), "n_above": body[:, 2:2 + n_p].copy(),
+               "hist": np.ascontiguousarray(body[:, 2 + self.n_t:]).view(np.uint64),
+               "edges": words[3 + self.n_t:head].view(np.float64).copy()}
+        out["fraction_above"] = out["n_above"] / out["n_voxels"][:, None].astype(np.float64)
+        return out
+
+
 def _pair_options(floor, combine):
     """Validated (floor, combine code) of the joint mask; ValueError on a bad value."""
     if not isinstance(combine, str) or combine not in COMBINE:
@@ -818,9 +1006,10 @@ def _pair_options(floor, combine):
     return floor, COMBINE[combine]
 
 
-def _pair_spec(shape, rel_percentile, rois, min_size, connectivity):
+def _pair_spec(shape, rel_percentile, rois, min_size, connectivity, percentile_box=None, percentile_method="linear"):
     """(boxes, dims, min_size, connectivity) of a two-channel call, validated by SummarySpec."""
-    spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
+    spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity,
+                       percentile_box=percentile_box, percentile_method=percentile_method)
     boxes = spec.resolve(shape)[0]
     min_size, connectivity = spec.opening(len(shape))
     if min_size < 1:
@@ -830,16 +1019,19 @@ def _pair_spec(shape, rel_percentile, rois, min_size, connectivity):
 
 
 class _PairCall(_BoxCall):
-    """The two-channel comparison of one frame bound to boxes and a device: two of3d_quantile,
+    """The two-channel comparison of one frame bound to boxes and a device: two of3d_quantile
+    (with a percentile_box or another percentile_method: two of3d_rel_select),
     of3d_mask_open_pair, then of3d_flow_pair.  Holds the boxes, sizes, workspaces, the keep volume
     and the result tensor: of3d_flow_pair's words, then the opening's 4 counts per box, then the
     two thresholds (one word each, in rel's dtype) — one small download."""
 
     def __init__(self, shape, rel_dtype, device, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None,
-                 bins=None, floor=0.0, combine="or", min_size=1, connectivity=None):
+                 bins=None, floor=0.0, combine="or", min_size=1, connectivity=None, percentile_box=None,
+                 percentile_method="linear"):
         import torch
 
-        boxes, dims, min_size, connectivity = _pair_spec(shape, rel_percentile, rois, min_size, connectivity)
+        boxes, dims, min_size, connectivity = _pair_spec(shape, rel_percentile, rois, min_size, connectivity,
+                                                         percentile_box, percentile_method)
         self.floor, self.combine = _pair_options(floor, combine)
         super().__init__(boxes, dims, rel_dtype == torch.float64)
         self._bind_bins(*SummarySpec._quantity_bins(bins, len(shape), "pair ", PAIR_QUANTITIES))
@@ -858,6 +1050,11 @@ class _PairCall(_BoxCall):
         self.result = torch.zeros((self.thresh_off + 16) // 8, dtype=torch.int64).to(device)
         self.n = int(np.prod(self.dims))
         self.ranks = _linear_ranks(self.n, rel_percentile, self.rel_dt)
+        # a crop or MATLAB's definition: each channel's own percentile over the same box, in place
+        self.select = None
+        if percentile_box is not None or percentile_method != "linear":
+            box = SummarySpec(percentile_box=percentile_box).threshold_request(shape)[0]
+            self.select = _SelectCall(self.dims, self.rel_f64, box, [float(rel_percentile)], percentile_method, device)
 
     @property
     def keep(self):
@@ -872,6 +1069,9 @@ class _PairCall(_BoxCall):
         lib, res = self.lib, self.result.data_ptr()
         t0, t1 = res + self.thresh_off, res + self.thresh_off + 8
         for rel, t in ((ptrs0[3], t0), (ptrs1[3], t1)):
+            if self.select is not None:
+                self.select.enqueue(rel, t, stream)
+                continue
             _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), t, self.qws.data_ptr(),
                                          stream or None))
         self.open.enqueue_pair(ptrs0[3], t0, ptrs1[3], t1, self.floor, self.combine, res + self.counts_off, stream)
@@ -976,6 +1176,27 @@ class _SummaryCall(_BoxCall):
         self.thresh = torch.empty(1, dtype=rel_dtype, device=device)
         self.n = int(np.prod(self.dims))
         self.ranks = _linear_ranks(self.n, spec.rel_percentile, _np_dtype(self.thresh))
+        self.thresh_ptr = self.thresh.data_ptr()
+        # a crop, MATLAB's definition or a profile: one of3d_rel_select for the profile's
+        # percentiles, the box's minimum and maximum and the summary's own percentile; then
+        # (rel_profile) of3d_rel_profile's block after the spread's
+        box, method, profile = spec.threshold_request(self.shape)
+        self.select, self.profile, self.profile_off = None, None, self.result_bytes
+        if box is not None or method != "linear" or profile is not None:
+            own = float(spec.rel_percentile)
+            sel = (list(profile[0]) + [0.0, 100.0]) if profile is not None else []
+            if own not in sel[:-2]:
+                sel.append(own)
+            if len(sel) > SELECT_MAX:
+                raise ValueError(f"summary: rel_percentile, the rel_profile percentiles and the extremes are "
+                                 f"{len(sel)} percentiles, one select takes {SELECT_MAX}: name rel_percentile among "
+                                 "the profile's")
+            self.select = _SelectCall(self.dims, self.rel_f64, box, sel, method, device)
+            self.thresh = torch.empty(len(sel), dtype=rel_dtype, device=device)
+            self.thresh_ptr = self.thresh.data_ptr() + sel.index(own) * self.thresh.element_size()
+            if profile is not None:
+                self.profile = _ProfileCall(self.boxes, self.dims, self.rel_f64, *profile)
+                self.result_bytes += self.profile.result_bytes
 
     def new_result(self, device):
         import torch
@@ -992,33 +1213,39 @@ class _SummaryCall(_BoxCall):
             raise ValueError("summary: contract_ptr goes with a contract request, and only with one")
         lo, hi, gamma = self.ranks
         lib, s = self.lib, self.spec
-        _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), self.thresh.data_ptr(),
-                                     self.qws.data_ptr(), stream or None))
-        args = (vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims, self.thresh.data_ptr(),
+        thresh_ptr = self.thresh_ptr
+        if self.select is None:
+            _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), thresh_ptr,
+                                         self.qws.data_ptr(), stream or None))
+        else:
+            self.select.enqueue(rel, self.thresh.data_ptr(), stream)
+        args = (vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims, thresh_ptr,
                 float(s.xyscale), float(s.zscale), float(s.tscale), self.roi_arr, len(self.boxes), self.nb_arr,
                 self.edge_arr, result_ptr, self.ws.data_ptr(), stream or None)
         if self.open is None:
             _lib.check(lib.of3d_flow_summary(*args))
         else:
-            self.open.enqueue(rel, self.thresh.data_ptr(), result_ptr + self.summary_bytes, stream)
+            self.open.enqueue(rel, thresh_ptr, result_ptr + self.summary_bytes, stream)
             _lib.check(lib.of3d_flow_summary_masked(*args, self.open.keep.data_ptr()))
         if self.axes is not None:
-            self.axes.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+            self.axes.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
                               self.open.keep.data_ptr() if self.open is not None else None,
                               result_ptr + self.axes_off, stream)
         if self.whist is not None:
-            self.whist.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+            self.whist.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
                                self.open.keep.data_ptr() if self.open is not None else None,
                                result_ptr + self.whist_off, stream)
         if self.spread is not None:
-            self.spread.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+            self.spread.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
                                 self.open.keep.data_ptr() if self.open is not None else None, result_ptr,
                                 self.nb_arr, result_ptr + self.spread_off, stream)
+        if self.profile is not None:
+            self.profile.enqueue(rel, self.thresh.data_ptr(), result_ptr + self.profile_off, stream)
         if self.quiver is not None:
-            self.quiver.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+            self.quiver.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
                                 self.open.keep.data_ptr() if self.open is not None else None, quiver_ptr, stream)
         if self.contract is not None:
-            self.contract.enqueue(vx, vy, vz, rel, v_f32, self.thresh.data_ptr(),
+            self.contract.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
                                   self.open.keep.data_ptr() if self.open is not None else None, contract_ptr,
                                   stream)
 
@@ -1050,21 +1277,110 @@ class _SummaryCall(_BoxCall):
             self.whist.decode(words[self.whist_off // 8:], out)
         if self.spread is not None:
             self.spread.decode(words[self.spread_off // 8:], out)
+        if self.profile is not None:
+            out["rel_profile"] = self.profile.decode(words[self.profile_off // 8:])
         return out
 
 
-def _thresholds_device(rels, rel_percentile, given):
+def _thresholds_device(rels, rel_percentile, given, percentile_box=None, percentile_method="linear"):
     """One threshold per rel field as a tensor of their dtype on their device: the `given` values,
-    or each field's rel_percentile-th percentile selected on the device (nothing goes to the host)."""
+    or each field's rel_percentile-th percentile selected on the device (nothing goes to the
+    host) — of the whole field by of3d_quantile, or with a percentile_box / another
+    percentile_method of that box of each field by of3d_rel_select."""
     import torch
 
     t = rels[0]
+    box, method, _ = SummarySpec(percentile_box=percentile_box,
+                                 percentile_method=percentile_method).threshold_request(tuple(t.shape))
     if given is not None:
         return torch.tensor([float(v) for v in given], dtype=t.dtype).to(t.device)
     thresh = torch.empty(len(rels), dtype=t.dtype, device=t.device)
     for i, r in enumerate(rels):
-        percentile_threshold_device(r, rel_percentile, out=thresh[i:i + 1])
+        if box is None and method == "linear":
+            percentile_threshold_device(r, rel_percentile, out=thresh[i:i + 1])
+        else:
+            reliability_thresholds(r, [rel_percentile], box=percentile_box, method=method, out=thresh[i:i + 1])
     return thresh
+
+
+def reliability_thresholds(rel, percentiles, box=None, method="linear", out=None):
+    """Percentiles of one box of rel as a tensor of len(percentiles) values of rel's dtype on rel's
+    device: the figure scripts' ``prctile(relCrop(:), relPer)`` of the cropped reliability
+    (plot_figure5.m:80-84, plot_figure3_ROIfigures.m:70-84) by of3d_rel_select — the volume is read
+    in place, all percentiles in one select, on the current stream with no synchronisation, so
+    every element is ready as a threshold for the next kernel on that stream.
+
+    rel: a float32 or float64 CUDA tensor, (nz, ny, nx) or (ny, nx).  percentiles: 1 to 8 values in
+    [0, 100], in any order (0 and 100 are the box's exact minimum and maximum).  box:
+    (z0, z1, y0, y1, x0, x1), or (y0, y1, x0, x1) in 2D, half-open; None: the whole volume.
+    method: "linear" (np.percentile's default) or "hazen" — np.percentile(..., method='hazen'),
+    which is MATLAB's prctile.  Each value equals ``np.percentile(crop, p, method=method)`` bit for
+    bit (-0.0 counts as +0.0); a NaN inside the box makes every value NaN, one outside is ignored."""
+    import torch
+
+    if not isinstance(rel, torch.Tensor) or not rel.is_cuda or rel.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rel must be a float32 or float64 CUDA tensor")
+    if rel.dim() not in (2, 3) or rel.numel() == 0:
+        raise ValueError("reliability_thresholds needs a non-empty (nz, ny, nx) or (ny, nx) field")
+    ps = _check_percentiles(percentiles, "percentiles")
+    shape = tuple(rel.shape)
+    b, method, _ = SummarySpec(percentile_box=box, percentile_method=method).threshold_request(shape)
+    tr = rel.contiguous()
+    if out is None:
+        out = torch.empty(len(ps), dtype=tr.dtype, device=tr.device)
+    elif (out.dtype != tr.dtype or out.device != tr.device or out.numel() != len(ps) or out.dim() != 1
+          or not out.is_contiguous()):
+        raise ValueError("out must be len(percentiles) contiguous elements of rel's dtype on rel's device")
+    dims = shape if len(shape) == 3 else (1,) + shape
+    call = _SelectCall(dims, tr.dtype == torch.float64, b, ps, method, tr.device)
+    call.enqueue(tr.data_ptr(), out.data_ptr(), torch.cuda.current_stream(tr.device).cuda_stream)
+    return out
+
+
+def reliability_profile(rel, percentiles=(85, 90, 95), box=None, method="linear", rois=None, bins=50, edges=None,
+                        device=None):
+    """What one needs to choose the reliability percentile (plot_figureS3_reliability.ipynb cells
+    4-8), reduced on the device: one select of `percentiles` plus 0 and 100 over `box`
+    (reliability_thresholds), then per ROI the voxels above each threshold and the histogram of rel
+    (of3d_rel_profile); one small download.
+
+    rel: numpy array or torch tensor, (nz, ny, nx) or (ny, nx), float32 or float64.  percentiles:
+    1 to 6 values; box and method as reliability_thresholds (the selection box; None: the whole
+    volume); rois as flow_summary (ROI 0 is the whole volume).  bins: the histogram's number of
+    equal bins (1 to 256) between the selection box's minimum and maximum,
+    ``np.histogram(rel.astype(float64), bins=np.linspace(float(min), float(max), bins + 1))`` — a
+    ROI's values outside that range are dropped, as np.histogram's `range` drops them; min == max
+    widens to min - 0.5, max + 0.5; a NaN or infinite min / max (a NaN in the selection box, an
+    infinite value) gives NaN edges and all-zero counts where numpy would raise.  edges: ascending
+    edges to use instead of `bins`.
+    Returns a dict of numpy values: percentiles, thresholds (rel's dtype), min and max of the
+    selection box, rois, per ROI n_voxels, n_nan, n_above (n_roi, n_percentiles: the voxels with
+    rel > threshold, compared in rel's dtype), fraction_above = n_above / n_voxels, hist
+    (n_roi, nbins) uint64 and edges (nbins + 1, float64).  Integer counts only: the same inputs
+    give the same bits on every run."""
+    import torch
+
+    host = isinstance(rel, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    shape = tuple(int(v) for v in rel.shape)
+    spec = SummarySpec(rois=rois, percentile_box=box, percentile_method=method,
+                       rel_profile=RelProfileSpec(percentiles=tuple(percentiles), bins=bins, edges=edges))
+    boxes = spec.resolve(shape)[0]
+    b, method, profile = spec.threshold_request(shape)
+    tr = _to_device(rel, host, dev)
+    if tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rel must be float32 or float64")
+    dims = shape if len(shape) == 3 else (1,) + shape
+    rel_f64 = tr.dtype == torch.float64
+    select = _SelectCall(dims, rel_f64, b, list(profile[0]) + [0.0, 100.0], method, tr.device)
+    call = _ProfileCall(boxes, dims, rel_f64, *profile)
+    with torch.cuda.device(tr.device):
+        stream = torch.cuda.current_stream(tr.device).cuda_stream
+        thresh = torch.empty(select.n_q, dtype=tr.dtype, device=tr.device)
+        res = torch.empty(call.result_bytes // 8, dtype=torch.int64, device=tr.device)
+        select.enqueue(tr.data_ptr(), thresh.data_ptr(), stream)
+        call.enqueue(tr.data_ptr(), thresh.data_ptr(), res.data_ptr(), stream)
+        return call.decode(res.cpu().numpy())
 
 
 def _mask_dict(keep, host, boxes, counts):
@@ -1082,7 +1398,8 @@ def _mask_dict(keep, host, boxes, counts):
     return out
 
 
-def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connectivity=None, rois=None, device=None):
+def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connectivity=None, rois=None, device=None,
+                     percentile_box=None, percentile_method="linear"):
     """The opened reliability mask of one frame, per ROI: MATLAB's
     ``bwareaopen(rel > relThresh, min_size, connectivity)`` of the reference's figure scripts
     (plot_figure5.m:87-88; principal_axes gives the regionprops3 step that follows it there) on
@@ -1096,7 +1413,10 @@ def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connect
     Returns a dict: keep (uint16, rel's shape; bit r set where the voxel lies in box r and in a
     component of at least min_size voxels of that box's mask; a torch tensor, numpy for numpy
     input), mask (r -> that bit plane as bool), rois, threshold and per ROI n_mask,
-    n_components, n_components_kept, n_kept (int64)."""
+    n_components, n_components_kept, n_kept (int64).
+    percentile_box, percentile_method (see SummarySpec): the percentile of that one box of rel,
+    read in place, by "linear" or "hazen" (MATLAB's prctile) — plot_figure5.m:80-84's
+    ``prctile(relCrop(:), relPer)`` (of3d_rel_select); the default is the whole field, "linear"."""
     import torch
 
     host = isinstance(rel, np.ndarray)
@@ -1114,7 +1434,8 @@ def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connect
     dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
     call = _OpenCall(boxes, dims, tr.dtype == torch.float64, min_size, connectivity, tr.device)
     with torch.cuda.device(tr.device):
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
+                                    percentile_box, percentile_method)
         counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tr.device)
         call.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(),
                      torch.cuda.current_stream(tr.device).cuda_stream)
@@ -1142,7 +1463,8 @@ def _rel_pair(rel0, rel1, device, what):
 
 
 def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor=0.0, combine="or", min_size=1,
-                           connectivity=None, rois=None, device=None):
+                           connectivity=None, rois=None, device=None, percentile_box=None,
+                           percentile_method="linear"):
     """The opened JOINT reliability mask of two channels of one frame, per ROI: figure 3's
     ``relMask = (rel > prctile(rel(:),relPer)) | (rel1 > prctile(rel1(:),relPer)); relMask =
     relMask & (rel > 0) & (rel1 > 0); relMask = bwareaopen(relMask, 10^5)``
@@ -1155,18 +1477,21 @@ def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor
     "and" of the two threshold tests.  A NaN in a field fails there; it also makes that channel's
     percentile NaN, whose test then fails everywhere.  min_size, connectivity, rois and the
     returned dict as reliability_mask, with `thresholds` (2 values of rel's dtype) in place of
-    `threshold`.  keep has reliability_mask's format: it feeds the same consumers."""
+    `threshold`.  keep has reliability_mask's format: it feeds the same consumers.
+    percentile_box, percentile_method as reliability_mask: each channel's own percentile over the
+    same box (plot_figure3_ROIfigures.m:70-84)."""
     import torch
 
     host, upload = _rel_pair(rel0, rel1, device, "joint_reliability_mask")
-    boxes, dims, min_size, connectivity = _pair_spec(tuple(rel0.shape), rel_percentile, rois, min_size, connectivity)
+    boxes, dims, min_size, connectivity = _pair_spec(tuple(rel0.shape), rel_percentile, rois, min_size, connectivity,
+                                                     percentile_box, percentile_method)
     floor, combine = _pair_options(floor, combine)
     if thresholds is not None and len(thresholds) != 2:
         raise ValueError("joint_reliability_mask: thresholds must be two values, one per channel")
     t0, t1 = upload()
     call = _OpenCall(boxes, dims, t0.dtype == torch.float64, min_size, connectivity, t0.device)
     with torch.cuda.device(t0.device):
-        thresh = _thresholds_device([t0, t1], rel_percentile, thresholds)
+        thresh = _thresholds_device([t0, t1], rel_percentile, thresholds, percentile_box, percentile_method)
         counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=t0.device)
         esz = thresh.element_size()
         call.enqueue_pair(t0.data_ptr(), thresh.data_ptr(), t1.data_ptr(), thresh.data_ptr() + esz, floor, combine,
@@ -1177,7 +1502,8 @@ def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor
 
 
 def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None, floor=0.0,
-                    combine="or", min_size=1, connectivity=None, in_plane=False, device=None):
+                    combine="or", min_size=1, connectivity=None, in_plane=False, device=None, percentile_box=None,
+                    percentile_method="linear"):
     """Two channels' flows of one frame compared over the same voxels, reduced on the device to
     a few kilobytes (one small device->host copy): figure 3 of the reference
     (plot_figure3_ROIfigures.m:67-193, plot_figure3_ChannelCompare.m:111-164).
@@ -1199,6 +1525,7 @@ def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale
     sum_diff (|v1 - v0|); the derived mean_dot, mean_cosine, dtheta_mean = atan2(sum_sin_dtheta,
     sum_cos_dtheta), mean_diff and magnitude_correlation (Pearson's r of the two magnitudes);
     hist[name] (n_roi, nbins) uint64 with edges[name].  An empty box gives NaN means.
+    percentile_box, percentile_method as joint_reliability_mask.
     Bit-reproducible: the same inputs give the same bits on every run."""
     import torch
 
@@ -1228,7 +1555,7 @@ def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale
         dev = ch0[3].device
     rel_dtype = torch.float64 if str(ch0[3].dtype).endswith("float64") else torch.float32
     call = _PairCall(shape, rel_dtype, dev, rel_percentile, xyscale, zscale, tscale, rois, bins, floor, combine,
-                     min_size, connectivity)
+                     min_size, connectivity, percentile_box, percentile_method)
     r0, r1 = upload_rel()
     t0, t1 = ([_to_device(a, host, dev) for a in ch[:3]] + [r] for ch, r in ((ch0, r0), (ch1, r1)))
     ptrs = lambda t: tuple(a.data_ptr() if a is not None else None for a in t)
@@ -1239,7 +1566,7 @@ def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale
 
 
 def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectivity=None, rois=None, physical=False,
-                   xyscale=1.0, zscale=1.0, device=None):
+                   xyscale=1.0, zscale=1.0, device=None, percentile_box=None, percentile_method="linear"):
     """The principal axes of one frame's reliability mask, per ROI: what the reference's
     plot_figure5.m:132-149 takes from ``regionprops3(relMask, 'EigenVectors', 'EigenValues')``,
     on the device (of3d_mask_axes); the mask-only part of flow_summary(axes="mask").
@@ -1251,7 +1578,8 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
     (n_roi, 10): n and the sums of x y z xx yy zz xy xz yz over box-local coordinates), centroid
     (x, y, z in volume coordinates), covariance (3, 3; population, exact numerators),
     axis_values (descending), axis_vectors (row k: e_k as x y z; largest component positive) and,
-    with min_size >= 1, the opening's counts.  An empty mask gives NaN."""
+    with min_size >= 1, the opening's counts.  An empty mask gives NaN.  percentile_box,
+    percentile_method as reliability_mask."""
     import torch
 
     host = isinstance(rel, np.ndarray)
@@ -1271,7 +1599,8 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
     opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tr.device) if min_size else None
     with torch.cuda.device(tr.device):
         stream = torch.cuda.current_stream(tr.device).cuda_stream
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
+                                    percentile_box, percentile_method)
         res = torch.empty(call.result_bytes // 8 + 4 * len(boxes), dtype=torch.int64, device=tr.device)
         counts_ptr = res.data_ptr() + call.result_bytes
         if opening is not None:
@@ -1289,7 +1618,7 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
 
 def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, bins=None,
                  device=None, min_size=0, connectivity=None, axes=None, axes_physical=False, axis_bins=None,
-                 weighted_bins=None, spread=None):
+                 weighted_bins=None, spread=None, percentile_box=None, percentile_method="linear", rel_profile=None):
     """One frame reduced on the device to a few kilobytes (one small device->host copy).
 
     Inputs as flow_statistics (numpy arrays or torch tensors, vz None for 2D).  The masking is
@@ -1325,6 +1654,10 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     and theta_std_all / phi_std_all with R * n_valid / n_voxels (the validation notebook divides by
     the array's size, NaNs included).  NaN where n_valid == 0.  By a centred pass of its own
     (of3d_flow_spread): std << |mean| loses nothing.
+    percentile_box, percentile_method (see SummarySpec): the threshold is the percentile of that
+    one box of rel, by "linear" or "hazen" (MATLAB's prctile), whatever `rois`.  rel_profile (a
+    RelProfileSpec): the dict also holds rel_profile, reliability_profile's dict for the same box
+    and method, from the same select.  Without the three the threshold is of3d_quantile's.
     Bit-reproducible: the same inputs give the same bits on every run."""
     import torch
 
@@ -1336,7 +1669,8 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     if tx.dim() != (3 if tz is not None else 2):
         raise ValueError("flow_summary needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
     spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale, min_size, connectivity, axes,
-                       axes_physical, axis_bins, weighted_bins=weighted_bins, spread=spread)
+                       axes_physical, axis_bins, weighted_bins=weighted_bins, spread=spread,
+                       percentile_box=percentile_box, percentile_method=percentile_method, rel_profile=rel_profile)
     call = _SummaryCall(spec, tuple(tx.shape), tr.dtype, tx.device)
     res = call.new_result(tx.device)
     call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
@@ -1353,7 +1687,8 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
 # the caller.
 # ---------------------------------------------------------------------------
 def quiver_sample(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, gap=2, rois=None,
-                  min_size=0, connectivity=None, threshold=None, max_vectors=65536, device=None):
+                  min_size=0, connectivity=None, threshold=None, max_vectors=65536, device=None, percentile_box=None,
+                  percentile_method="linear"):
     """The quiver vectors of one frame, per ROI: the voxels of the gap lattice
     ``[z0:z1:gz, y0:y1:gy, x0:x1:gx]`` of every ROI whose masked physical velocity is not NaN
     (flow_summary's validity), in C order, by of3d_quiver_sample; only the lists leave the device.
@@ -1362,7 +1697,8 @@ def quiver_sample(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, t
     tensors, vz None for 2D; ROI 0 is the whole volume); gap and max_vectors as QuiverSpec.  The
     threshold is the rel_percentile-th percentile of rel (percentile_threshold_device) unless
     `threshold` (a Python float, used as one element of rel's dtype) is given; min_size >= 1
-    opens every ROI's mask first (reliability_mask).
+    opens every ROI's mask first (reliability_mask); percentile_box, percentile_method as
+    reliability_mask.
     Returns a dict: threshold, rois (n_roi, 6), gap (gz, gy, gx) and samples, a list with one
     dict per ROI: zyx (int64 (n, 3), volume coordinates; z = 0 in 2D), v (float64 (n, 3): vx,
     vy, vz in physical units, vz 0.0 in 2D), magnitude, theta and (3D) phi (float64 (n,), formed
@@ -1392,7 +1728,8 @@ def quiver_sample(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, t
     opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tx.device) if min_size else None
     with torch.cuda.device(tx.device):
         stream = torch.cuda.current_stream(tx.device).cuda_stream
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
+                                    percentile_box, percentile_method)
         if opening is not None:
             counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tx.device)
             opening.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(), stream)
@@ -1458,7 +1795,8 @@ def read_quiver(path, ndim=3):
 # direction to that centre — on the resident fields, so that a series run with
 # save_fields=False still yields the figure's distributions.
 # ---------------------------------------------------------------------------
-def largest_component_mask(rel, rel_percentile=90, threshold=None, connectivity=None, rois=None, device=None):
+def largest_component_mask(rel, rel_percentile=90, threshold=None, connectivity=None, rois=None, device=None,
+                           percentile_box=None, percentile_method="linear"):
     """The largest connected component of the reliability mask of one frame, per ROI: the
     notebook's measure.label / sort by area / zero all but the first, on the device
     (of3d_mask_largest).  Among components of equal size the one holding the smallest linear
@@ -1468,7 +1806,8 @@ def largest_component_mask(rel, rel_percentile=90, threshold=None, connectivity=
     Arguments but min_size as reliability_mask's, and so is the returned dict: keep (uint16,
     rel's shape; bit r set where the voxel lies in box r and in that box's largest component),
     mask (r -> that bit plane as bool), rois, threshold and per ROI n_mask, n_components,
-    n_components_kept (0 or 1), n_kept (int64)."""
+    n_components_kept (0 or 1), n_kept (int64).  percentile_box, percentile_method as
+    reliability_mask."""
     import torch
 
     host = isinstance(rel, np.ndarray)
@@ -1483,7 +1822,8 @@ def largest_component_mask(rel, rel_percentile=90, threshold=None, connectivity=
     dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
     call = _LargestCall(boxes, dims, tr.dtype == torch.float64, connectivity, tr.device)
     with torch.cuda.device(tr.device):
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold])
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
+                                    percentile_box, percentile_method)
         counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tr.device)
         call.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(),
                      torch.cuda.current_stream(tr.device).cuda_stream)
@@ -1493,7 +1833,7 @@ def largest_component_mask(rel, rel_percentile=90, threshold=None, connectivity=
 
 
 def contractility(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, spec=None,
-                  device=None):
+                  device=None, percentile_box=None, percentile_method="linear"):
     """One frame's contractility per ROI (ROI 0 is the whole volume, `rois` follow), reduced on
     the device to a few hundred bytes: the mask's centroid and, over the valid voxels (the masked
     velocity's magnitude is not NaN, flow_summary's validity), the angle in degrees between the
@@ -1510,6 +1850,7 @@ def contractility(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, t
     the voxels with an angle, mean_angle, mean_dot, mean_inward, mean_speed (formed here from the
     sums; NaN where n_angle == 0), inward_fraction = n_inward / n_angle, and hist[name]
     (n_roi, nbins) uint64 with edges[name] for every quantity in spec.bins.
+    percentile_box, percentile_method as reliability_mask.
     A cosine that rounding left a last bit beyond +-1 gives exactly 0 or 180 degrees where the
     notebook's arccos gives NaN.  Bit-reproducible: the same inputs give the same bits on every run."""
     import torch
@@ -1530,7 +1871,7 @@ def contractility(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, t
                          tx.device)
     with torch.cuda.device(tx.device):
         stream = torch.cuda.current_stream(tx.device).cuda_stream
-        thresh = _thresholds_device([tr], rel_percentile, None)
+        thresh = _thresholds_device([tr], rel_percentile, None, percentile_box, percentile_method)
         res = call.new_result(tx.device)
         call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
                      tx.dtype == torch.float32, thresh.data_ptr(), None, res.data_ptr(), stream)
@@ -1623,6 +1964,26 @@ CSV_SPREAD_COLUMNS = (tuple("spread_center_" + k for k in SPREAD_COMPONENTS) + _
                       + ("vcov_xx", "vcov_yy", "vcov_zz", "vcov_xy", "vcov_xz", "vcov_yz"))
 
 
+# appended when the summaries carry a reliability profile (SummarySpec.rel_profile): these, then
+# per percentile p of the profile rel_p<p> (its threshold) and n_above_p<p> (int), <p> = format(p, "g")
+CSV_PROFILE_COLUMNS = ("rel_min", "rel_max", "rel_n_nan")
+
+
+def profile_columns(percentiles):
+    """The CSV columns of a reliability profile with these percentiles."""
+    return CSV_PROFILE_COLUMNS + tuple(f"{k}_p{format(float(p), 'g')}" for p in percentiles
+                                       for k in ("rel", "n_above"))
+
+
+def _profile_row(s, r):
+    """The profile_columns values of ROI r of a summary dict."""
+    p = s["rel_profile"]
+    row = [repr(float(p["min"])), repr(float(p["max"])), int(p["n_nan"][r])]
+    for k in range(len(p["percentiles"])):
+        row += [repr(float(p["thresholds"][k])), int(p["n_above"][r][k])]
+    return row
+
+
 def _spread_row(s, r):
     """The CSV_SPREAD_COLUMNS values of ROI r of a summary dict."""
     c = s["velocity_covariance"][r]
@@ -1645,16 +2006,22 @@ def write_summaries(prefix, frames, summaries):
     """<prefix>_summary.csv (one row per frame and ROI; floats as repr, so they read back
     exactly; the columns CSV_COLUMNS, then CSV_OPEN_COLUMNS when the summaries were made with
     min_size >= 1, then CSV_AXES_COLUMNS when they were made with axes, then CSV_SPREAD_COLUMNS
-    when they were made with spread) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
-    (frames, n_roi, nbins), and with weighted_bins wedges_<name>, weights_<name> float64 of that
-    shape) from flow_summary dicts of consecutive frames."""
+    when they were made with spread, then profile_columns(percentiles) when they were made with
+    rel_profile) and <prefix>_summary_hist.npz (frames, edges_<name>, counts_<name> of shape
+    (frames, n_roi, nbins), with weighted_bins wedges_<name>, weights_<name> float64 of that
+    shape, and with rel_profile counts_rel (frames, n_roi, nbins) and edges_rel (frames,
+    nbins + 1): the auto edges differ from frame to frame) from flow_summary dicts of
+    consecutive frames."""
     opened = bool(summaries) and all(k in summaries[0] for k in CSV_OPEN_COLUMNS)
     with_axes = bool(summaries) and "axes_used" in summaries[0]
     with_spread = bool(summaries) and "spread_center" in summaries[0]
+    with_profile = bool(summaries) and "rel_profile" in summaries[0]
     with open(prefix + "_summary.csv", "w", newline="") as f:
         f.write(",".join(CSV_COLUMNS + (CSV_OPEN_COLUMNS if opened else ())
                          + (CSV_AXES_COLUMNS if with_axes else ())
-                         + (CSV_SPREAD_COLUMNS if with_spread else ())) + "\n")
+                         + (CSV_SPREAD_COLUMNS if with_spread else ())
+                         + (profile_columns(summaries[0]["rel_profile"]["percentiles"]) if with_profile else ()))
+                + "\n")
         for frame, s in zip(frames, summaries):
             for r in range(len(s["rois"])):
                 row = [int(frame), r] + [int(v) for v in s["rois"][r]] + [repr(float(s["threshold"]))]
@@ -1666,6 +2033,8 @@ def write_summaries(prefix, frames, summaries):
                     row += _axes_row(s, r)
                 if with_spread:
                     row += _spread_row(s, r)
+                if with_profile:
+                    row += _profile_row(s, r)
                 f.write(",".join(str(v) for v in row) + "\n")
     arrays = {"frames": np.asarray(list(frames), dtype=np.int64)}
     if summaries:
@@ -1675,6 +2044,9 @@ def write_summaries(prefix, frames, summaries):
         for name, e in summaries[0].get("edges_weighted", {}).items():
             arrays["wedges_" + name] = e
             arrays["weights_" + name] = np.stack([s["hist_weighted"][name] for s in summaries])
+        if with_profile:
+            arrays["counts_rel"] = np.stack([s["rel_profile"]["hist"] for s in summaries])
+            arrays["edges_rel"] = np.stack([s["rel_profile"]["edges"] for s in summaries])
     np.savez(prefix + "_summary_hist.npz", **arrays)
 
 
@@ -1684,5 +2056,6 @@ def read_summary_csv(path):
         cols = f.readline().strip().split(",")
         rows = [line.strip().split(",") for line in f if line.strip()]
     ints = set(CSV_COLUMNS[:8]) | {"n_valid", "n_voxels"} | set(CSV_OPEN_COLUMNS) | set(CSV_AXES_INT_COLUMNS)
+    ints |= {"rel_n_nan"} | {c for c in cols if c.startswith("n_above_p")}
     return {c: np.array([int(r[i]) if c in ints else float(r[i]) for r in rows],
                         dtype=np.int64 if c in ints else np.float64) for i, c in enumerate(cols)}

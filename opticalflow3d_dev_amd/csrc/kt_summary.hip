@@ -10,6 +10,7 @@
 
 #include "../../include/of3d.h"
 #include "kernels.hpp"
+#include "radix_key.hpp"
 #include "summary_dev.hpp"
 
 namespace {
@@ -17,15 +18,12 @@ namespace {
 using u64 = unsigned long long;
 
 // ---------------------------------------------------------------------------
-// Radix select.  key(v): the order-preserving unsigned image of the float bits (sign bit set:
-// all bits flipped, else the sign bit set); -0.0 takes +0.0's key.  11-bit digits from the top:
-// float32 11 + 11 + 10 bits (3 passes), float64 5 x 11 + 9 bits (6 passes).  Both ranks are
-// narrowed at once: each carries its own key prefix and remaining rank; while the prefixes
-// agree one histogram serves both.
+// Radix select over radix_key.hpp's keys and 11-bit digits (float32 3 passes, float64 6).
+// Both ranks are narrowed at once: each carries its own key prefix and remaining rank; while
+// the prefixes agree one histogram serves both.
 // ---------------------------------------------------------------------------
-constexpr int kDigit = 11, kBins = 1 << kDigit;
+using of3dk::kDigit, of3dk::kBins, of3dk::kMaxPasses, of3dk::KeyOf, of3dk::digit_shift, of3dk::digit_width;  // radix_key.hpp
 constexpr int kSelThreads = 256;
-constexpr int kMaxPasses = 6;
 
 // workspace: state, then one histogram pair per pass (zeroed once per call)
 struct SelState {
@@ -36,42 +34,6 @@ struct SelState {
 };
 constexpr size_t kSelHistWords = (size_t)kMaxPasses * 2 * kBins;
 constexpr size_t kSelBytes = sizeof(SelState) + kSelHistWords * sizeof(u64);
-
-template <typename T>
-struct KeyOf;
-template <>
-struct KeyOf<float> {
-    static constexpr int bits = 32, passes = 3;
-    static __device__ __forceinline__ u64 key(float v) {
-        unsigned u = __float_as_uint(v);
-        if ((u << 1) == 0) u = 0;  // -0.0 -> +0.0
-        return (u & 0x80000000u) ? (unsigned)~u : (u | 0x80000000u);
-    }
-    static __device__ __forceinline__ float value(u64 k) {
-        const unsigned u = (unsigned)k;
-        return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-    }
-};
-template <>
-struct KeyOf<double> {
-    static constexpr int bits = 64, passes = 6;
-    static __device__ __forceinline__ u64 key(double v) {
-        u64 u = (u64)__double_as_longlong(v);
-        if ((u << 1) == 0) u = 0;
-        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-    }
-    static __device__ __forceinline__ double value(u64 k) {
-        return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-    }
-};
-
-// digit p of a `bits`-wide key: [shift, shift + width)
-__host__ __device__ constexpr int digit_shift(int bits, int p) {
-    return bits - (p + 1) * kDigit > 0 ? bits - (p + 1) * kDigit : 0;
-}
-__host__ __device__ constexpr int digit_width(int bits, int p) {
-    return bits - (p + 1) * kDigit >= 0 ? kDigit : bits - p * kDigit;
-}
 
 template <typename T>
 __global__ __launch_bounds__(kSelThreads) void k_sel_hist(const T* __restrict__ a, size_t n, int pass,
@@ -171,11 +133,7 @@ __global__ __launch_bounds__(kSelThreads) void k_sel_pick(int pass, SelState* __
         }
         if (pass == KeyOf<T>::passes - 1) {
             // numpy's _lerp in the array's dtype (method 'linear')
-            const T a = KeyOf<T>::value(pf[0]), b = KeyOf<T>::value(pf[1]);
-            const T g1 = (T)gamma;
-            // lo == hi: b == a and the same expression gives a — or NaN for an infinite a, as numpy's
-            const T diff = b - a;
-            T v = g1 < (T)0.5 ? a + diff * g1 : b - diff * ((T)1 - g1);
+            T v = of3dk::select_lerp<T>(KeyOf<T>::value(pf[0]), KeyOf<T>::value(pf[1]), gamma);
             if (st->n_nan) v = (T)__builtin_nan("");
             *out = v;
         }

@@ -2,7 +2,8 @@
 // summary_dev.hpp — the per-voxel device helpers shared by the frame summary (kt_summary.hip:
 // k_sum_boxes), the projected flow (kt_axes.hip: k_proj_boxes), the magnitude-weighted
 // histograms (kt_whist.hip: k_whist_boxes), the two-channel comparison (kt_pair.hip:
-// k_pair_boxes) and the spread (kt_spread.hip: k_spread_boxes): one statement of the masking arithmetic, the histogram bin search, the walk
+// k_pair_boxes), the spread (kt_spread.hip: k_spread_boxes) and the reliability profile
+// (kt_relsel.hip: k_rp_boxes): one statement of the masking arithmetic, the histogram bin search, the walk
 // over a box, a workgroup's share of a box and the reduction of its sums, so the passes cannot
 // drift apart.  The host side (box check, workgroup plan, histogram plan, edge upload) is
 // summary_host.hpp's.

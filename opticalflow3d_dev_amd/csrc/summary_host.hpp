@@ -1,6 +1,6 @@
 #pragma once
 // summary_host.hpp — the host side shared by the device-side summary passes (kt_summary.hip,
-// kt_ccl.hip, kt_axes.hip, kt_whist.hip, kt_pair.hip, kt_spread.hip): one statement of the box check, the
+// kt_ccl.hip, kt_axes.hip, kt_whist.hip, kt_pair.hip, kt_spread.hip, kt_relsel.hip): one statement of the box check, the
 // workgroup plan, the histogram plan with its edge validation, and the edge upload.  The entry
 // points keep their own order of argument checks; what a check tests and says is here.
 #include <hip/hip_runtime.h>
