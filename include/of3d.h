@@ -790,6 +790,16 @@ int of3d_rel_profile(const void* d_rel, int rel_f64, int64_t nz, int64_t ny, int
  * store for those tensors.  Enqueued on `stream`. */
 int of3d_rel3d(const double* tensor, int64_t n, void* rel, int rel_f64, void* stream);
 
+/* Fill the plan's device workspace (both field buffers) with `byte` on `stream`, and forget every
+ * temporal derivative an earlier call formed for a later one (execute_next's, execute_ahead's
+ * slots): the next execute call recomputes.  plan == NULL: the same for every plan the host
+ * entry points cache, their input and output staging included (synchronous).  Results of later
+ * calls must not change: between calls the workspace carries nothing but those tagged
+ * derivatives.  `byte` in [0, 255]; 0xFF makes every fp64 and fp32 element a NaN.  Returns 0 for
+ * a plan, the number of cached plans filled for NULL, negative on error.  For tests (no
+ * reference counterpart); never called on a product path. */
+int of3d_plan_poison(of3d_plan* plan, int byte, void* stream);
+
 /* Blocking copy of n buffers on the GPU's DMA (SDMA) engines through the HSA
  * runtime: no compute units and no HIP stream involved, so a download does
  * not contend with kernels for the memory pipeline.  Host buffers must be

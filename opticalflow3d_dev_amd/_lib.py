@@ -40,7 +40,7 @@ EXPORTED = (
     "of3d_copy_async", "of3d_dma_copy", "of3d_plan_set_timing_mask", "of3d_flow_stats",
     "of3d_plan_set_overlap", "of3d_cache_clear", "of3d_plan_set_rows",
     "of3d_plan_kernels", "of3d_build_info", "of3d_plan_execute_next", "of3d_plan_execute_ahead",
-    "of3d_rel3d", "of3d_plan_geometry",
+    "of3d_rel3d", "of3d_plan_geometry", "of3d_plan_poison",
     "of3d_quantile", "of3d_quantile_workspace_bytes", "of3d_flow_summary", "of3d_flow_summary_result_bytes",
     "of3d_flow_summary_workspace_bytes",
     "of3d_mask_open", "of3d_mask_open_workspace_bytes", "of3d_flow_summary_masked",
@@ -293,6 +293,8 @@ def load():
         lib.of3d_rel_profile.restype = ctypes.c_int
         lib.of3d_rel3d.argtypes = [P, i64, P, ctypes.c_int, P]
         lib.of3d_rel3d.restype = ctypes.c_int
+        lib.of3d_plan_poison.argtypes = [P, ctypes.c_int, P]
+        lib.of3d_plan_poison.restype = ctypes.c_int
         lib.of3d_copy_async.argtypes = [P, P, ctypes.c_size_t, ctypes.c_int, P]
         lib.of3d_copy_async.restype = ctypes.c_int
         lib.of3d_dma_copy.argtypes = [ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(ctypes.c_size_t),
@@ -305,6 +307,13 @@ def load():
 def cache_clear():
     """of3d_cache_clear: release the device workspaces cached by calc_flow3D / calc_flow2D."""
     check(load().of3d_cache_clear())
+
+
+def cache_poison(byte=0xFF):
+    """of3d_plan_poison(NULL): fill the workspaces and staging buffers of the plans calc_flow3D /
+    calc_flow2D cache with `byte` (tests: results of later calls must not change); returns the
+    number of cached plans it filled."""
+    return check(load().of3d_plan_poison(None, int(byte), None))
 
 
 def last_error() -> str:
@@ -409,6 +418,11 @@ class Plan:
     def set_rows(self, y0, y1):
         """of3d_plan_set_rows: outputs only rows [y0, y1), compact; raises where unsupported."""
         check(self.lib.of3d_plan_set_rows(self.handle, int(y0), int(y1)))
+
+    def poison(self, byte=0xFF, stream=0):
+        """of3d_plan_poison: fill the workspace with `byte` on `stream` and drop every pre-formed
+        temporal derivative (tests: results of later calls must not change)."""
+        check(self.lib.of3d_plan_poison(self.handle, int(byte), stream or None))
 
     def kernels(self):
         """of3d_plan_kernels: the kernel families this plan has launched so far."""

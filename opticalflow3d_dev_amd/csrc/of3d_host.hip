@@ -1862,6 +1862,36 @@ int of3d_rel3d(const double* tensor, int64_t n, void* rel, int rel_f64, void* st
     return 0;
 }
 
+namespace {
+// of3d_plan_poison for one plan: both field buffers filled on s, every pre-formed dt0 forgotten
+int poison_plan(of3d_plan* p, int byte, hipStream_t s) {
+    OF3D_HIP(hipSetDevice(p->device));
+    const size_t bytes = 9 * p->fs * elem_size(p);
+    OF3D_HIP(hipMemsetAsync(p->X, byte, bytes, s));
+    OF3D_HIP(hipMemsetAsync(p->Y, byte, bytes, s));
+    p->pipe.valid = false;
+    for (auto& d : p->dts) d.valid = false;
+    return 0;
+}
+}  // namespace
+
+int of3d_plan_poison(of3d_plan* p, int byte, void* stream) {
+    if (byte < 0 || byte > 255) return fail("of3d: poison byte must be in [0, 255]");
+    if (p) return poison_plan(p, byte, (hipStream_t)stream);
+    // the host entry points' plans: their streams are their own, so fill and wait under the lock
+    std::lock_guard<std::mutex> lk(g_cache_mu);
+    int filled = 0;  // the NULL form's result: cached plans filled (a test sees that its call met one)
+    for (auto& e : g_cache) {
+        of3d_plan* q = e.plan;
+        ++filled;
+        if (poison_plan(q, byte, q->stream)) return -1;
+        if (q->d_in) OF3D_HIP(hipMemsetAsync(q->d_in, byte, q->d_in_bytes, q->stream));
+        if (q->d_out) OF3D_HIP(hipMemsetAsync(q->d_out, byte, q->d_out_bytes, q->stream));
+        OF3D_HIP(hipStreamSynchronize(q->stream));
+    }
+    return filled;
+}
+
 int of3d_copy_async(void* dst, const void* src, size_t bytes, int max_blocks, void* stream) {
     if (bytes == 0) return 0;
     if (!dst || !src) return fail("of3d: null argument");

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import poison
 from opticalflow3d_dev_amd import _lib, calc_flow2D, make_taps, radii
 from oracle import cpu_ref
 
@@ -29,12 +30,13 @@ def _batch(series, s, t, w, zo0=None, zo1=None, mode=0):
     fp32 = bool(mode & _lib.OF3D_FP32)
     vt = torch.float32 if fp32 else torch.float64
     n = (zo1 - zo0) * ny * nx
-    vx, vy, rel = (torch.empty(n, dtype=vt, device=dev) for _ in range(3))
+    (vx, vy, rel), check_all = poison.guarded_set(n, [vt, vt, vt], dev, names=("vx", "vy", "rel"))
     plan = _lib.Plan(2, nout, ny, nx, make_taps(s, t, w), device=0, mode=mode)
     try:
         plan.execute([d_in[j].data_ptr() for j in range(nwin)], _lib.OF3D_U16, 0, zo0, zo1, vx.data_ptr(),
                      vy.data_ptr(), 0, rel.data_ptr())
         torch.cuda.synchronize(dev)
+        check_all(what=f"planes [{zo0}, {zo1})")  # every pixel of the batch written, nothing beside it
         kernels = plan.kernels()
     finally:
         plan.close()

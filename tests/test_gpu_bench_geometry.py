@@ -23,6 +23,7 @@ import os
 import numpy as np
 import pytest
 
+import poison
 from conftest import assert_rel_within, bits_equal, oracle3d
 
 pytestmark = pytest.mark.gpu
@@ -63,13 +64,13 @@ def run_plan(d_in, nz, ny, nx, s, t, w, mode=0, geo=None):
     fp32 = bool(mode & _lib.OF3D_FP32)
     n = nz * ny * nx
     vt = torch.float32 if fp32 else torch.float64
-    outs = [torch.full((n,), float("nan"), dtype=vt, device=dev) for _ in range(3)]
-    outs.append(torch.full((n,), float("nan"), dtype=torch.float32, device=dev))
+    outs, check_all = poison.guarded_set(n, [vt, vt, vt, torch.float32], dev)
     plan = _lib.Plan(3, nz, ny, nx, make_taps(s, t, w), device=dev.index, timing=4, mode=mode)
     try:
         plan.execute([d_in[i].data_ptr() for i in range(d_in.shape[0])], _lib.OF3D_U16, 0, 0, nz,
                      *[o.data_ptr() for o in outs], torch.cuda.current_stream(dev).cuda_stream)
         torch.cuda.synchronize(dev)
+        check_all()  # every voxel written, nothing beside the outputs
         kernels = plan.kernels()
         if geo is not None:
             geo.append(plan.geometry())

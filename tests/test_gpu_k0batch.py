@@ -7,6 +7,7 @@ streaming driver (FlowStream(k0_batch=M)) against the host entry point."""
 import numpy as np
 import pytest
 
+import poison
 from conftest import bits_equal
 from opticalflow3d_dev_amd import _lib, calc_flow3D, make_taps, radii
 
@@ -34,12 +35,12 @@ def _call(plan, frames, k, nwin, n_ahead, vt, reld, plain=False):
     import torch
 
     n = NZ * NY * NX
-    outs = [torch.full((n,), float("nan"), dtype=vt, device="cuda") for _ in range(3)]
-    outs.append(torch.full((n,), float("nan"), dtype=reld, device="cuda"))
+    outs, check_all = poison.guarded_set(n, [vt, vt, vt, reld], "cuda")
     ptrs = [f.data_ptr() for f in frames[k:k + nwin]]
     ahead = None if plain else [f.data_ptr() for f in frames[k + nwin:k + nwin + n_ahead]]
     plan.execute(ptrs, _lib.OF3D_U16, 0, 0, NZ, *[o.data_ptr() for o in outs], ahead_ptrs=ahead)
     torch.cuda.synchronize()
+    check_all(what=f"window {k}")  # everything written, nothing beside it
     return [o.cpu().numpy().reshape(NZ, NY, NX) for o in outs]
 
 
@@ -278,12 +279,12 @@ def test_zslab_subrange_batched(z0, z1):
     try:
         n = (z1 - z0) * NY * NX
         for k in range(stack.shape[0] - nwin + 1):
-            outs = [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda") for _ in range(3)]
-            outs.append(torch.full((n,), float("nan"), dtype=torch.float32, device="cuda"))
+            outs, check_all = poison.guarded_set(n, [torch.float64] * 3 + [torch.float32], "cuda")
             ptrs = [f.data_ptr() for f in frames[k:k + nwin]]
             ahead = [f.data_ptr() for f in frames[k + nwin:k + nwin + 3]]
             plan.execute(ptrs, _lib.OF3D_U16, zi0, z0, z1, *[o.data_ptr() for o in outs], ahead_ptrs=ahead)
             torch.cuda.synchronize()
+            check_all(what=f"window {k} planes [{z0}, {z1})")
             full = calc_flow3D(stack[k:k + nwin], s, t, w)
             for a, b in zip(outs, full):
                 assert bits_equal(a.cpu().numpy().reshape(z1 - z0, NY, NX), b[z0:z1]), (k, z0, z1)

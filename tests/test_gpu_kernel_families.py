@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import poison
 from opticalflow3d_dev_amd import _lib, make_taps, radii
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,10 @@ FAMILY_ENV = ("OF3D_K34", "OF3D_K5C", "OF3D_K1C", "OF3D_K12", "OF3D_K5C_NW", "OF
 def _run(img, s, t, w, ndim, mode, old, force=None, kernels=None, geometry=None):
     """One execution of a fresh plan under the kernel-family switches (old: every FAMILY_ENV
     switch 0; force: switches set on top); kernels (a list) and geometry (a dict) receive
-    plan.kernels() and plan.geometry() after the execution: what actually ran."""
+    plan.kernels() and plan.geometry() after the execution: what actually ran.  The outputs
+    sit between guard runs of a sentinel (poison.guarded): nothing may be left unwritten, and
+    nothing written outside — the family-vs-family comparisons cannot pass on what the
+    other family's run left in the allocator's block."""
     import torch
 
     saved = {k: os.environ.get(k) for k in FAMILY_ENV}
@@ -43,14 +47,14 @@ def _run(img, s, t, w, ndim, mode, old, force=None, kernels=None, geometry=None)
         fp32 = bool(mode & _lib.OF3D_FP32)
         vt = torch.float32 if fp32 else torch.float64
         n = nz * ny * nx
-        outs = [torch.empty(n, dtype=vt, device=dev) for _ in range(3)]
-        rel = torch.empty(n, dtype=torch.float64 if (ndim == 2 and not fp32) else (vt if ndim == 2 else torch.float32),
-                          device=dev)
+        reld = torch.float64 if (ndim == 2 and not fp32) else (vt if ndim == 2 else torch.float32)
+        (*outs, rel), check_all = poison.guarded_set(n, [vt, vt, vt, reld], dev)
         plan = _lib.Plan(ndim, nz, ny, nx, make_taps(s, t, w), device=0, mode=mode)
         try:
             plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.OF3D_U16, 0, 0, nz,
                          outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), rel.data_ptr())
             torch.cuda.synchronize(dev)
+            check_all(used=(0, 1, 2, 3) if ndim == 3 else (0, 1, 3))  # (2D: no vz)
             if kernels is not None:
                 kernels.extend(plan.kernels())
             if geometry is not None:

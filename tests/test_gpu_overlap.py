@@ -7,6 +7,7 @@ and ones that leave a ragged last chunk, and chunks thinner than the W-z halo.""
 import numpy as np
 import pytest
 
+import poison
 from conftest import bits_equal
 from opticalflow3d_dev_amd import _lib, make_taps, radii
 from oracle import cpu_ref
@@ -26,8 +27,7 @@ def _run_plan(img, s, t, w, chunk, z0=0, z1=None, mode=0, timing_stage=None):
     fp32 = bool(mode & _lib.OF3D_FP32)
     vt = torch.float32 if fp32 else torch.float64
     n = (z1 - z0) * ny * nx
-    outs = [torch.full((n,), float("nan"), dtype=vt, device=dev) for _ in range(3)]
-    rel = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+    (*outs, rel), check_all = poison.guarded_set(n, [vt, vt, vt, torch.float32], dev)
     plan = _lib.Plan(3, nz, ny, nx, make_taps(s, t, w), device=0, mode=mode, timing=4 if timing_stage else 0)
     try:
         plan.set_overlap(chunk)
@@ -36,6 +36,7 @@ def _run_plan(img, s, t, w, chunk, z0=0, z1=None, mode=0, timing_stage=None):
         plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.OF3D_U16, 0, z0, z1,
                      outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), rel.data_ptr())
         torch.cuda.synchronize(dev)
+        check_all(what=f"chunk {chunk} planes [{z0}, {z1})")  # every chunk's planes written, nothing beside them
         times = plan.stage_times() if timing_stage else None
     finally:
         plan.close()

@@ -11,6 +11,7 @@ Tolerances:
 import numpy as np
 import pytest
 
+import poison
 from conftest import bits_equal, golden_cases, load_golden
 from opticalflow3d_dev_amd import calc_flow2D, calc_flow3D
 from opticalflow3d_dev_amd.calc_flow import _flow3d
@@ -193,13 +194,13 @@ def test_seeded_3d_fused_gradients_ran(case, monkeypatch):
     win = np.ascontiguousarray(img[c - rt:c + rt + 1])
     d_in = torch.from_numpy(win.view(np.uint8).reshape(2 * rt + 1, -1)).to("cuda")
     n = nz * ny * nx
-    outs = [torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(3)]
-    d_rel = torch.empty(n, dtype=torch.float32, device="cuda")
+    (*outs, d_rel), check_all = poison.guarded_set(n, [torch.float64] * 3 + [torch.float32], "cuda")
     plan = _lib.Plan(3, nz, ny, nx, make_taps(s, t, w), device=0)
     try:
         plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.DTYPE_CODES[img.dtype], 0, 0, nz,
                      outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), d_rel.data_ptr())
         torch.cuda.synchronize()
+        check_all()  # every voxel written, nothing beside the outputs
         used = plan.kernels()
     finally:
         plan.close()

@@ -7,6 +7,7 @@ streaming driver's lookahead ring (stream.FlowStream) against the host entry poi
 import numpy as np
 import pytest
 
+import poison
 from conftest import bits_equal
 from opticalflow3d_dev_amd import _lib, calc_flow3D, make_taps, radii
 
@@ -25,13 +26,13 @@ def _run(plan, dev_frames, z0, z1, nvox_shape, vt, calls, rt_dtype=None):
     res = []
     for w, nw, pipe in calls:
         n = int(np.prod(nvox_shape))
-        outs = [torch.full((n,), float("nan"), dtype=vt, device="cuda") for _ in range(3)]
-        outs.append(torch.full((n,), float("nan"), dtype=rt_dtype or torch.float32, device="cuda"))
+        outs, check_all = poison.guarded_set(n, [vt, vt, vt, rt_dtype or torch.float32], "cuda")
         ptrs = [f.data_ptr() for f in dev_frames[w]]
         nxt = [f.data_ptr() for f in dev_frames[nw]] if nw is not None else None
         plan.execute(ptrs, _lib.OF3D_U16, 0 if z0 is None else z0[0], z1[0], z1[1],
                      *[o.data_ptr() for o in outs], next_ptrs=nxt, pipelined=pipe)
         torch.cuda.synchronize()
+        check_all(what=f"window {w}")  # everything written, nothing beside it
         res.append([o.cpu().numpy().reshape(nvox_shape) for o in outs])
     return res
 

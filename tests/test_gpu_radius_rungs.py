@@ -39,6 +39,7 @@ the window already needs 11 rows per thread.)"""
 import numpy as np
 import pytest
 
+import poison
 from conftest import assert_rel_within, bits_equal, oracle3d
 from opticalflow3d_dev_amd import _lib, make_taps, radii
 from oracle import cpu_ref
@@ -106,14 +107,14 @@ def _run(img, taps, ndim, mode, zout=None, max_out_planes=0):
     else:
         rt_ = torch.float64 if mode & _lib.OF3D_REL_F64 else torch.float32
     n = (z1 - z0) * ny * nx
-    outs = [torch.empty(n, dtype=vt, device=dev) for _ in range(3)]
-    rel = torch.empty(n, dtype=rt_, device=dev)
+    (*outs, rel), check_all = poison.guarded_set(n, [vt, vt, vt, rt_], dev)
     plan = _lib.Plan(ndim, nz, ny, nx, taps, device=0, mode=mode, max_out_planes=max_out_planes)
     try:
         zin = plan.input_range(z0, z1)
         plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.DTYPE_CODES[img.dtype], 0, z0, z1,
                      outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), rel.data_ptr())
         torch.cuda.synchronize(dev)
+        check_all(used=(0, 1, 2, 3) if ndim == 3 else (0, 1, 3))  # everything written, nothing beside it
         kernels, geom = plan.kernels(), plan.geometry()
     finally:
         plan.close()

@@ -4,6 +4,7 @@ than the stencil halo; the C-ABI's input range equals shard.halo_planes."""
 import numpy as np
 import pytest
 
+import poison
 from conftest import bits_equal
 from opticalflow3d_dev_amd import _lib, calc_flow3D, make_taps, radii
 from opticalflow3d_dev_amd.shard import flow3d_zslabs_host, halo_planes, zslab_bounds
@@ -125,11 +126,11 @@ def test_plan_output_rows(rows, fp32):
             if (r0, r1) != (0, 60):
                 plan.set_rows(r0, r1)
             n = 20 * (r1 - r0) * 40
-            outs = [torch.empty(n, dtype=vt, device=dev) for _ in range(3)] + [torch.empty(n, dtype=torch.float32,
-                                                                                          device=dev)]
+            outs, check_all = poison.guarded_set(n, [vt, vt, vt, torch.float32], dev)
             plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.OF3D_U16, 0, 0, 20,
                          *[o.data_ptr() for o in outs])
             torch.cuda.synchronize(dev)
+            check_all(what=f"rows [{r0}, {r1})")  # the compact outputs: all written, nothing beside them
             return [o.cpu().numpy().reshape(20, r1 - r0, 40) for o in outs]
         finally:
             plan.close()
@@ -165,11 +166,11 @@ def test_plan_output_rows_z_tiled(rows, fp32, monkeypatch):
             if (r0, r1) != (0, ny):
                 plan.set_rows(r0, r1)
             n = nz * (r1 - r0) * nx
-            outs = [torch.empty(n, dtype=vt, device=dev) for _ in range(3)] + [torch.empty(n, dtype=torch.float32,
-                                                                                          device=dev)]
+            outs, check_all = poison.guarded_set(n, [vt, vt, vt, torch.float32], dev)
             plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.OF3D_U16, 0, 0, nz,
                          *[o.data_ptr() for o in outs])
             torch.cuda.synchronize(dev)
+            check_all(what=f"rows [{r0}, {r1}) tile {tile}")
             return [o.cpu().numpy().reshape(nz, r1 - r0, nx) for o in outs]
         finally:
             plan.close()
