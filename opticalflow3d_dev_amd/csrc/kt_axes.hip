@@ -271,9 +271,6 @@ __global__ __launch_bounds__(64) void k_axes(AxParams P, GivenAxes given, u64* _
 // Projection.  k_sum_boxes' partition, masking and reduction (summary_dev.hpp, kt_summary.hip)
 // with p_k = (vx*e_k.x + vy*e_k.y) + vz*e_k.z in place of its eight quantities.
 // ---------------------------------------------------------------------------
-// The kernel spells out its share of the box and its reduction where k_sum_boxes, k_whist_boxes
-// and k_pair_boxes call of3dk::box_share, reduce_to_slot and flush_hist (the same statements):
-// with the helpers the register allocation of three of its eight instances moves by two VGPRs.
 template <typename VT, typename RelT, bool Masked>
 __global__ __launch_bounds__(kSumThreads) void k_proj_boxes(const VT* __restrict__ vx, const VT* __restrict__ vy,
                                                             const VT* __restrict__ vz, const RelT* __restrict__ rel,
@@ -304,79 +301,32 @@ __global__ __launch_bounds__(kSumThreads) void k_proj_boxes(const VT* __restrict
 #pragma unroll
         for (int i = 0; i < 3; ++i) ax[k][i] = __longlong_as_double((long long)rr[kWUsed + 3 * k + i]);
 
-    const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
-    const unsigned dy = P.box[roi][3] - y0, dx = P.box[roi][5] - x0;
-    const long long R = (long long)(P.box[roi][1] - z0) * dy;
-    const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
-    const long long count = (r1 - r0) * dx;  // this workgroup's voxels (< 2^31: checked on the host)
-    of3dk::BoxWalk w(dy, dx, r0, threadIdx.x, kSumThreads);
-    const double thr = Masked ? 0.0 : (double)*thr_p;
-    const bool is3 = vz != nullptr;
+    of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
+    const of3dk::FlowFields<VT, RelT, Masked> F{vx,    vy,   vz,   rel, keep,         Masked ? 0.0 : (double)*thr_p,
+                                                P.sxy, P.sz, P.st, roi, vz != nullptr};
+    const bool is3 = F.is3;
     double acc[kNA] = {0, 0, 0};
     unsigned nvalid = 0;
 
-    constexpr int U = 4;
-    for (long long e = threadIdx.x; e < count; e += (long long)U * kSumThreads) {
-        double fx[U], fy[U], fz[U], fr[U];
-        bool in[U];
+    // no root is taken: the sum of squares says whether the voxel is valid
+    of3dk::for_valid_voxels(F, sh, [&](const of3dk::Voxel& v, unsigned, unsigned, unsigned) {
+        ++nvalid;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            in[u] = e + (long long)u * kSumThreads < count;
-            fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
-            if (in[u]) {
-                const size_t i = ((size_t)(z0 + w.z) * P.ny + (y0 + w.y)) * P.nx + (x0 + w.x);
-                if constexpr (Masked)
-                    fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
-                else
-                    fr[u] = (double)rel[i];
-                fx[u] = (double)vx[i];
-                fy[u] = (double)vy[i];
-                if (is3) fz[u] = (double)vz[i];
-            }
-            w.advance();
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (!in[u]) continue;
-            const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;
-            const double vxp = of3dk::masked_velocity(fx[u], m, P.sxy, P.st);
-            const double vyp = of3dk::masked_velocity(fy[u], m, P.sxy, P.st);
-            const double vzp = is3 ? of3dk::masked_velocity(fz[u], m, P.sz, P.st) : 0.0;
-            // valid <=> the magnitude is not NaN; sqrt keeps the NaN-ness of its argument
-            const double xy2 = vxp * vxp + vyp * vyp;
-            const double m2 = is3 ? xy2 + vzp * vzp : xy2;
-            if (m2 != m2) continue;
-            ++nvalid;
-#pragma unroll
-            for (int k = 0; k < kNA; ++k) {
-                const double xy = vxp * ax[k][0] + vyp * ax[k][1];
-                const double p = is3 ? xy + vzp * ax[k][2] : xy;
-                acc[k] += p;
-                if (P.nbins[k]) {
-                    const int b = of3dk::find_bin(edges + P.eoff[k], P.nbins[k], p);
-                    if (b >= 0) atomicAdd(&hist[P.hoff[k] + b], 1u);
-                }
+        for (int k = 0; k < kNA; ++k) {
+            const double xy = v.vxp * ax[k][0] + v.vyp * ax[k][1];
+            const double p = is3 ? xy + v.vzp * ax[k][2] : xy;
+            acc[k] += p;
+            if (P.nbins[k]) {
+                const int b = of3dk::find_bin(edges + P.eoff[k], P.nbins[k], p);
+                if (b >= 0) atomicAdd(&hist[P.hoff[k] + b], 1u);
             }
         }
-    }
+    });
 
-    // lanes: the fixed shuffle tree; waves: the partials added in wave order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < kNA; ++q) {
-        const double v = of3dk::wave_sum(acc[q]);
-        if (lane == 0) wsum[wave][q] = v;
-    }
     if (nvalid) atomicAdd(&nvalid_s, nvalid);
-    __syncthreads();
-    if (threadIdx.x < kNA) {
-        double v = wsum[0][threadIdx.x];
-        for (int i = 1; i < kSumWaves; ++i) v += wsum[i][threadIdx.x];
-        slots[((size_t)roi * kSumMaxBlocks + blockIdx.x) * kNA + threadIdx.x] = v;
-    }
+    of3dk::reduce_to_slot(acc, wsum, slots + ((size_t)roi * kSumMaxBlocks + blockIdx.x) * kNA);
     if (threadIdx.x == 0 && nvalid_s) atomicAdd(&rr[kWValid], (u64)nvalid_s);
-    for (int i = threadIdx.x; i < ntot; i += kSumThreads)
-        if (hist[i]) atomicAdd(&rr[kAxHead + i], (u64)hist[i]);
+    of3dk::flush_hist(hist, ntot, rr + kAxHead);
 }
 
 // One workgroup per box: its slots staged in LDS, then added in index order.
@@ -432,9 +382,7 @@ int of3d_mask_axes(const void* vx, const void* vy, const void* vz, const void* r
     if (!rois || !d_result || !workspace || (!d_keep && (!rel || !d_thresh)) || (project && !vy) ||
         (!project && (vy || vz)))
         return of3dk::set_error("of3d: null argument");
-    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
-        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
-    if (project && !vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (of3dk::check_volume(nz, ny, nx, project && !vz) != 0) return -1;
     if (!of3dk::bins_ok<kNA>(nbins3)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     if (!project && (nbins3[0] || nbins3[1] || nbins3[2]))
         return of3dk::set_error("of3d: axis histograms need the velocity fields");
@@ -483,25 +431,17 @@ int of3d_mask_axes(const void* vx, const void* vy, const void* vz, const void* r
         hipLaunchKernelGGL((k_mom_boxes<float, false>), mgrid, mblock, 0, s, (const float*)rel,
                            (const float*)d_thresh, d_keep, P, res);
     hipLaunchKernelGGL(k_axes, dim3(n_roi), dim3(64), 0, s, P, given, res);
-    if (project) {
-        auto launch = [&](auto vt, auto rt) {
+    if (project)
+        of3dk::with_flow_types(v_f32, rel_f64, d_keep != nullptr, [&](auto vt, auto rt, auto masked_c) {
             using VT = decltype(vt);
             using RT = decltype(rt);
-            if (d_keep)
-                hipLaunchKernelGGL((k_proj_boxes<VT, RT, true>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
-                                   (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh,
-                                   d_keep, P, (const double*)d_edges, slots, res);
-            else
-                hipLaunchKernelGGL((k_proj_boxes<VT, RT, false>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
-                                   (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh,
-                                   d_keep, P, (const double*)d_edges, slots, res);
-            hipLaunchKernelGGL(k_proj_final, dim3(n_roi), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, P, res);
-        };
-        if (v_f32)
-            rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
-        else
-            rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
-    }
+            constexpr bool M = decltype(masked_c)::value;
+            hipLaunchKernelGGL((k_proj_boxes<VT, RT, M>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s, (const VT*)vx,
+                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P,
+                               (const double*)d_edges, slots, res);
+            hipLaunchKernelGGL(k_proj_final, dim3(n_roi), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, P,
+                               res);
+        });
     OF3DK_HIP(hipGetLastError());
     return 0;
 }

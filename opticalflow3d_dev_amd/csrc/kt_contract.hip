@@ -95,73 +95,42 @@ __global__ __launch_bounds__(kSumThreads) void k_ct_boxes(const VT* __restrict__
     const double czs = __longlong_as_double((long long)rr[kWUsed + 2]) * P.sz;
 
     of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
-    const long long count = sh.count;
-    const double thr = Masked ? 0.0 : (double)*thr_p;
-    const bool is3 = vz != nullptr;
+    const of3dk::FlowFields<VT, RelT, Masked> F{vx,    vy,   vz,   rel, keep,         Masked ? 0.0 : (double)*thr_p,
+                                                P.sxy, P.sz, P.st, roi, vz != nullptr};
+    const bool is3 = F.is3;
     double acc[kNSum] = {0, 0, 0, 0};
     unsigned nvalid = 0, nangle = 0, ninward = 0;
 
-    constexpr int U = 4;
-    for (long long e = threadIdx.x; e < count; e += (long long)U * kSumThreads) {
-        double fx[U], fy[U], fz[U], fr[U];
-        unsigned kx[U], ky[U], kz[U];
-        bool in[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            in[u] = e + (long long)u * kSumThreads < count;
-            fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
-            kx[u] = sh.w.x, ky[u] = sh.w.y, kz[u] = sh.w.z;
-            if (in[u]) {
-                const size_t i = sh.index();
-                if constexpr (Masked)
-                    fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
-                else
-                    fr[u] = (double)rel[i];
-                fx[u] = (double)vx[i];
-                fy[u] = (double)vy[i];
-                if (is3) fz[u] = (double)vz[i];
-            }
-            sh.w.advance();
+    of3dk::for_valid_voxels(F, sh, [&](const of3dk::Voxel& v, unsigned kx, unsigned ky, unsigned kz) {
+        const double vxp = v.vxp, vyp = v.vyp, vzp = v.vzp, speed = sqrt(v.sq);
+        ++nvalid;
+        // the notebook's expression trees, plain multiplies and adds in this order
+        const double dx = (double)kx * P.sxy - cxs;
+        const double dy = (double)ky * P.sxy - cys;
+        const double dz = (double)kz * P.sz - czs;
+        const double d2 = dx * dx + dy * dy;
+        const double nd = is3 ? sqrt(d2 + dz * dz) : sqrt(d2);
+        const double xy = (vxp / speed) * (-dx / nd) + (vyp / speed) * (-dy / nd);
+        const double dot = is3 ? xy + (vzp / speed) * (-dz / nd) : xy;
+        if (dot != dot) return;  // nd == 0 (the centre's own voxel) or no centre: no direction
+        ++nangle;
+        ninward += dot > 0.0;
+        // stated deviation: numpy's arccos gives NaN a last bit beyond +-1, this gives 0 / 180
+        const double angle = acos(fmin(fmax(dot, -1.0), 1.0)) * kDegrees;
+        const double inward = speed * dot;
+        acc[0] += angle;
+        acc[1] += dot;
+        acc[2] += inward;
+        acc[3] += speed;
+        if (P.nbins[0]) {
+            const int b = of3dk::find_bin(edges + P.eoff[0], P.nbins[0], angle);
+            if (b >= 0) atomicAdd(&hist[P.hoff[0] + b], 1u);
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (!in[u]) continue;
-            const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
-            const double vxp = of3dk::masked_velocity(fx[u], m, P.sxy, P.st);
-            const double vyp = of3dk::masked_velocity(fy[u], m, P.sxy, P.st);
-            const double vzp = is3 ? of3dk::masked_velocity(fz[u], m, P.sz, P.st) : 0.0;
-            const double xy2 = vxp * vxp + vyp * vyp;
-            const double speed = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
-            if (speed != speed) continue;  // valid <=> the magnitude is not NaN
-            ++nvalid;
-            // the notebook's expression trees, plain multiplies and adds in this order
-            const double dx = (double)kx[u] * P.sxy - cxs;
-            const double dy = (double)ky[u] * P.sxy - cys;
-            const double dz = (double)kz[u] * P.sz - czs;
-            const double d2 = dx * dx + dy * dy;
-            const double nd = is3 ? sqrt(d2 + dz * dz) : sqrt(d2);
-            const double xy = (vxp / speed) * (-dx / nd) + (vyp / speed) * (-dy / nd);
-            const double dot = is3 ? xy + (vzp / speed) * (-dz / nd) : xy;
-            if (dot != dot) continue;  // nd == 0 (the centre's own voxel) or no centre: no direction
-            ++nangle;
-            ninward += dot > 0.0;
-            // stated deviation: numpy's arccos gives NaN a last bit beyond +-1, this gives 0 / 180
-            const double angle = acos(fmin(fmax(dot, -1.0), 1.0)) * kDegrees;
-            const double inward = speed * dot;
-            acc[0] += angle;
-            acc[1] += dot;
-            acc[2] += inward;
-            acc[3] += speed;
-            if (P.nbins[0]) {
-                const int b = of3dk::find_bin(edges + P.eoff[0], P.nbins[0], angle);
-                if (b >= 0) atomicAdd(&hist[P.hoff[0] + b], 1u);
-            }
-            if (P.nbins[1]) {
-                const int b = of3dk::find_bin(edges + P.eoff[1], P.nbins[1], inward);
-                if (b >= 0) atomicAdd(&hist[P.hoff[1] + b], 1u);
-            }
+        if (P.nbins[1]) {
+            const int b = of3dk::find_bin(edges + P.eoff[1], P.nbins[1], inward);
+            if (b >= 0) atomicAdd(&hist[P.hoff[1] + b], 1u);
         }
-    }
+    });
 
     if (nvalid) atomicAdd(&count_s[0], nvalid);
     if (nangle) atomicAdd(&count_s[1], nangle);
@@ -208,9 +177,7 @@ int of3d_flow_contract(const void* vx, const void* vy, const void* vz, const voi
                        void* workspace, void* stream) {
     if (!vx || !vy || !rois || !d_result || !workspace || (!d_keep && (!rel || !d_thresh)))
         return of3dk::set_error("of3d: null argument");
-    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
-        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
-    if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (of3dk::check_volume(nz, ny, nx, !vz) != 0) return -1;
     if (vz && nz == 1) return of3dk::set_error("of3d: a 2D volume (nz == 1) takes no vz");
     if (!of3dk::bins_ok<kNQ>(nbins2)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     CtParams P{};
@@ -249,22 +216,14 @@ int of3d_flow_contract(const void* vx, const void* vy, const void* vz, const voi
     of3dk::put_edges(s, d_edges, host_edges, eo);
     hipLaunchKernelGGL(k_ct_centre, dim3(n_roi), dim3(64), 0, s, (const u64*)mom, given, kCtHead + P.ntot, res);
     const dim3 grid(max_nb, n_roi);
-    auto launch = [&](auto vt, auto rt) {
+    of3dk::with_flow_types(v_f32, rel_f64, d_keep != nullptr, [&](auto vt, auto rt, auto masked_c) {
         using VT = decltype(vt);
         using RT = decltype(rt);
-        if (d_keep)
-            hipLaunchKernelGGL((k_ct_boxes<VT, RT, true>), grid, dim3(kSumThreads), 0, s, (const VT*)vx, (const VT*)vy,
-                               (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, (const double*)d_edges,
-                               slots, res);
-        else
-            hipLaunchKernelGGL((k_ct_boxes<VT, RT, false>), grid, dim3(kSumThreads), 0, s, (const VT*)vx, (const VT*)vy,
-                               (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, (const double*)d_edges,
-                               slots, res);
-    };
-    if (v_f32)
-        rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
-    else
-        rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
+        constexpr bool M = decltype(masked_c)::value;
+        hipLaunchKernelGGL((k_ct_boxes<VT, RT, M>), grid, dim3(kSumThreads), 0, s, (const VT*)vx, (const VT*)vy,
+                           (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, (const double*)d_edges, slots,
+                           res);
+    });
     hipLaunchKernelGGL(k_ct_final, dim3(n_roi), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, P, res);
     OF3DK_HIP(hipGetLastError());
     return 0;

@@ -202,8 +202,7 @@ int of3d_flow_pair(const void* vx0, const void* vy0, const void* vz0, const void
     if (!vx0 || !vy0 || !vx1 || !vy1 || !rois || !d_keep || !d_result || !workspace)
         return of3dk::set_error("of3d: null argument");
     if (!vz0 != !vz1) return of3dk::set_error("of3d: vz of both channels or of neither (in-plane mode)");
-    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
-        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
+    if (of3dk::check_volume(nz, ny, nx, false) != 0) return -1;
     if (!of3dk::bins_ok<kNQ>(nbins4)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     PairParams P{};
     P.sxy = xyscale, P.sz = zscale, P.st = tscale;

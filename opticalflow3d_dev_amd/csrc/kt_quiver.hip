@@ -15,7 +15,6 @@
 
 #include <cstdint>
 #include <string>
-#include <type_traits>
 
 #include "../../include/of3d.h"
 #include "kernels.hpp"
@@ -57,34 +56,24 @@ __device__ __forceinline__ u64 walk_wave(const VT* __restrict__ vx, const VT* __
     of3dk::BoxWalk w(ly, lx, r0, (unsigned)(p0 + lane), 64);
     const int z0 = P.box[roi][0], y0 = P.box[roi][2], x0 = P.box[roi][4];
     const size_t ny = P.ny, nx = P.nx;
-    const double thr = Masked ? 0.0 : (double)*thr_p;
-    const bool is3 = vz != nullptr;
+    const of3dk::FlowFields<VT, RelT, Masked> F{vx,    vy,   vz,   rel, keep,         Masked ? 0.0 : (double)*thr_p,
+                                                P.sxy, P.sz, P.st, roi, vz != nullptr};
     const long long cap = P.cap[roi];
     const u64 below = ((u64)1 << lane) - 1;
     u64 n = 0;
     for (long long e = p0; e < p1; e += 64) {  // the same trips in every lane
         if (Emit && (long long)(base + n) >= cap) break;  // wave-uniform: the block is full
-        double fx = 0.0, fy = 0.0, fz = 0.0, fr = 0.0;  // past the end: mask factor 0, not valid
+        of3dk::RawVoxel raw{0.0, 0.0, 0.0, 0.0};  // past the end: mask factor 0, not valid
         size_t i = 0;
         if (e + lane < p1) {
             i = ((size_t)(z0 + (size_t)w.z * P.gap[0]) * ny + (y0 + (size_t)w.y * P.gap[1])) * nx +
                 (x0 + (size_t)w.x * P.gap[2]);
-            if constexpr (Masked)
-                fr = (keep[i] >> roi & 1) ? 1.0 : 0.0;
-            else
-                fr = (double)rel[i];
-            fx = (double)vx[i];
-            fy = (double)vy[i];
-            if (is3) fz = (double)vz[i];
+            raw = of3dk::load_voxel(F, i);
         }
         w.advance();
-        const double m = Masked ? fr : (fr > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
-        const double vxp = of3dk::masked_velocity(fx, m, P.sxy, P.st);
-        const double vyp = of3dk::masked_velocity(fy, m, P.sxy, P.st);
-        const double vzp = is3 ? of3dk::masked_velocity(fz, m, P.sz, P.st) : 0.0;
-        const double xy2 = vxp * vxp + vyp * vyp;
-        const double mag = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
-        const bool valid = mag == mag;  // badRows = isnan(mag)
+        const of3dk::Voxel v = of3dk::physical_voxel(F, raw);
+        const double vxp = v.vxp, vyp = v.vyp, vzp = v.vzp;
+        const bool valid = v.sq == v.sq;
         const u64 bal = __ballot(valid);
         if constexpr (Emit) {
             const long long pos = (long long)(base + n) + __popcll(bal & below);
@@ -233,9 +222,7 @@ int of3d_quiver_sample(const void* vx, const void* vy, const void* vz, const voi
                        const uint16_t* d_keep, void* d_result, void* workspace, void* stream) {
     if (!vx || !vy || !rois || !gap3 || !capacity || !d_result || !workspace || (!d_keep && (!rel || !d_thresh)))
         return of3dk::set_error("of3d: null argument");
-    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
-        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
-    if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (of3dk::check_volume(nz, ny, nx, !vz) != 0) return -1;
     if (vz && nz == 1) return of3dk::set_error("of3d: a 2D quiver sample (nz == 1) takes no vz");
     QvParams P{};
     P.sxy = xyscale, P.sz = zscale, P.st = tscale;
@@ -255,28 +242,17 @@ int of3d_quiver_sample(const void* vx, const void* vy, const void* vz, const voi
     u64* ws = (u64*)workspace;
     u64* res = (u64*)d_result;
     const dim3 grid(max_nb, n_roi);
-    auto launch = [&](auto vt, auto rt) {
+    of3dk::with_flow_types(v_f32, rel_f64, d_keep != nullptr, [&](auto vt, auto rt, auto masked_c) {
         using VT = decltype(vt);
         using RT = decltype(rt);
-        auto pass = [&](auto masked) {
-            constexpr bool M = decltype(masked)::value;
-            hipLaunchKernelGGL((k_quiver_count<VT, RT, M>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
-                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, ws);
-            hipLaunchKernelGGL(k_quiver_scan, dim3(n_roi), dim3(kScanThreads), 0, s, ws, P, d_thresh, rel_f64,
-                               (long long)gap3[0], (long long)gap3[1], (long long)gap3[2], vz ? 1 : 0, res);
-            hipLaunchKernelGGL((k_quiver_emit<VT, RT, M>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
-                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P,
-                               (const u64*)ws, res);
-        };
-        if (d_keep)
-            pass(std::true_type{});
-        else
-            pass(std::false_type{});
-    };
-    if (v_f32)
-        rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
-    else
-        rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
+        constexpr bool M = decltype(masked_c)::value;
+        hipLaunchKernelGGL((k_quiver_count<VT, RT, M>), grid, dim3(kSumThreads), 0, s, (const VT*)vx, (const VT*)vy,
+                           (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, ws);
+        hipLaunchKernelGGL(k_quiver_scan, dim3(n_roi), dim3(kScanThreads), 0, s, ws, P, d_thresh, rel_f64,
+                           (long long)gap3[0], (long long)gap3[1], (long long)gap3[2], vz ? 1 : 0, res);
+        hipLaunchKernelGGL((k_quiver_emit<VT, RT, M>), grid, dim3(kSumThreads), 0, s, (const VT*)vx, (const VT*)vy,
+                           (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, (const u64*)ws, res);
+    });
     OF3DK_HIP(hipGetLastError());
     return 0;
 }

@@ -61,7 +61,7 @@ __device__ __forceinline__ double wave_extreme(double v) {
 }
 
 // Grid (max workgroups of a box, n_roi).  Masked: the mask factor of a voxel is bit `roi` of keep
-// (of3d_mask_open) instead of rel > thr.  The voxel loop is k_sum_boxes'.
+// (of3d_mask_open) instead of rel > thr.
 template <typename VT, typename RelT, bool Masked>
 __global__ __launch_bounds__(kSumThreads) void k_spread_boxes(const VT* __restrict__ vx, const VT* __restrict__ vy,
                                                               const VT* __restrict__ vz, const RelT* __restrict__ rel,
@@ -78,9 +78,9 @@ __global__ __launch_bounds__(kSumThreads) void k_spread_boxes(const VT* __restri
     __syncthreads();
 
     of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
-    const long long count = sh.count;
-    const double thr = Masked ? 0.0 : (double)*thr_p;
-    const bool is3 = vz != nullptr;
+    const of3dk::FlowFields<VT, RelT, Masked> F{vx,    vy,   vz,   rel, keep,         Masked ? 0.0 : (double)*thr_p,
+                                                P.sxy, P.sz, P.st, roi, vz != nullptr};
+    const bool is3 = F.is3;
     const double cx = box_center(P, summary, roi, 0), cy = box_center(P, summary, roi, 1);
     const double cz = box_center(P, summary, roi, 2), cm = box_center(P, summary, roi, 3);
     const double inf = __builtin_inf();
@@ -88,59 +88,30 @@ __global__ __launch_bounds__(kSumThreads) void k_spread_boxes(const VT* __restri
     double ext[kNExt] = {inf, inf, inf, inf, -inf, -inf, -inf, -inf};
     unsigned nvalid = 0;
 
-    constexpr int U = 4;
-    for (long long e = threadIdx.x; e < count; e += (long long)U * kSumThreads) {
-        double fx[U], fy[U], fz[U], fr[U];
-        bool in[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            in[u] = e + (long long)u * kSumThreads < count;
-            fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
-            if (in[u]) {
-                const size_t i = sh.index();
-                if constexpr (Masked)
-                    fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
-                else
-                    fr[u] = (double)rel[i];
-                fx[u] = (double)vx[i];
-                fy[u] = (double)vy[i];
-                if (is3) fz[u] = (double)vz[i];
-            }
-            sh.w.advance();
+    of3dk::for_valid_voxels(F, sh, [&](const of3dk::Voxel& v, unsigned, unsigned, unsigned) {
+        const double vxp = v.vxp, vyp = v.vyp, vzp = v.vzp, mag = sqrt(v.sq);
+        const double dx = vxp - cx, dy = vyp - cy, dz = is3 ? vzp - cz : 0.0, dm = mag - cm;
+        ++nvalid;
+        acc[0] += dx * dx;
+        acc[1] += dy * dy;
+        acc[2] += dz * dz;
+        acc[3] += dm * dm;
+        acc[4] += dx * dy;
+        acc[5] += dx * dz;
+        acc[6] += dy * dz;
+        if (is3) {  // phi = atan(vz / h): sin = vz / mag, cos = h / mag, as the summary's sin(theta) = vy / h
+            acc[7] += vzp / mag;
+            acc[8] += sqrt(v.xy2) / mag;
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (!in[u]) continue;
-            const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
-            const double vxp = of3dk::masked_velocity(fx[u], m, P.sxy, P.st);
-            const double vyp = of3dk::masked_velocity(fy[u], m, P.sxy, P.st);
-            const double vzp = is3 ? of3dk::masked_velocity(fz[u], m, P.sz, P.st) : 0.0;
-            const double xy2 = vxp * vxp + vyp * vyp;
-            const double mag = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
-            if (mag != mag) continue;  // badRows = isnan(mag)
-            const double dx = vxp - cx, dy = vyp - cy, dz = is3 ? vzp - cz : 0.0, dm = mag - cm;
-            ++nvalid;
-            acc[0] += dx * dx;
-            acc[1] += dy * dy;
-            acc[2] += dz * dz;
-            acc[3] += dm * dm;
-            acc[4] += dx * dy;
-            acc[5] += dx * dz;
-            acc[6] += dy * dz;
-            if (is3) {  // phi = atan(vz / h): sin = vz / mag, cos = h / mag, as the summary's sin(theta) = vy / h
-                acc[7] += vzp / mag;
-                acc[8] += sqrt(xy2) / mag;
-            }
-            ext[0] = vxp < ext[0] ? vxp : ext[0];
-            ext[1] = vyp < ext[1] ? vyp : ext[1];
-            ext[2] = vzp < ext[2] ? vzp : ext[2];
-            ext[3] = mag < ext[3] ? mag : ext[3];
-            ext[4] = vxp > ext[4] ? vxp : ext[4];
-            ext[5] = vyp > ext[5] ? vyp : ext[5];
-            ext[6] = vzp > ext[6] ? vzp : ext[6];
-            ext[7] = mag > ext[7] ? mag : ext[7];
-        }
-    }
+        ext[0] = vxp < ext[0] ? vxp : ext[0];
+        ext[1] = vyp < ext[1] ? vyp : ext[1];
+        ext[2] = vzp < ext[2] ? vzp : ext[2];
+        ext[3] = mag < ext[3] ? mag : ext[3];
+        ext[4] = vxp > ext[4] ? vxp : ext[4];
+        ext[5] = vyp > ext[5] ? vyp : ext[5];
+        ext[6] = vzp > ext[6] ? vzp : ext[6];
+        ext[7] = mag > ext[7] ? mag : ext[7];
+    });
 
     if (nvalid) atomicAdd(&nvalid_s, nvalid);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -212,9 +183,7 @@ int of3d_flow_spread(const void* vx, const void* vy, const void* vz, const void*
                      const int* summary_nbins, const double* center, void* d_result, void* workspace, void* stream) {
     if (!vx || !vy || !rois || !d_result || !workspace || (!d_keep && (!rel || !d_thresh)))
         return of3dk::set_error("of3d: null argument");
-    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
-        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
-    if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (of3dk::check_volume(nz, ny, nx, !vz) != 0) return -1;
     if (!center && !d_summary) return of3dk::set_error("of3d: a spread needs a center or the summary's result");
     if (!center && !of3dk::bins_ok<kNQ>(summary_nbins))
         return of3dk::set_error("of3d: the summary's nbins: 0 to 256 bins per quantity");
@@ -236,22 +205,13 @@ int of3d_flow_spread(const void* vx, const void* vy, const void* vz, const void*
     const u64* sum = (const u64*)d_summary;
     OF3DK_HIP(hipMemsetAsync(d_result, 0, of3d_flow_spread_result_bytes(n_roi), s));
     const dim3 grid(max_nb, n_roi);
-    auto launch = [&](auto vt, auto rt) {
+    of3dk::with_flow_types(v_f32, rel_f64, d_keep != nullptr, [&](auto vt, auto rt, auto masked_c) {
         using VT = decltype(vt);
         using RT = decltype(rt);
-        if (d_keep)
-            hipLaunchKernelGGL((k_spread_boxes<VT, RT, true>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
-                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, sum,
-                               slots, res);
-        else
-            hipLaunchKernelGGL((k_spread_boxes<VT, RT, false>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
-                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, sum,
-                               slots, res);
-    };
-    if (v_f32)
-        rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
-    else
-        rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
+        constexpr bool M = decltype(masked_c)::value;
+        hipLaunchKernelGGL((k_spread_boxes<VT, RT, M>), grid, dim3(kSumThreads), 0, s, (const VT*)vx, (const VT*)vy,
+                           (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, sum, slots, res);
+    });
     hipLaunchKernelGGL(k_spread_final, dim3(n_roi, 2), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, P, sum,
                        res);
     OF3DK_HIP(hipGetLastError());

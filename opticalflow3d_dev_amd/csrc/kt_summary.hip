@@ -218,65 +218,36 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_boxes(const VT* __restrict_
     __syncthreads();
 
     of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
-    const long long count = sh.count;
-    const double thr = (double)*thr_p;
-    const bool is3 = vz != nullptr;
+    // the threshold is read (and reported by k_sum_final) with a keep volume too
+    const of3dk::FlowFields<VT, RelT, Masked> F{vx,    vy,   vz,   rel, keep,         (double)*thr_p,
+                                                P.sxy, P.sz, P.st, roi, vz != nullptr};
     double acc[kNSum] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned nvalid = 0;
 
-    constexpr int U = 4;
-    for (long long e = threadIdx.x; e < count; e += (long long)U * kSumThreads) {
-        double fx[U], fy[U], fz[U], fr[U];
-        bool in[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            in[u] = e + (long long)u * kSumThreads < count;
-            fx[u] = fy[u] = fz[u] = fr[u] = 0.0;
-            if (in[u]) {
-                const size_t i = sh.index();
-                if constexpr (Masked)
-                    fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
-                else
-                    fr[u] = (double)rel[i];
-                fx[u] = (double)vx[i];
-                fy[u] = (double)vy[i];
-                if (is3) fz[u] = (double)vz[i];
-            }
-            sh.w.advance();
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (!in[u]) continue;
-            const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
-            const double vxp = of3dk::masked_velocity(fx[u], m, P.sxy, P.st);
-            const double vyp = of3dk::masked_velocity(fy[u], m, P.sxy, P.st);
-            const double vzp = is3 ? of3dk::masked_velocity(fz[u], m, P.sz, P.st) : 0.0;
-            const double xy2 = vxp * vxp + vyp * vyp;
-            const double mag = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
-            if (mag != mag) continue;  // badRows = isnan(mag)
-            const double h = sqrt(xy2);
-            const double sn = vyp / h, cs = vxp / h;
-            ++nvalid;
-            acc[0] += mag;
-            acc[1] += vxp;
-            acc[2] += vyp;
-            acc[3] += vzp;
-            acc[4] += sn;
-            acc[5] += cs;
-            acc[6] += mag * sn;
-            acc[7] += mag * cs;
-            auto put = [&](int q, double v) {
-                const int b = find_bin(edges + P.eoff[q], P.nbins[q], v);
-                if (b >= 0) atomicAdd(&hist[P.hoff[q] + b], 1u);
-            };
-            if (P.nbins[0]) put(0, vxp);
-            if (P.nbins[1]) put(1, vyp);
-            if (P.nbins[2]) put(2, vzp);
-            if (P.nbins[3]) put(3, mag);
-            if (P.nbins[4]) put(4, atan2(vyp, vxp));
-            if (P.nbins[5]) put(5, atan(vzp / h));
-        }
-    }
+    of3dk::for_valid_voxels(F, sh, [&](const of3dk::Voxel& v, unsigned, unsigned, unsigned) {
+        const double vxp = v.vxp, vyp = v.vyp, vzp = v.vzp;
+        const double mag = sqrt(v.sq), h = sqrt(v.xy2);
+        const double sn = vyp / h, cs = vxp / h;
+        ++nvalid;
+        acc[0] += mag;
+        acc[1] += vxp;
+        acc[2] += vyp;
+        acc[3] += vzp;
+        acc[4] += sn;
+        acc[5] += cs;
+        acc[6] += mag * sn;
+        acc[7] += mag * cs;
+        auto put = [&](int q, double x) {
+            const int b = find_bin(edges + P.eoff[q], P.nbins[q], x);
+            if (b >= 0) atomicAdd(&hist[P.hoff[q] + b], 1u);
+        };
+        if (P.nbins[0]) put(0, vxp);
+        if (P.nbins[1]) put(1, vyp);
+        if (P.nbins[2]) put(2, vzp);
+        if (P.nbins[3]) put(3, mag);
+        if (P.nbins[4]) put(4, atan2(vyp, vxp));
+        if (P.nbins[5]) put(5, atan(vzp / h));
+    });
 
     if (nvalid) atomicAdd(&nvalid_s, nvalid);
     of3dk::reduce_to_slot(acc, wsum, slots + ((size_t)roi * kSumMaxBlocks + blockIdx.x) * kNSum);
@@ -341,9 +312,7 @@ static int summary_launch(const void* vx, const void* vy, const void* vz, const 
                           const uint16_t* keep, bool masked) {
     if (!vx || !vy || !rel || !d_thresh || !rois || !d_result || !workspace || (masked && !keep))
         return of3dk::set_error("of3d: null argument");
-    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
-        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
-    if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (of3dk::check_volume(nz, ny, nx, !vz) != 0) return -1;
     if (n_roi < 1 || n_roi > kMaxRoi) return of3dk::set_error("of3d: 1 to 16 ROI boxes");
     if (!of3dk::bins_ok<kNQ>(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     if (!vz && (nbins[2] || nbins[5])) return of3dk::set_error("of3d: vz and phi histograms need a 3D volume");
@@ -361,24 +330,16 @@ static int summary_launch(const void* vx, const void* vy, const void* vz, const 
     double* d_edges = (double*)((char*)workspace + kSumSlotBytes);
     OF3DK_HIP(hipMemsetAsync(d_result, 0, of3d_flow_summary_result_bytes(n_roi, nbins), s));
     of3dk::put_edges(s, d_edges, host_edges, eo);
-    auto launch = [&](auto vt, auto rt) {
+    of3dk::with_flow_types(v_f32, rel_f64, masked, [&](auto vt, auto rt, auto masked_c) {
         using VT = decltype(vt);
         using RT = decltype(rt);
-        if (masked)
-            hipLaunchKernelGGL((k_sum_boxes<VT, RT, true>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
-                               (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, keep,
-                               P, (const double*)d_edges, slots, (u64*)d_result);
-        else
-            hipLaunchKernelGGL((k_sum_boxes<VT, RT, false>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
-                               (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, keep,
-                               P, (const double*)d_edges, slots, (u64*)d_result);
-        hipLaunchKernelGGL(k_sum_final<RT>, dim3(n_roi), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots, (const RT*)d_thresh,
-                           P, (u64*)d_result);
-    };
-    if (v_f32)
-        rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
-    else
-        rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
+        constexpr bool M = decltype(masked_c)::value;
+        hipLaunchKernelGGL((k_sum_boxes<VT, RT, M>), dim3(max_nb, n_roi), dim3(kSumThreads), 0, s,
+                           (const VT*)vx, (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, keep, P,
+                           (const double*)d_edges, slots, (u64*)d_result);
+        hipLaunchKernelGGL(k_sum_final<RT>, dim3(n_roi), dim3(of3dk::kFinalThreads), 0, s, (const double*)slots,
+                           (const RT*)d_thresh, P, (u64*)d_result);
+    });
     OF3DK_HIP(hipGetLastError());
     return 0;
 }

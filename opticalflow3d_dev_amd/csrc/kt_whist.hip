@@ -87,47 +87,20 @@ __global__ __launch_bounds__(kSumThreads) void k_whist_boxes(const VT* __restric
     __syncthreads();
 
     of3dk::BoxShare sh = of3dk::box_share(P, roi, nb);
-    const long long count = sh.count;
-    const double thr = Masked ? 0.0 : (double)*thr_p;
-    const bool is3 = vz != nullptr;
+    const of3dk::FlowFields<VT, RelT, Masked> F{vx,    vy,   vz,   rel, keep,         Masked ? 0.0 : (double)*thr_p,
+                                                P.sxy, P.sz, P.st, roi, vz != nullptr};
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double* mine = whist[wave];
     unsigned nvalid = 0;
 
-    constexpr int U = 4;
-    for (long long e0 = 0; e0 < count; e0 += (long long)U * kSumThreads) {  // the same trips in every lane
-        double fx[U], fy[U], fz[U], fr[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            fx[u] = fy[u] = fz[u] = fr[u] = 0.0;  // past the end: mask factor 0, not valid
-            if (e0 + threadIdx.x + (long long)u * kSumThreads < count) {
-                const size_t i = sh.index();
-                if constexpr (Masked)
-                    fr[u] = (keep[i] >> roi & 1) ? 1.0 : 0.0;
-                else
-                    fr[u] = (double)rel[i];
-                fx[u] = (double)vx[i];
-                fy[u] = (double)vy[i];
-                if (is3) fz[u] = (double)vz[i];
-            }
-            sh.w.advance();
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const double m = Masked ? fr[u] : (fr[u] > thr) ? 1.0 : 0.0;  // numpy: v * bool mask
-            const double vxp = of3dk::masked_velocity(fx[u], m, P.sxy, P.st);
-            const double vyp = of3dk::masked_velocity(fy[u], m, P.sxy, P.st);
-            const double vzp = is3 ? of3dk::masked_velocity(fz[u], m, P.sz, P.st) : 0.0;
-            const double xy2 = vxp * vxp + vyp * vyp;
-            const double mag = is3 ? sqrt(xy2 + vzp * vzp) : sqrt(xy2);
-            const bool valid = mag == mag;  // badRows = isnan(mag)
-            nvalid += valid;
-            if (!__ballot(valid)) continue;  // wave-uniform: no lane of this wave has anything to add
-            const double v = of3dk::quantity_value(q, vxp, vyp, vzp, mag, sqrt(xy2));
-            const int bin = valid ? of3dk::find_bin(edges, nbins, v) : -1;
-            wave_add(mine, bin, bin >= 0 ? mag : 0.0, lane);
-        }
-    }
+    of3dk::for_voxels_uniform(F, sh, [&](const of3dk::Voxel& vox, bool valid) {
+        nvalid += valid;
+        if (!__ballot(valid)) return;  // wave-uniform: no lane of this wave has anything to add
+        const double mag = sqrt(vox.sq);
+        const double v = of3dk::quantity_value(q, vox.vxp, vox.vyp, vox.vzp, mag, sqrt(vox.xy2));
+        const int bin = valid ? of3dk::find_bin(edges, nbins, v) : -1;
+        wave_add(mine, bin, bin >= 0 ? mag : 0.0, lane);
+    });
 
     if (k == 0 && nvalid) atomicAdd(&nvalid_s, nvalid);
     __syncthreads();
@@ -186,9 +159,7 @@ int of3d_flow_whist(const void* vx, const void* vy, const void* vz, const void* 
                     const double* const* edges, void* d_result, void* workspace, void* stream) {
     if (!vx || !vy || !rois || !d_result || !workspace || (!d_keep && (!rel || !d_thresh)))
         return of3dk::set_error("of3d: null argument");
-    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
-        return of3dk::set_error("of3d: summary dims must lie in [1, 2^31)");
-    if (!vz && nz != 1) return of3dk::set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    if (of3dk::check_volume(nz, ny, nx, !vz) != 0) return -1;
     if (!of3dk::bins_ok<kNQ>(nbins)) return of3dk::set_error("of3d: 0 to 256 bins per quantity");
     if (!vz && (nbins[2] || nbins[5])) return of3dk::set_error("of3d: vz and phi histograms need a 3D volume");
     WhParams P{};
@@ -214,22 +185,14 @@ int of3d_flow_whist(const void* vx, const void* vy, const void* vz, const void* 
     OF3DK_HIP(hipMemsetAsync(d_result, 0, of3d_flow_whist_result_bytes(n_roi, nbins), s));
     of3dk::put_edges(s, d_edges, host_edges, eo);
     const dim3 grid(max_nb, n_roi, P.nq);
-    auto launch = [&](auto vt, auto rt) {
+    of3dk::with_flow_types(v_f32, rel_f64, d_keep != nullptr, [&](auto vt, auto rt, auto masked_c) {
         using VT = decltype(vt);
         using RT = decltype(rt);
-        if (d_keep)
-            hipLaunchKernelGGL((k_whist_boxes<VT, RT, true>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
-                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P,
-                               (const double*)d_edges, slots, res);
-        else
-            hipLaunchKernelGGL((k_whist_boxes<VT, RT, false>), grid, dim3(kSumThreads), 0, s, (const VT*)vx,
-                               (const VT*)vy, (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P,
-                               (const double*)d_edges, slots, res);
-    };
-    if (v_f32)
-        rel_f64 ? launch(float{}, double{}) : launch(float{}, float{});
-    else
-        rel_f64 ? launch(double{}, double{}) : launch(double{}, float{});
+        constexpr bool M = decltype(masked_c)::value;
+        hipLaunchKernelGGL((k_whist_boxes<VT, RT, M>), grid, dim3(kSumThreads), 0, s, (const VT*)vx, (const VT*)vy,
+                           (const VT*)vz, (const RT*)rel, (const RT*)d_thresh, d_keep, P, (const double*)d_edges, slots,
+                           res);
+    });
     hipLaunchKernelGGL(k_whist_final, dim3((P.ntot + 255) / 256, n_roi), dim3(256), 0, s, (const double*)slots, P, res);
     OF3DK_HIP(hipGetLastError());
     return 0;

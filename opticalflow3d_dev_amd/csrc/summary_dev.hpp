@@ -2,11 +2,12 @@
 // summary_dev.hpp — the per-voxel device helpers shared by the frame summary (kt_summary.hip:
 // k_sum_boxes), the projected flow (kt_axes.hip: k_proj_boxes), the magnitude-weighted
 // histograms (kt_whist.hip: k_whist_boxes), the two-channel comparison (kt_pair.hip:
-// k_pair_boxes), the spread (kt_spread.hip: k_spread_boxes) and the reliability profile
-// (kt_relsel.hip: k_rp_boxes): one statement of the masking arithmetic, the histogram bin search, the walk
-// over a box, a workgroup's share of a box and the reduction of its sums, so the passes cannot
-// drift apart.  The host side (box check, workgroup plan, histogram plan, edge upload) is
-// summary_host.hpp's.
+// k_pair_boxes), the quiver samples (kt_quiver.hip: walk_wave), the contractility
+// (kt_contract.hip: k_ct_boxes), the spread (kt_spread.hip: k_spread_boxes) and the reliability
+// profile (kt_relsel.hip: k_rp_boxes): one statement of the masking arithmetic, the histogram bin
+// search, the walk over a box, a workgroup's share of a box, the loop over its voxels and the
+// reduction of its sums, so the passes cannot drift apart.  The host side (volume and box
+// checks, workgroup plan, histogram plan, edge upload, type dispatch) is summary_host.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -98,6 +99,112 @@ __device__ __forceinline__ BoxShare box_share(const BoxParams& P, int roi, int n
     const long long R = (long long)(P.box[roi][1] - z0) * dy;
     const long long r0 = R * blockIdx.x / nb, r1 = R * (blockIdx.x + 1) / nb;
     return {z0, y0, x0, P.ny, P.nx, dy, dx, (r1 - r0) * dx, BoxWalk(dy, dx, r0, threadIdx.x, kSumThreads)};
+}
+
+// ---------------------------------------------------------------------------
+// The voxels of a flow pass: what the pass takes of the fields, one voxel's load and masking
+// arithmetic, and the two loops over a workgroup's share of a box.
+// ---------------------------------------------------------------------------
+// Masked: the mask factor of a voxel is bit `roi` of keep (of3d_mask_open, of3d_mask_largest)
+// instead of rel > thr.  is3: the pass has a vz.
+template <typename VT, typename RelT, bool Masked>
+struct FlowFields {
+    const VT *__restrict__ vx, *__restrict__ vy, *__restrict__ vz;
+    const RelT* __restrict__ rel;
+    const uint16_t* __restrict__ keep;
+    double thr, sxy, sz, st;
+    int roi;
+    bool is3;
+};
+
+struct RawVoxel {
+    double x, y, z, r;  // the loaded velocity; r: the mask bit as 0 / 1 (Masked) or rel
+};
+
+struct Voxel {
+    double vxp, vyp, vzp;  // physical velocity, NaN outside the mask and where it was an exact zero
+    double xy2, sq;        // vxp^2 + vyp^2; the magnitude's square: xy2 (+ vzp^2 with a vz)
+};
+
+template <typename VT, typename RelT, bool Masked>
+__device__ __forceinline__ RawVoxel load_voxel(const FlowFields<VT, RelT, Masked>& F, size_t i) {
+    RawVoxel v{0.0, 0.0, 0.0, 0.0};
+    if constexpr (Masked)
+        v.r = (F.keep[i] >> F.roi & 1) ? 1.0 : 0.0;
+    else
+        v.r = (double)F.rel[i];
+    v.x = (double)F.vx[i];
+    v.y = (double)F.vy[i];
+    if (F.is3) v.z = (double)F.vz[i];
+    return v;
+}
+
+// The voxel is valid <=> its magnitude is not NaN (badRows = isnan(mag)) <=> sq == sq: a sum of
+// squares is NaN or >= 0, so its root is NaN exactly where it is.  The magnitude is sqrt(sq).
+template <typename VT, typename RelT, bool Masked>
+__device__ __forceinline__ Voxel physical_voxel(const FlowFields<VT, RelT, Masked>& F, const RawVoxel& raw) {
+    const double m = Masked ? raw.r : (raw.r > F.thr) ? 1.0 : 0.0;  // numpy: v * bool mask
+    Voxel v;
+    v.vxp = masked_velocity(raw.x, m, F.sxy, F.st);
+    v.vyp = masked_velocity(raw.y, m, F.sxy, F.st);
+    v.vzp = F.is3 ? masked_velocity(raw.z, m, F.sz, F.st) : 0.0;
+    v.xy2 = v.vxp * v.vxp + v.vyp * v.vyp;
+    v.sq = F.is3 ? v.xy2 + v.vzp * v.vzp : v.xy2;
+    return v;
+}
+
+// One trip of a thread over its share: kVoxUnroll voxels kSumThreads apart, the first of them
+// element e of the share, all loads issued before any arithmetic.  An element past the end is
+// not loaded: in[u] false and zeros, which are never valid (a zero velocity becomes NaN).
+// k[u]: the voxel inside the box (x y z).
+constexpr int kVoxUnroll = 4;
+template <typename VT, typename RelT, bool Masked>
+__device__ __forceinline__ void load_trip(const FlowFields<VT, RelT, Masked>& F, BoxShare& sh, long long e,
+                                          RawVoxel (&raw)[kVoxUnroll], bool (&in)[kVoxUnroll],
+                                          unsigned (&k)[kVoxUnroll][3]) {
+#pragma unroll
+    for (int u = 0; u < kVoxUnroll; ++u) {
+        in[u] = e + (long long)u * kSumThreads < sh.count;
+        raw[u] = RawVoxel{0.0, 0.0, 0.0, 0.0};
+        k[u][0] = sh.w.x, k[u][1] = sh.w.y, k[u][2] = sh.w.z;
+        if (in[u]) raw[u] = load_voxel(F, sh.index());
+        sh.w.advance();
+    }
+}
+
+// body(voxel, x, y, z) for every valid voxel of the share, x y z inside the box; a thread takes
+// its voxels in ascending order and leaves once it has none left.
+template <typename VT, typename RelT, bool Masked, typename Body>
+__device__ __forceinline__ void for_valid_voxels(const FlowFields<VT, RelT, Masked>& F, BoxShare& sh, Body&& body) {
+    for (long long e = threadIdx.x; e < sh.count; e += (long long)kVoxUnroll * kSumThreads) {
+        RawVoxel raw[kVoxUnroll];
+        bool in[kVoxUnroll];
+        unsigned k[kVoxUnroll][3];
+        load_trip(F, sh, e, raw, in, k);
+#pragma unroll
+        for (int u = 0; u < kVoxUnroll; ++u) {
+            if (!in[u]) continue;
+            const Voxel v = physical_voxel(F, raw[u]);
+            if (v.sq == v.sq) body(v, k[u][0], k[u][1], k[u][2]);
+        }
+    }
+}
+
+// The wave-uniform form, for bodies with ballots and shuffles: the same trips in every lane and
+// body(voxel, valid) for every element, those past the end included (not valid).
+template <typename VT, typename RelT, bool Masked, typename Body>
+__device__ __forceinline__ void for_voxels_uniform(const FlowFields<VT, RelT, Masked>& F, BoxShare& sh, Body&& body) {
+    for (long long e0 = 0; e0 < sh.count; e0 += (long long)kVoxUnroll * kSumThreads) {
+        RawVoxel raw[kVoxUnroll];
+        bool in[kVoxUnroll];
+        unsigned k[kVoxUnroll][3];
+        load_trip(F, sh, e0 + threadIdx.x, raw, in, k);
+#pragma unroll
+        for (int u = 0; u < kVoxUnroll; ++u) {
+            const Voxel v = physical_voxel(F, raw[u]);
+            body(v, v.sq == v.sq);
+        }
+    }
 }
 
 // The fixed shuffle tree over a wave's 64 lanes, all of them active: lane 0 returns the sum

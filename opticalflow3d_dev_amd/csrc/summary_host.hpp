@@ -1,13 +1,15 @@
 #pragma once
 // summary_host.hpp — the host side shared by the device-side summary passes (kt_summary.hip,
-// kt_ccl.hip, kt_axes.hip, kt_whist.hip, kt_pair.hip, kt_spread.hip, kt_relsel.hip): one statement of the box check, the
-// workgroup plan, the histogram plan with its edge validation, and the edge upload.  The entry
-// points keep their own order of argument checks; what a check tests and says is here.
+// kt_ccl.hip, kt_axes.hip, kt_whist.hip, kt_pair.hip, kt_quiver.hip, kt_contract.hip, kt_spread.hip,
+// kt_relsel.hip): one statement of the volume check, the box check, the workgroup plan, the
+// histogram plan with its edge validation, the edge upload and the dispatch over the field types.
+// The entry points keep their own order of argument checks; what a check tests and says is here.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/of3d.h"
 #include "kernels.hpp"
@@ -31,6 +33,33 @@ inline int64_t sum_workgroups(int64_t vox, int64_t rows) {
     int64_t nb = (vox + kSumVoxPerBlock - 1) / kSumVoxPerBlock;
     nb = nb > kSumMaxBlocks ? kSumMaxBlocks : nb;
     return nb > rows ? rows : nb;
+}
+
+// ---------------------------------------------------------------------------
+// The volume and the field types of a flow pass
+// ---------------------------------------------------------------------------
+// dims in [1, 2^31); flat (the pass has no vz): a single plane
+inline int check_volume(int64_t nz, int64_t ny, int64_t nx, bool flat) {
+    if (nz < 1 || ny < 1 || nx < 1 || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX)
+        return set_error("of3d: summary dims must lie in [1, 2^31)");
+    if (flat && nz != 1) return set_error("of3d: a 2D summary (vz NULL) needs nz == 1");
+    return 0;
+}
+
+// f(VT{}, RelT{}, std::bool_constant<Masked>{}) for the velocity type, the rel type and the
+// mask source of a call: the box kernels' template arguments, chosen once
+template <typename F>
+void with_flow_types(int v_f32, int rel_f64, bool masked, F&& f) {
+    auto with_mask = [&](auto vt, auto rt) {
+        if (masked)
+            f(vt, rt, std::true_type{});
+        else
+            f(vt, rt, std::false_type{});
+    };
+    if (v_f32)
+        rel_f64 ? with_mask(float{}, double{}) : with_mask(float{}, float{});
+    else
+        rel_f64 ? with_mask(double{}, double{}) : with_mask(double{}, float{});
 }
 
 // ---------------------------------------------------------------------------

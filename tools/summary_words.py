@@ -19,7 +19,15 @@ all six quantities binned plain (two edge uploads: more than 384 edges) and weig
 axis histograms with axes="mask" and with a given 3x3, and the pair pass in 3D and in-plane with
 both `combine` values.  Zeros and NaNs are planted in the velocities.
 
-    python tools/summary_words.py --out words.npz [--commit ID] [--skip b]
+The later passes ride on the same cases and dtype pairs through `_SummaryCall(spec, quiver=,
+contract=)` with `SummarySpec(spread=)`, unmasked and opened: of3d_flow_spread about the box mean
+and about a given centre; of3d_quiver_sample with gap 1 and with an anisotropic gap, at a capacity
+that truncates the volume's list but not the box's (QUIVER_MAX); of3d_flow_contract over the summary's mask
+and (unmasked summary only) over of3d_mask_largest's, about the mask's centroid and a given
+centre, both histograms binned, with of3d_mask_largest's keep volume.  The quiver's and the
+contract's result tensors are zeroed first: the kernels leave the records past n_stored alone.
+
+    python tools/summary_words.py --out words.npz [--commit ID] [--skip b] [--beside old.npz]
 """
 
 import argparse
@@ -45,6 +53,17 @@ AXIS_BINS = {"axis1": np.linspace(-2.0, 2.0, 21), "axis2": np.linspace(-1.0, 1.0
              "axis3": np.linspace(-3.0, 3.0, 16)}
 PAIR_BINS = {"dot": np.linspace(-1.0, 1.0, 21), "cosine": np.linspace(-1.0001, 1.0001, 37),
              "dtheta": np.linspace(-np.pi, np.pi, 37), "dmagnitude": np.linspace(-1.0, 1.0, 12)}
+CONTRACT_BINS = {"angle": np.linspace(0.0, 180.0, 19), "inward": np.linspace(-1.0, 1.0, 12)}
+SPREAD_CENTER = (0.1, -0.2, 0.3, 0.5)  # vx vy vz magnitude (2D: without vz)
+CONTRACT_CENTER = (20.5, 11.25, 1.5)   # x y z, box-local (2D: x y)
+QUIVER_GAP = (2, 3, 2)                 # gz gy gx (2D: gy gx = 3 2)
+# max_vectors at gap 1 and at QUIVER_GAP.  In QUIVER_SPLIT's run the capacity lies between the valid lattice
+# points of the interior box and of the volume, so the volume's list truncates and the box's does
+# not: a and c at gap 1 (a 865 / 2134, past the volume's first workgroup; c 268 / 438 unmasked,
+# opened a few less), b at QUIVER_GAP (645 / 1147).  b at gap 1 (nine workgroups, 6485 / 12330)
+# truncates both: a record is four incompressible words and the file has 1 MiB.
+QUIVER_MAX = {"a": (1200, 65536), "b": (600, 900), "c": (320, 65536)}
+QUIVER_SPLIT = {"a": "g1", "b": "aniso", "c": "g1"}  # where one list truncates and the other does not
 
 
 def fields(shape, rng):
@@ -65,7 +84,8 @@ def generate(skip=()):
     """name -> array of every case; needs a GPU."""
     import torch
 
-    from opticalflow3d_dev_amd.analysis import SummarySpec, _AxesCall, _PairCall, _SummaryCall
+    from opticalflow3d_dev_amd.analysis import (ContractSpec, QuiverSpec, SummarySpec, _AxesCall, _PairCall,
+                                                _SummaryCall)
 
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -103,6 +123,34 @@ def generate(skip=()):
                         alone.enqueue(None, None, None, ptr(t0[3]), 0, call.thresh.data_ptr(),
                                       call.open.keep.data_ptr(), ares.data_ptr(), stream)
                         out[f"{case}/r{np.dtype(rdt).itemsize * 8}/axes_alone"] = ares.cpu().numpy()
+            # spread, quiver and contract: (spread, quiver, contract mask, contract centre) per run
+            runs = [("mean", "g1", "summary", "mask"), ("given", "aniso", "summary", "given")]
+            for min_size in (0, 3):
+                for sp, qv, cmask, centre in runs + ([(None, None, "largest", "mask"),
+                                                      (None, None, "largest", "given")] if not min_size else []):
+                    given = SPREAD_CENTER if nd == 3 else SPREAD_CENTER[:2] + SPREAD_CENTER[3:]
+                    spread = None if sp is None else "mean" if sp == "mean" else given
+                    quiver = None if qv is None else (QuiverSpec(gap=1, max_vectors=QUIVER_MAX[case][0]) if qv == "g1"
+                                                      else QuiverSpec(gap=QUIVER_GAP[3 - nd:],
+                                                                      max_vectors=QUIVER_MAX[case][1]))
+                    contract = ContractSpec(mask=cmask, center="mask" if centre == "mask" else CONTRACT_CENTER[:nd],
+                                            bins=CONTRACT_BINS)
+                    spec = SummarySpec(rois=[box], rel_percentile=80, min_size=min_size, spread=spread, **SCALES)
+                    call = _SummaryCall(spec, shape, t0[3].dtype, dev, quiver=quiver, contract=contract)
+                    res = call.new_result(dev)
+                    qres = None if quiver is None else torch.zeros_like(call.quiver.new_result(dev))
+                    cres = torch.zeros_like(call.contract.new_result(dev))
+                    call.enqueue(ptr(t0[0]), ptr(t0[1]), ptr(t0[2]), ptr(t0[3]), v_f32, res.data_ptr(), stream,
+                                 quiver_ptr=ptr(qres), contract_ptr=cres.data_ptr())
+                    out[f"{tag}/contract/{cmask}/m{min_size}/{centre}"] = cres.cpu().numpy()
+                    if spread is not None:
+                        out[f"{tag}/spread/m{min_size}/{sp}"] = res[call.spread_off // 8:].cpu().numpy()
+                    if quiver is not None:
+                        words = out[f"{tag}/quiver/m{min_size}/{qv}"] = qres.cpu().numpy()
+                        if qv == QUIVER_SPLIT[case]:  # n_valid against the capacity: the volume truncates, the box does not
+                            assert words[7] > call.quiver.capacity[0] and words[11] <= call.quiver.capacity[1], words[:14]
+                    if cmask == "largest" and centre == "mask" and not v_f32:
+                        out[f"{case}/r{np.dtype(rdt).itemsize * 8}/largest_keep"] = call.contract.largest.keep.cpu().numpy()
             for combine in ("or", "and"):
                 for in_plane in ((False, True) if nd == 3 else (True,)):
                     call = _PairCall(shape, t0[3].dtype, dev, rel_percentile=70, rois=[box], bins=PAIR_BINS, floor=0.9,
@@ -123,8 +171,12 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--commit", default="", help="recorded in the file: the commit the library was built from")
     ap.add_argument("--skip", default="", help="comma-separated cases to leave out (a, b, c)")
+    ap.add_argument("--beside", default="", help="an earlier file: write only the arrays it does not hold")
     args = ap.parse_args()
     arrays = generate(tuple(s for s in args.skip.split(",") if s))
+    if args.beside:
+        with np.load(args.beside) as f:
+            arrays = {k: a for k, a in arrays.items() if k not in f.files}
     arrays["meta_commit"] = np.array(args.commit)
     arrays["meta_rocm"] = np.array(str(torch.version.hip))
     arrays["meta_device"] = np.array(torch.cuda.get_device_name(0))
