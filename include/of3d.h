@@ -610,6 +610,64 @@ int of3d_quiver_sample(const void* d_vx, const void* d_vy, const void* d_vz, con
                        const uint16_t* d_keep /* NULL: rel > *d_thresh */, void* d_result, void* workspace,
                        void* stream);
 
+/* Field export: the fields themselves, cropped to the boxes of the frame summary, masked the way
+ * the reference's scripts mask them right after loading them, in physical units, optionally
+ * narrowed to float32, as compact blocks — what every figure script keeps of the four full-size
+ * outputs (vx(y1:y2,x1:x2,z1:z2), then vx.*relMask./relMask*xyscale/tscale in plot_figure3 / 4 / 5,
+ * vx.*relMask in plot_FigureS2_dt.m:123, vx*relMask; vx[vx==0]=nan in the notebooks), so that the
+ * download, the pinned memory and the files scale with the ROI instead of the volume.  Fields,
+ * d_rel, dtypes, dims, d_thresh, scales and rois as of3d_flow_summary's; d_keep as
+ * of3d_quiver_sample's (NULL: the mask factor is rel > *d_thresh, else bit r of d_keep for box r).
+ * Only what the call uses must be given: the requested fields, and with a mask_mode other than 0
+ * d_keep, or d_rel and d_thresh.  2D: d_vz == NULL and nz == 1 (a d_vz with nz == 1, and the vz bit
+ * without a d_vz, are errors).
+ * fields: bit 0 vx, 1 vy, 2 vz, 3 rel: the fields exported, one at least.  Bit
+ * OF3D_EXPORT_SKIP_SHIFT + r: box r is listed but not exported — it keeps its index, and so its bit
+ * of d_keep, and has no blocks (the boxes of a summary of which only some are wanted).
+ * Per voxel of box r, with m the mask factor as 0.0 or 1.0 and s = xyscale (zscale for vz):
+ *   mask_mode 0 (none)     v                                    the plain crop
+ *             1 (nan)      (v * m) / m                          v.*relMask./relMask
+ *             2 (zero)     v * m                                v.*relMask
+ *             3 (summary)  v * m, then an exact zero -> NaN     of3d_flow_summary's masking
+ *   physical               then (x * s) / tscale, in that order
+ * every operation an fp64 operation of its own (a float32 v is widened first; no FMA contraction),
+ * so -3.0 * 0.0 is -0.0 and inf * 0.0 is NaN.  rel is always the plain crop.  out_f32 narrows every
+ * finished float64 value with one round-to-nearest conversion; without it a field keeps its own
+ * type (a float32 field's values are computed in fp64 and rounded once).  A value that no
+ * arithmetic and no conversion touches (mode 0 without physical in the field's own type; rel in its
+ * own type) is a bit copy, NaN payloads and -0.0 included.
+ *
+ * Result (device, of3d_field_export_result_bytes(...) bytes, 8-byte words; d_result 16-byte aligned):
+ *   word 0        the threshold as float64 (NaN without a d_thresh)
+ *   words 1..7    n_roi, fields, mask_mode, physical, out_f32, has_vz, the total word count (int64)
+ *   then per box, 6 words: its voxel count, the element sizes (velocity blocks' + 256 * the rel
+ *   block's, in bytes), the word offsets of its vx, vy, vz and rel blocks (0: not exported)
+ *   then the blocks, box by box and vx, vy, vz, rel within a box: each starts on a 16-byte
+ *   boundary, holds the box's dz * dy * dx elements in C order and is padded to whole 16 bytes
+ *   with zeros.
+ * Every byte of the result is written by the call, and nothing outside it.  One launch on `stream`
+ * for all blocks, and a one-workgroup launch behind it for the header.  The blocks' launch has the
+ * grid (workgroups, box, field); box r has sum_workgroups(voxels, rows) workgroups — a function of
+ * the box alone — over contiguous runs of 16-byte groups of a block; a lane owns one group (2 fp64
+ * or 4 fp32 consecutive elements of the compact block) per step and stores it with one aligned
+ * 16-byte store whatever x0 and dx are; a group may straddle a row end of the box, the source
+ * address is formed per element.  Every output element has one writer: no atomics, no workspace,
+ * no host copy, no host synchronisation, no workgroup waits for another.
+ * of3d_field_export_result_bytes: host arithmetic only; 0 (and of3d_last_error's text) on a
+ * refusal: a null pointer, an invalid box, more than 16 boxes, no field bit set (or bits beyond
+ * the four and the skip bits of the boxes), every box skipped, a workgroup share of 2^31 elements
+ * or more.  of3d_field_export refuses the same, a missing pointer, a d_result that is not 16-byte
+ * aligned, a mask_mode outside 0..3, and the vz bit in a 2D call (-1). */
+#define OF3D_EXPORT_HEAD_WORDS 8
+#define OF3D_EXPORT_ROI_WORDS 6
+#define OF3D_EXPORT_SKIP_SHIFT 16
+size_t of3d_field_export_result_bytes(const int64_t* rois, int n_roi, int fields, int v_f32, int rel_f64, int out_f32);
+int of3d_field_export(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32, int rel_f64,
+                      int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                      double tscale, const int64_t* rois, int n_roi, int fields /* bit 0 vx, 1 vy, 2 vz, 3 rel */,
+                      int mask_mode, int physical, int out_f32, const uint16_t* d_keep /* NULL: rel > *d_thresh */,
+                      void* d_result, void* stream);
+
 /* Contractility: the flow with respect to the centroid of the mask, on the device — the
  * reference's figure 2 / movie S2 (plot_figure2_movie.ipynb cell 1: com = center_of_mass(relMask),
  * normalc = -(pos - com) / |pos - com| in physical units, vnorm = v / |v|,

@@ -781,6 +781,141 @@ class _QuiverCall(_BoxCall):
         return out
 
 
+EXPORT_FIELDS = ("vx", "vy", "vz", "rel")  # of3d_field_export's field bits, in order
+EXPORT_MASKS = {None: 0, "nan": 1, "zero": 2, "summary": 3}  # its mask_mode
+_EXPORT_HEAD, _EXPORT_ROI, _EXPORT_SKIP = 8, 6, 16  # OF3D_EXPORT_HEAD_WORDS, _ROI_WORDS, _SKIP_SHIFT
+
+
+@dataclasses.dataclass
+class FieldSpec:
+    """The fields themselves, cropped to ROIs of the summary, asked of export_fields /
+    FlowStream(fields=) / process_flow(save_fields=): what the figure scripts keep of the four
+    full-size outputs (``vx(y1:y2,x1:x2,z1:z2)``, then ``vx.*relMask./relMask*xyscale/tscale``).
+
+    rois: indices into the summary's ROI list (0 = the whole volume); None: every ROI after 0,
+    or (0,) when there are none.  fields: names among vx, vy, vz, rel (2D: vz is dropped from the
+    default, and an error if named).  mask — what the (opened) reliability mask m does to a
+    velocity: None: nothing (the plain crop); "nan": ``(v*m)/m``, the figures' ``v.*relMask./relMask``;
+    "zero": ``v*m`` (plot_FigureS2_dt.m:123); "summary": ``v*m`` with exact zeros -> NaN, the
+    notebooks' and flow_summary's masking.  rel is always the plain crop.  physical: velocities
+    then become ``(v*xyscale)/tscale`` (vz: zscale).  dtype: None — every block in its field's own
+    type — or "float32": every value narrowed once, from the float64 it was computed in."""
+    rois: tuple | None = None
+    fields: tuple = EXPORT_FIELDS
+    mask: str | None = "nan"
+    physical: bool = True
+    dtype: str | None = None
+
+    def resolve(self, ndim, n_roi):
+        """Validated (rois, names, field bits, mask_mode, physical, out_f32) for an ndim-D volume
+        whose summary has n_roi boxes (the whole volume included); ValueError on a bad value."""
+        is_int = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if self.rois is None:
+            rois = tuple(range(1, n_roi)) or (0,)
+        else:
+            try:
+                rois = tuple(self.rois)
+            except TypeError:
+                raise ValueError(f"fields: rois {self.rois!r} is not a sequence of ROI indices") from None
+            if not rois or not all(is_int(r) for r in rois):
+                raise ValueError(f"fields: rois {self.rois!r} is not a non-empty sequence of ROI indices")
+            if any(not 0 <= r < n_roi for r in rois):
+                raise ValueError(f"fields: ROI index out of range in {rois} (the summary has ROIs 0..{n_roi - 1})")
+            if len(set(rois)) != len(rois):
+                raise ValueError(f"fields: duplicate ROI index in {rois}")
+            rois = tuple(int(r) for r in rois)
+        if self.fields is EXPORT_FIELDS:
+            names = tuple(n for n in EXPORT_FIELDS if ndim == 3 or n != "vz")
+        else:
+            if isinstance(self.fields, str):
+                raise ValueError(f"fields: fields {self.fields!r} is not a sequence of names among {EXPORT_FIELDS}")
+            try:
+                names = tuple(self.fields)
+            except TypeError:
+                raise ValueError(f"fields: fields {self.fields!r} is not a sequence of names among "
+                                 f"{EXPORT_FIELDS}") from None
+            if not names:
+                raise ValueError("fields: no field named")
+            for n in names:
+                if n not in EXPORT_FIELDS:
+                    raise ValueError(f"fields: unknown field name {n!r} (one of {EXPORT_FIELDS})")
+            if len(set(names)) != len(names):
+                raise ValueError(f"fields: duplicate field name in {names}")
+            if ndim == 2 and "vz" in names:
+                raise ValueError("fields: a 2D volume has no vz to export")
+        if self.mask is not None and (not isinstance(self.mask, str) or self.mask not in EXPORT_MASKS):
+            raise ValueError(f"fields: mask {self.mask!r} is not None, 'nan', 'zero' or 'summary'")
+        if self.dtype is not None and (not isinstance(self.dtype, str) or self.dtype != "float32"):
+            raise ValueError(f"fields: dtype {self.dtype!r} is not None or 'float32'")
+        bits = sum(1 << EXPORT_FIELDS.index(n) for n in names)
+        return rois, names, bits, EXPORT_MASKS[self.mask], bool(self.physical), self.dtype == "float32"
+
+
+class _ExportCall(_BoxCall):
+    """of3d_field_export bound to the summary's boxes, of which spec.rois are exported (the
+    others are listed and skipped, so every box keeps its bit of the keep volume): the size, the
+    launch and the decoding.  v_f32: whether the velocity fields are float32."""
+
+    def __init__(self, boxes, dims, rel_f64, v_f32, spec, ndim, scales):
+        super().__init__(boxes, dims, rel_f64)
+        self.ndim, self.v_f32 = int(ndim), int(bool(v_f32))
+        self.rois, self.names, bits, self.mask_mode, self.physical, self.out_f32 = spec.resolve(self.ndim,
+                                                                                                len(self.boxes))
+        self.scales = tuple(float(v) for v in scales)
+        f = bits | sum(1 << (_EXPORT_SKIP + r) for r in range(len(self.boxes)) if r not in self.rois)
+        self.fields = f - (1 << 32) if f >> 31 else f  # as a C int
+        self.v_dtype = np.dtype(np.float32 if self.out_f32 or self.v_f32 else np.float64)
+        self.rel_dtype = np.dtype(np.float32 if self.out_f32 or not self.rel_f64 else np.float64)
+        self.result_bytes = self.lib.of3d_field_export_result_bytes(self.roi_arr, len(self.boxes), self.fields,
+                                                                    self.v_f32, self.rel_f64, int(self.out_f32))
+        if self.result_bytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+
+    def new_result(self, device):
+        """The result block on `device`, 16-byte aligned as of3d_field_export asks."""
+        import torch
+
+        res = torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
+        assert res.data_ptr() % 16 == 0
+        return res
+
+    def enqueue(self, vx, vy, vz, rel, thresh_ptr, keep_ptr, result_ptr, stream):
+        """The export kernel and its header on `stream` (device pointers)."""
+        _lib.check(self.lib.of3d_field_export(vx, vy, vz or None, rel, self.v_f32, self.rel_f64, *self.dims,
+                                              thresh_ptr, *self.scales, self.roi_arr, len(self.boxes), self.fields,
+                                              self.mask_mode, int(self.physical), int(self.out_f32),
+                                              keep_ptr or None, result_ptr, stream or None))
+
+    def decode(self, words):
+        """The result words as export_fields' `blocks`: views of `words`, a host int64 array or
+        an int64 tensor (which stays where it is; only its header is read on the host)."""
+        n_roi, host = len(self.boxes), isinstance(words, np.ndarray)
+        nhead = _EXPORT_HEAD + _EXPORT_ROI * n_roi
+        head = words[:nhead] if host else words[:nhead].cpu().numpy()
+        assert (head[1] == n_roi and head[2] == self.fields & 0xFFFFFFFF and head[3] == self.mask_mode
+                and head[6] == (self.ndim == 3) and head[7] * 8 == self.result_bytes), head[:8]
+        out = []
+        for r in self.rois:
+            box = tuple(int(v) for v in self.boxes[r])
+            n, sizes, *offs = (int(v) for v in head[_EXPORT_HEAD + _EXPORT_ROI * r:_EXPORT_HEAD + _EXPORT_ROI * (r + 1)])
+            shape = tuple(box[2 * a + 1] - box[2 * a] for a in range(3))
+            assert n == int(np.prod(shape)) and sizes == self.v_dtype.itemsize + 256 * self.rel_dtype.itemsize
+            entry = {"roi": r, "box": box}
+            for name in self.names:
+                dt = self.rel_dtype if name == "rel" else self.v_dtype
+                off = offs[EXPORT_FIELDS.index(name)]
+                flat = words[off:off + (n * dt.itemsize + 7) // 8]
+                if host:
+                    flat = flat.view(dt)[:n]
+                else:
+                    import torch
+
+                    flat = flat.view(getattr(torch, dt.name))[:n]
+                entry[name] = flat.reshape(shape if self.ndim == 3 else shape[1:])
+            out.append(entry)
+        return out
+
+
 @dataclasses.dataclass
 class ContractSpec:
     """The contractility of every ROI, asked of contractility / FlowStream(contract=) /
@@ -1121,9 +1256,12 @@ class _SummaryCall(_BoxCall):
     (a QuiverSpec): also of3d_quiver_sample over the same boxes, threshold and opened mask, into
     a result block of its own (self.quiver: the _QuiverCall; enqueue's quiver_ptr).  contract (a
     ContractSpec): likewise of3d_flow_contract (self.contract: the _ContractCall; contract_ptr);
-    the quiver keeps the summary's mask whatever the contract's."""
+    the quiver keeps the summary's mask whatever the contract's.  export (a FieldSpec): likewise
+    of3d_field_export, with the summary's threshold and opened mask, after all of them
+    (self.export: the _ExportCall; export_ptr); v_f32: whether the velocity fields it will be
+    given are float32 (its blocks are sized at construction)."""
 
-    def __init__(self, spec, shape, rel_dtype, device, quiver=None, contract=None):
+    def __init__(self, spec, shape, rel_dtype, device, quiver=None, contract=None, export=None, v_f32=False):
         import torch
 
         self.spec, self.shape = spec, tuple(int(v) for v in shape)
@@ -1132,6 +1270,8 @@ class _SummaryCall(_BoxCall):
             quiver.resolve(len(self.shape))  # a bad request fails before anything is allocated
         if contract is not None:
             contract.resolve(len(self.shape))
+        if export is not None:
+            export.resolve(len(self.shape), len(boxes))
         self.min_size, self.connectivity = spec.opening(len(self.shape))
         super().__init__(boxes, self.shape if len(self.shape) == 3 else (1,) + self.shape,
                          rel_dtype == torch.float64)
@@ -1169,6 +1309,10 @@ class _SummaryCall(_BoxCall):
         if contract is not None:
             self.contract = _ContractCall(self.boxes, self.dims, self.rel_f64, contract, len(self.shape),
                                           (spec.xyscale, spec.zscale, spec.tscale), device)
+        self.export = None
+        if export is not None:
+            self.export = _ExportCall(self.boxes, self.dims, self.rel_f64, v_f32, export, len(self.shape),
+                                      (spec.xyscale, spec.zscale, spec.tscale))
         self.open =_OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
                               device) if self.min_size else None
         self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
@@ -1203,14 +1347,20 @@ class _SummaryCall(_BoxCall):
 
         return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
 
-    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream, quiver_ptr=None, contract_ptr=None):
+    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream, quiver_ptr=None, contract_ptr=None,
+                export_ptr=None):
         """Quantile + summary kernels on `stream` (device pointers; vz 0/None for 2D); with a
         quiver request, its kernels after them into the block at quiver_ptr; with a contract
-        request, its kernels after those into the block at contract_ptr."""
+        request, its kernels after those into the block at contract_ptr; with an export request,
+        its kernel last into the block at export_ptr."""
         if (self.quiver is None) != (quiver_ptr is None):
             raise ValueError("summary: quiver_ptr goes with a quiver request, and only with one")
         if (self.contract is None) != (contract_ptr is None):
             raise ValueError("summary: contract_ptr goes with a contract request, and only with one")
+        if (self.export is None) != (export_ptr is None):
+            raise ValueError("summary: export_ptr goes with an export request, and only with one")
+        if self.export is not None and self.export.v_f32 != int(bool(v_f32)):
+            raise ValueError("summary: the export was sized for the other velocity type")
         lo, hi, gamma = self.ranks
         lib, s = self.lib, self.spec
         thresh_ptr = self.thresh_ptr
@@ -1248,6 +1398,9 @@ class _SummaryCall(_BoxCall):
             self.contract.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
                                   self.open.keep.data_ptr() if self.open is not None else None, contract_ptr,
                                   stream)
+        if self.export is not None:
+            self.export.enqueue(vx, vy, vz, rel, thresh_ptr,
+                                self.open.keep.data_ptr() if self.open is not None else None, export_ptr, stream)
 
     def decode(self, words):
         """The result words (host int64 array) as flow_summary's dict."""
@@ -1740,6 +1893,58 @@ def quiver_sample(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, t
         words = res.cpu().numpy()
     return {"threshold": _np_dtype(tr).type(words[:1].view(np.float64)[0]), "rois": boxes.copy(),
             "gap": call.gap, "samples": call.decode(words)}
+
+
+def export_fields(vx, vy, vz, rel, rel_percentile=90, threshold=None, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None,
+                  spec=None, min_size=0, connectivity=None, percentile_box=None, percentile_method="linear",
+                  device=None):
+    """The fields of one frame cropped to ROIs, masked and scaled as the figure scripts do right
+    after loading them, by of3d_field_export: compact blocks, formed on the device.
+
+    Inputs, scales, rois, min_size and connectivity as flow_summary (numpy arrays or torch
+    tensors, vz None for 2D; ROI 0 is the whole volume); threshold, percentile_box and
+    percentile_method as quiver_sample.  spec: a FieldSpec (default FieldSpec(): every ROI after
+    0, all fields, mask "nan", physical units, the fields' own types); min_size >= 1 opens every
+    ROI's mask first (reliability_mask), and ROI r is masked by its own opened mask.
+    Returns a dict: threshold, rois (n_roi, 6) and blocks, a list with one dict per exported ROI:
+    roi (its index), box (6 ints) and per exported field an array of shape (dz, dy, dx) — (dy, dx)
+    in 2D.  numpy inputs give numpy arrays, torch inputs device tensors; all of them view one
+    result block.  With mask None, physical False and dtype None a block is ``f[z0:z1, y0:y1,
+    x0:x1]`` bit for bit."""
+    import torch
+
+    host = isinstance(vx, np.ndarray)
+    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    shape = tuple(int(v) for v in vx.shape)
+    if len(shape) != (3 if vz is not None else 2):
+        raise ValueError("export_fields needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+    summary = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
+    boxes = summary.resolve(shape)[0]
+    min_size, connectivity = summary.opening(len(shape))
+    spec = FieldSpec() if spec is None else spec
+    spec.resolve(len(shape), len(boxes))
+    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
+    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
+        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
+    dims = shape if len(shape) == 3 else (1,) + shape
+    rel_f64 = tr.dtype == torch.float64
+    call = _ExportCall(boxes, dims, rel_f64, tx.dtype == torch.float32, spec, len(shape), (xyscale, zscale, tscale))
+    opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tx.device) if min_size else None
+    with torch.cuda.device(tx.device):
+        stream = torch.cuda.current_stream(tx.device).cuda_stream
+        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
+                                    percentile_box, percentile_method)
+        if opening is not None:
+            counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tx.device)
+            opening.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(), stream)
+        res = call.new_result(tx.device)
+        call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
+                     thresh.data_ptr(), opening.keep.data_ptr() if opening is not None else None, res.data_ptr(),
+                     stream)
+        words = res.cpu().numpy() if host else res
+        head = words[:1] if host else words[:1].cpu().numpy()
+    return {"threshold": _np_dtype(tr).type(head.view(np.float64)[0]), "rois": boxes.copy(),
+            "blocks": call.decode(words)}
 
 
 _SPLIT_COLUMNS = {"vx": 0, "vy": 1, "vz": 2}

@@ -203,7 +203,15 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     percentile, per-ROI valid counts, mean magnitude, circular means of theta, histograms:
     analysis.flow_summary) and ``<imNameSave>_summary.csv`` (one row per frame and ROI) and
     ``<imNameSave>_summary_hist.npz`` (edges and (frames, n_roi, nbins) counts per quantity)
-    are written; save_fields=False then downloads and writes no field TIFFs at all.  A spec
+    are written; save_fields=False then downloads and writes no field TIFFs at all;
+    save_fields=analysis.FieldSpec (needs a summary) downloads and writes, instead of the four
+    full-size fields, their crops to the spec's ROIs — masked with the summary's threshold and
+    opened mask, in physical units, optionally float32, formed on the device
+    (analysis.export_fields) — as ``<imNameSave>_{vx,vy,vz,rel}_roi<r>_t%04d.tiff`` per saved
+    frame and exported ROI r (the pixel type is the block's; with matlab_output=True only
+    dtype=None), and once ``<imNameSave>_fields.csv`` with one row per exported ROI (roi, z0,
+    z1, y0, y1, x0, x1, mask, physical, dtype, xyscale, zscale, tscale); every other file is
+    what it is without it.  A spec
     with min_size >= 1 opens every ROI's reliability mask first (bwareaopen, as the figure
     scripts do) and appends the columns n_mask, n_components, n_components_kept, n_kept.  A
     spec with axes adds the mask's moments, centroid, covariance and principal axes and the flow
@@ -287,6 +295,13 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     NtSlice = math.ceil(NtChunk / 2) - 1
 
     rank, world = _dist_context()
+    from .analysis import FieldSpec
+
+    if isinstance(save_fields, FieldSpec):
+        if summary is None:
+            raise ValueError("save_fields=FieldSpec needs a summary")
+        if matlab_output and save_fields.dtype is not None:
+            raise ValueError("matlab_output writes float64 files: use FieldSpec(dtype=None)")
     if not save_fields and summary is None:
         raise ValueError("save_fields=False needs a summary")
     if quiver is not None and summary is None:
@@ -425,7 +440,10 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
     (both lines of a frame are printed once its files are written).
     out_range = (h0, h1): the windows starting at frames h0 .. h1 - 1 (a rank's block).
     summary (a SummarySpec): each frame's device-side summary is collected and written as
-    <prefix>_summary.csv / _summary_hist.npz at the end; save_fields=False: no TIFFs.  quiver (a
+    <prefix>_summary.csv / _summary_hist.npz at the end; save_fields=False: no TIFFs;
+    save_fields=FieldSpec (needs a summary): each frame's export blocks (FlowStream(fields=FieldSpec))
+    are written as <prefix>_<field>_roi<r>_t%04d.tiff by the same pool and write_fn, and
+    <prefix>_fields.csv at the end; no full-size TIFFs.  quiver (a
     QuiverSpec): each frame's quiver vectors are written as <prefix>_quiver_t%04d.npz.  contract (a
     ContractSpec): each frame's contractility is collected and written as <prefix>_contract.csv /
     _contract_hist.npz at the end."""
@@ -459,7 +477,12 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
                 write_quiver(prefix + '_quiver_t' + str(frame).zfill(4) + '.npz',
                              {"threshold": s["threshold"], "rois": s["rois"], "gap": fs.summary.quiver.gap,
                               "samples": pending.quiver()})
-            if save_fields:
+            if fs.field_spec is not None:
+                for blk in pending.fields():
+                    fields = fs.summary.export.names
+                    _write_frame(prefix, [n + '_roi' + str(blk["roi"]) for n in fields], frame,
+                                 [blk[n] for n in fields], pool, write_fn)
+            elif save_fields:
                 _write_frame(prefix, names, frame, pending.result(), pool, write_fn)
         finally:
             pending.release()
@@ -491,6 +514,20 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
         from .analysis import write_contract
 
         write_contract(prefix, frames, contracts)
+    if fs.field_spec is not None:
+        _write_fields_csv(prefix + '_fields.csv', fs.summary.export, fs.field_spec)
+
+
+def _write_fields_csv(path, export, spec):
+    """<prefix>_fields.csv: one row per exported ROI — what its TIFFs hold (export: the stream's
+    analysis._ExportCall, spec: its FieldSpec)."""
+    cols = ['roi', 'z0', 'z1', 'y0', 'y1', 'x0', 'x1', 'mask', 'physical', 'dtype', 'xyscale', 'zscale', 'tscale']
+    with open(path, 'w', newline='') as f:
+        f.write(','.join(cols) + '\n')
+        for r in export.rois:
+            vals = [r] + [int(v) for v in export.boxes[r]] + [str(spec.mask).lower(), bool(export.physical),
+                                                               export.v_dtype.name] + list(export.scales)
+            f.write(','.join(v if isinstance(v, str) else _fmt_csv(v) for v in vals) + '\n')
 
 
 def _process_slab(load_part, axis, vol, nOut, NtChunk, NtSlice, xyzSig, tSig, wSig, prefix, names, precision,

@@ -3,8 +3,8 @@
 // k_sum_boxes), the projected flow (kt_axes.hip: k_proj_boxes), the magnitude-weighted
 // histograms (kt_whist.hip: k_whist_boxes), the two-channel comparison (kt_pair.hip:
 // k_pair_boxes), the quiver samples (kt_quiver.hip: walk_wave), the contractility
-// (kt_contract.hip: k_ct_boxes), the spread (kt_spread.hip: k_spread_boxes) and the reliability
-// profile (kt_relsel.hip: k_rp_boxes): one statement of the masking arithmetic, the histogram bin
+// (kt_contract.hip: k_ct_boxes), the spread (kt_spread.hip: k_spread_boxes), the reliability
+// profile (kt_relsel.hip: k_rp_boxes) and the field export (kt_export.hip: export_block): one statement of the masking arithmetic, the histogram bin
 // search, the walk over a box, a workgroup's share of a box, the loop over its voxels and the
 // reduction of its sums, so the passes cannot drift apart.  The host side (volume and box
 // checks, workgroup plan, histogram plan, edge upload, type dispatch) is summary_host.hpp's.
@@ -30,12 +30,21 @@ __device__ __forceinline__ int find_bin(const double* e, int nb, double v) {
     return lo;
 }
 
-// example_analysis_script.ipynb cell 5 for one component: v * mask (numpy: v * bool mask),
-// exact zeros -> NaN, then (v * scale) / tscale
-__device__ __forceinline__ double masked_velocity(double v, double m, double scale, double tscale) {
+// example_analysis_script.ipynb cell 5 for one component, step by step (kt_export.hip applies the
+// steps one at a time): v * mask (numpy: v * bool mask) with exact zeros -> NaN, and the
+// physical units (v * scale) / tscale
+__device__ __forceinline__ double zeroed_to_nan(double v, double m) {
     v = v * m;
     if (v == 0.0) v = __builtin_nan("");
+    return v;
+}
+
+__device__ __forceinline__ double physical_units(double v, double scale, double tscale) {
     return (v * scale) / tscale;
+}
+
+__device__ __forceinline__ double masked_velocity(double v, double m, double scale, double tscale) {
+    return physical_units(zeroed_to_nan(v, m), scale, tscale);
 }
 
 // Quantity q of a valid voxel in of3d_flow_summary's order (0 vx, 1 vy, 2 vz, 3 magnitude,
@@ -126,13 +135,24 @@ struct Voxel {
     double xy2, sq;        // vxp^2 + vyp^2; the magnitude's square: xy2 (+ vzp^2 with a vz)
 };
 
+// RawVoxel's r of voxel i, and the mask factor (0.0 / 1.0) it stands for
+template <typename VT, typename RelT, bool Masked>
+__device__ __forceinline__ double load_mask(const FlowFields<VT, RelT, Masked>& F, size_t i) {
+    if constexpr (Masked)
+        return (F.keep[i] >> F.roi & 1) ? 1.0 : 0.0;
+    else
+        return (double)F.rel[i];
+}
+
+template <typename VT, typename RelT, bool Masked>
+__device__ __forceinline__ double mask_factor(const FlowFields<VT, RelT, Masked>& F, double r) {
+    return Masked ? r : (r > F.thr) ? 1.0 : 0.0;  // numpy: v * bool mask
+}
+
 template <typename VT, typename RelT, bool Masked>
 __device__ __forceinline__ RawVoxel load_voxel(const FlowFields<VT, RelT, Masked>& F, size_t i) {
     RawVoxel v{0.0, 0.0, 0.0, 0.0};
-    if constexpr (Masked)
-        v.r = (F.keep[i] >> F.roi & 1) ? 1.0 : 0.0;
-    else
-        v.r = (double)F.rel[i];
+    v.r = load_mask(F, i);
     v.x = (double)F.vx[i];
     v.y = (double)F.vy[i];
     if (F.is3) v.z = (double)F.vz[i];
@@ -143,7 +163,7 @@ __device__ __forceinline__ RawVoxel load_voxel(const FlowFields<VT, RelT, Masked
 // squares is NaN or >= 0, so its root is NaN exactly where it is.  The magnitude is sqrt(sq).
 template <typename VT, typename RelT, bool Masked>
 __device__ __forceinline__ Voxel physical_voxel(const FlowFields<VT, RelT, Masked>& F, const RawVoxel& raw) {
-    const double m = Masked ? raw.r : (raw.r > F.thr) ? 1.0 : 0.0;  // numpy: v * bool mask
+    const double m = mask_factor(F, raw.r);
     Voxel v;
     v.vxp = masked_velocity(raw.x, m, F.sxy, F.st);
     v.vyp = masked_velocity(raw.y, m, F.sxy, F.st);

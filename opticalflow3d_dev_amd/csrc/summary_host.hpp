@@ -1,7 +1,7 @@
 #pragma once
 // summary_host.hpp — the host side shared by the device-side summary passes (kt_summary.hip,
 // kt_ccl.hip, kt_axes.hip, kt_whist.hip, kt_pair.hip, kt_quiver.hip, kt_contract.hip, kt_spread.hip,
-// kt_relsel.hip): one statement of the volume check, the box check, the workgroup plan, the
+// kt_relsel.hip, kt_export.hip): one statement of the volume check, the box check, the workgroup plan, the
 // histogram plan with its edge validation, the edge upload and the dispatch over the field types.
 // The entry points keep their own order of argument checks; what a check tests and says is here.
 #include <hip/hip_runtime.h>

@@ -51,7 +51,8 @@ class FlowStream:
     back (at most `depth` frames in flight).  With lookahead, push one frame more than
     the window before submit() to pipeline the next window's temporal derivative.
     summary=SummarySpec: the frame is also reduced on the device (.summary() gives
-    analysis.flow_summary's dict); fields=False: only that, no field downloads."""
+    analysis.flow_summary's dict); fields=False: only that, no field downloads;
+    fields=FieldSpec: the fields cropped to ROIs, masked and scaled on the device (.fields())."""
 
     def __init__(self, ndim, vol_shape, dtype, xyzSig, tSig, wSig, device=None, depth=3, d2h="dma",
                  d2h_blocks=64, precision="fp64", rel_fp64=False, zslab=None, lookahead=None, k0_batch=None,
@@ -72,7 +73,13 @@ class FlowStream:
         with mask="largest" csrc/kt_ccl.hip's labelling and selection first) follow those, again
         into a device block and a pinned host block of their own per buffer set, copied after the
         summary words; Pending.contract() returns analysis.contractility's dict.  The quiver keeps
-        the summary's mask whatever the contract's.
+        the summary's mask whatever the contract's.  fields=analysis.FieldSpec (needs a summary):
+        instead of the full-size fields, their crops to the spec's ROIs — masked with the summary's
+        threshold and opened mask, scaled, optionally narrowed (csrc/kt_export.hip) — are formed
+        behind the summary's kernels on the compute stream, in one device block per buffer set,
+        and downloaded by the d2h path the full-size fields would take into one pinned block of
+        the same size; no full-size pinned buffer is allocated, Pending.fields() returns
+        analysis.export_fields' `blocks` and Pending.result() raises.
 
         zslab=(rank, world, group[, axis]): this process holds one slab of every frame (3D
         only) — axis 0 (default): output planes shard.zslab_bounds(nz, rank, world); axis 1:
@@ -96,10 +103,16 @@ class FlowStream:
 
         from .shard import check_slab_split, halo_planes, zslab_bounds
 
+        from .analysis import FieldSpec
+
         self.torch = torch
         self.ndim = ndim
+        self.field_spec = fields if isinstance(fields, FieldSpec) else None
+        fields = fields if self.field_spec is None else False  # no full-size downloads
         if summary is not None and zslab is not None:
             raise ValueError("FlowStream: summaries of slab streams are not supported (whole volumes only)")
+        if self.field_spec is not None and summary is None:
+            raise ValueError("FlowStream: fields=FieldSpec needs a summary")
         if not fields and summary is None:
             raise ValueError("FlowStream: fields=False needs a summary")
         if quiver is not None and summary is None:
@@ -180,7 +193,14 @@ class FlowStream:
                     self.rows_direct = True
                 except RuntimeError:  # kernels without row ranges: whole sub-volume, then a slice
                     pass
-        depth = self._fit_device_memory(depth, tdt, ndim, precision, rel_fp64)
+        export_bytes = 0
+        if self.field_spec is not None:  # sized ahead of the buffers: _SummaryCall allocates on the device
+            from .analysis import _ExportCall
+
+            export_bytes = _ExportCall(summary.resolve(self.shape)[0], (nz, ny, nx),
+                                       precision == "fp64" and (ndim == 2 or rel_fp64), precision == "fp32",
+                                       self.field_spec, ndim, (1.0, 1.0, 1.0)).result_bytes
+        depth = self._fit_device_memory(depth, tdt, ndim, precision, rel_fp64, export_bytes=export_bytes)
         # nwin + 1 (+ lookahead) slots: a new frame's upload (and halo exchange) goes to the slot
         # the frame before last read, so it overlaps the previous frame's compute
         nslot = self.nwin + 1 + self.L
@@ -233,7 +253,8 @@ class FlowStream:
         if summary is not None:
             from .analysis import _SummaryCall
 
-            self.summary = _SummaryCall(summary, self.shape, rel_t, self.dev, quiver=quiver, contract=contract)
+            self.summary = _SummaryCall(summary, self.shape, rel_t, self.dev, quiver=quiver, contract=contract,
+                                        export=self.field_spec, v_f32=precision == "fp32")
             self.dsum = [self.summary.new_result(self.dev) for _ in range(depth)]
             self.hsum = [torch.empty(self.summary.result_bytes // 8, dtype=torch.int64, pin_memory=True)
                          for _ in range(depth)]
@@ -245,6 +266,10 @@ class FlowStream:
                 self.dcont = [self.summary.contract.new_result(self.dev) for _ in range(depth)]
                 self.hcont = [torch.empty(self.summary.contract.result_bytes // 8, dtype=torch.int64,
                                           pin_memory=True) for _ in range(depth)]
+            if self.field_spec is not None:
+                assert self.summary.export.result_bytes == export_bytes
+                self.dexp = [self.summary.export.new_result(self.dev) for _ in range(depth)]
+                self.hexp = [torch.empty(export_bytes // 8, dtype=torch.int64, pin_memory=True) for _ in range(depth)]
         # row slabs without row ranges: the plan writes all rows of its sub-volume here; the own
         # rows are copied out
         self.dfull = mk(False, max(self.nblock, 1)) if self.axis == 1 and not self.rows_direct else None
@@ -254,9 +279,9 @@ class FlowStream:
         self.slot_evt = {}               # ring slot -> event of the last compute that read it
         self.k = 0
 
-    def _fit_device_memory(self, depth, tdt, ndim, precision, rel_fp64, margin=1 << 30):
-        """Output sets in flight and frames of lookahead that fit the device beside the plan's
-        workspace (already allocated): fewer output sets first, then K0 batching M -> 2 -> none
+    def _fit_device_memory(self, depth, tdt, ndim, precision, rel_fp64, margin=1 << 30, export_bytes=0):
+        """Output sets in flight (each with its export block of export_bytes, if any) and frames of
+        lookahead that fit the device beside the plan's workspace (already allocated): fewer output sets first, then K0 batching M -> 2 -> none
         (frame pipelining: -> none); raises only when even one set and no lookahead do not fit.
         Returns the depth; self.batch / self.L are updated."""
         torch = self.torch
@@ -264,7 +289,7 @@ class FlowStream:
         nout = 4 if ndim == 3 else 3
         v_sz = 4 if precision == "fp32" else 8
         rel_sz = 4 if precision == "fp32" else (8 if (ndim == 2 or rel_fp64) else 4)
-        set_b = max(self.nvox, 1) * ((nout - 1) * v_sz + rel_sz)
+        set_b = max(self.nvox, 1) * ((nout - 1) * v_sz + rel_sz) + export_bytes
         slot_b = max(self.nblock, 1) * torch.empty((), dtype=tdt).element_size()
         fixed = slot_b * (self.nwin + 1) + (max(self.nvox, 1) * slot_b // max(self.nblock, 1) if self.axis == 1 else 0)
         if self.axis == 1:  # row slabs without row ranges write a whole sub-volume set first
@@ -378,10 +403,12 @@ class FlowStream:
             # ordered behind these reads by the stream itself
             with_quiver = self.summary.quiver is not None
             with_contract = self.summary.contract is not None
+            with_export = self.summary.export is not None
             self.summary.enqueue(dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(),
                                  self.precision == "fp32", self.dsum[b].data_ptr(), self.comp.cuda_stream,
                                  quiver_ptr=self.dquiv[b].data_ptr() if with_quiver else None,
-                                 contract_ptr=self.dcont[b].data_ptr() if with_contract else None)
+                                 contract_ptr=self.dcont[b].data_ptr() if with_contract else None,
+                                 export_ptr=self.dexp[b].data_ptr() if with_export else None)
             with torch.cuda.stream(self.comp):
                 self.hsum[b].copy_(self.dsum[b], non_blocking=True)
                 if with_quiver:
@@ -395,7 +422,9 @@ class FlowStream:
         for s in self.order[:self.nwin + self.L]:  # the window and (lookahead) the next frame
             self.slot_evt[s] = cev
         self.free.append(self.order.pop(0))  # the window's oldest frame is done with (after cev)
-        if not self.fields:
+        if self.field_spec is not None:  # the export block travels as the fields would
+            hout, dout = [self.hexp[b]], [self.dexp[b]]
+        elif not self.fields:
             return pending
         if self.d2h_mode == "dma":
             self.dl_q.put((cev, hout, dout, pending))
@@ -478,16 +507,29 @@ class Pending:
         out["threshold"] = rel_dt.type(words[:1].view(np.float64)[0])
         return out
 
-    def result(self):
-        """Host arrays: views of pinned buffers, valid until release()."""
-        if not self.fs.fields:
-            raise RuntimeError("FlowStream(fields=False) downloads no fields: use summary()")
+    def _wait_download(self):
         if self.event is not None:
             self.event.synchronize()
         else:
             self.done.wait()
             if self.error is not None:
                 raise self.error
+
+    def fields(self):
+        """analysis.export_fields' `blocks` of this frame (streams created with fields=FieldSpec):
+        views of the pinned block, valid until release()."""
+        if self.fs.field_spec is None:
+            raise RuntimeError("FlowStream was created without a FieldSpec")
+        self._wait_download()
+        return self.fs.summary.export.decode(self.fs.hexp[self.b].numpy())
+
+    def result(self):
+        """Host arrays: views of pinned buffers, valid until release()."""
+        if self.fs.field_spec is not None:
+            raise RuntimeError("FlowStream(fields=FieldSpec) downloads no full-size fields: use fields()")
+        if not self.fs.fields:
+            raise RuntimeError("FlowStream(fields=False) downloads no fields: use summary()")
+        self._wait_download()
         shp, n = self.fs.shape, self.fs.nvox
         return [t.numpy()[:n].reshape(shp) for t in self.fs.hout[self.b]]
 
