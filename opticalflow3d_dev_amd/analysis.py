@@ -30,6 +30,18 @@ def _np_dtype(t):
     return np.dtype(_dtype_name(t))
 
 
+def _dims(shape):
+    """(nz, ny, nx) of a volume's shape: a 2D field is one plane."""
+    return shape if len(shape) == 3 else (1,) + shape
+
+
+def _cuda_device(device):
+    """The torch device of an entry's `device` argument (None: the library's default)."""
+    import torch
+
+    return torch.device("cuda", _lib.device_index() if device is None else device)
+
+
 def _to_device(a, host, dev):
     """A field as a contiguous tensor: a numpy array (host) uploaded to dev, a tensor where it is;
     None stays None."""
@@ -147,7 +159,7 @@ def flow_statistics(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0,
     import torch
 
     host = isinstance(vx, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
+    dev = _cuda_device(device)
     tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
     if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
         raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
@@ -341,8 +353,7 @@ class SummarySpec:
         RelProfileSpec.resolve()'s triple; ValueError on a bad value.  All None / "linear": the
         flat select (of3d_quantile); anything else goes through of3d_rel_select."""
         shape = tuple(int(v) for v in shape)
-        ndim = len(shape)
-        dims = shape if ndim == 3 else (1,) + shape
+        ndim, dims = len(shape), _dims(shape)
         box = None
         if self.percentile_box is not None:
             try:
@@ -464,7 +475,7 @@ class SummarySpec:
             raise ValueError(f"summary: volume shape {shape} is not 2D or 3D")
         ndim = len(shape)
         self.opening(ndim)
-        dims = shape if ndim == 3 else (1,) + shape
+        dims = _dims(shape)
         if not (0 <= float(self.rel_percentile) <= 100):
             raise ValueError(f"summary: rel_percentile {self.rel_percentile} outside [0, 100]")
         boxes = [(0, dims[0], 0, dims[1], 0, dims[2])]
@@ -497,14 +508,37 @@ def _decode_open_counts(words, n_roi, out):
         out[name] = counts[:, i].copy()
 
 
+def _word_threshold(words, rel_f64):
+    """The threshold a pass left in the first word of its result (a double) as a numpy scalar of
+    rel's dtype."""
+    return (np.float64 if rel_f64 else np.float32)(words[:1].view(np.float64)[0])
+
+
 class _BoxCall:
     """What every summary pass is bound to: the library, the boxes (int64 (n_roi, 6)) with their
-    ctypes view, the volume's dims (nz, ny, nx) and whether rel is float64."""
+    ctypes view, the volume's dims (nz, ny, nx), whether rel is float64 and, for the passes over
+    physical velocities, the scales (xyscale, zscale, tscale) as floats.
 
-    def __init__(self, boxes, dims, rel_f64):
+    The passes that follow the threshold on a frame (_AxesCall, _WhistCall, _SpreadCall,
+    _ProfileCall, _QuiverCall, _ContractCall, _ExportCall) share one calling convention:
+    ``enqueue(fields, thresh_ptr, keep_ptr, result_ptr, stream)`` — fields: the frame's device
+    pointers and velocity type (vx, vy, vz or None, rel, v_f32), _Frame.fields; thresh_ptr: the
+    threshold on the device; keep_ptr: the opened mask's keep volume or None; result_ptr: where
+    the pass's result_bytes go (new_result allocates them)."""
+
+    def __init__(self, boxes, dims, rel_f64, scales=None):
         self.lib, self.dims, self.rel_f64 = _lib.load(), tuple(dims), int(rel_f64)
+        self.scales = None if scales is None else tuple(float(v) for v in scales)
         self.boxes = np.ascontiguousarray(boxes, dtype=np.int64)
         self.roi_arr = self.boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+    def new_result(self, device):
+        """The result block (result_bytes) on `device`, 16-byte aligned as of3d_field_export asks."""
+        import torch
+
+        res = torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
+        assert res.data_ptr() % 16 == 0
+        return res
 
     def _bind_bins(self, nbins, edges):
         """nbins / edges (one entry per quantity, None without bins) kept, with their ctypes arrays."""
@@ -534,11 +568,16 @@ class _OpenCall(_BoxCall):
         self.min_size, self.connectivity = int(min_size), int(connectivity)
         self.ws = self._workspace(self.lib.of3d_mask_open_workspace_bytes(self.roi_arr, len(self.boxes)), device)
         self.keep = torch.empty(self.dims, dtype=torch.uint16, device=device)
+        self.result_bytes = 32 * len(self.boxes)  # d_counts
 
     def enqueue(self, rel, thresh_ptr, counts_ptr, stream):
         _lib.check(self.lib.of3d_mask_open(rel, self.rel_f64, *self.dims, thresh_ptr, self.roi_arr, len(self.boxes),
                                            self.min_size, self.connectivity, self.keep.data_ptr(), counts_ptr,
                                            self.ws.data_ptr(), stream or None))
+
+    def decode(self, words, out):
+        _decode_open_counts(words, len(self.boxes), out)
+        return out
 
     def enqueue_pair(self, rel0, thresh0_ptr, rel1, thresh1_ptr, floor, combine, counts_ptr, stream):
         """of3d_mask_open_pair: the joint mask of two channels, opened like the single one."""
@@ -552,17 +591,18 @@ class _AxesCall(_BoxCall):
     """of3d_mask_axes bound to boxes and a device: sizes, the workspace and the decoding."""
 
     def __init__(self, boxes, dims, rel_f64, request, physical, scales, device):
-        super().__init__(boxes, dims, rel_f64)
+        super().__init__(boxes, dims, rel_f64, scales)
         self.given = request[0]
         self._bind_bins(*request[1:])
-        self.physical, self.scales = int(bool(physical)), tuple(float(v) for v in scales)
+        self.physical = int(bool(physical))
         self.given_arr = (self.given.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
                           if self.given is not None else None)
         self.ws = self._workspace(self.lib.of3d_mask_axes_workspace_bytes(self.roi_arr, len(self.boxes)), device)
         self.result_bytes = self.lib.of3d_mask_axes_result_bytes(len(self.boxes), self.nb_arr)
 
-    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
         """Moments, axes and (vx given) projection kernels on `stream` (device pointers)."""
+        vx, vy, vz, rel, v_f32 = fields
         _lib.check(self.lib.of3d_mask_axes(vx or None, vy or None, vz or None, rel, int(v_f32), self.rel_f64,
                                            *self.dims, thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
                                            keep_ptr or None, self.given_arr, self.physical, self.nb_arr,
@@ -598,15 +638,15 @@ class _WhistCall(_BoxCall):
     """of3d_flow_whist bound to boxes and a device: sizes, the workspace and the decoding."""
 
     def __init__(self, boxes, dims, rel_f64, nbins, edges, scales, device):
-        super().__init__(boxes, dims, rel_f64)
+        super().__init__(boxes, dims, rel_f64, scales)
         self._bind_bins(nbins, edges)
-        self.scales = tuple(float(v) for v in scales)
         self.ws = self._workspace(
             self.lib.of3d_flow_whist_workspace_bytes(self.roi_arr, len(self.boxes), self.nb_arr), device)
         self.result_bytes = self.lib.of3d_flow_whist_result_bytes(len(self.boxes), self.nb_arr)
 
-    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
         """The accumulation and final kernels on `stream` (device pointers)."""
+        vx, vy, vz, rel, v_f32 = fields
         _lib.check(self.lib.of3d_flow_whist(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
                                             thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
                                             keep_ptr or None, self.nb_arr, self.edge_arr, result_ptr,
@@ -626,23 +666,26 @@ class _WhistCall(_BoxCall):
 class _SpreadCall(_BoxCall):
     """of3d_flow_spread bound to boxes and a device: sizes, the workspace and the decoding.
     given: None (every box about its own mean, read on the device from the summary's result) or
-    the 4 float64 values of SummarySpec.spread_request."""
+    the 4 float64 values of SummarySpec.spread_request.  It follows a summary in the summary's own
+    result block: summary_nbins are that summary's ctypes nbins, and its words begin
+    summary_before bytes ahead of the spread's."""
 
-    def __init__(self, boxes, dims, rel_f64, given, ndim, scales, device):
-        super().__init__(boxes, dims, rel_f64)
+    def __init__(self, boxes, dims, rel_f64, given, ndim, scales, device, summary_nbins, summary_before):
+        super().__init__(boxes, dims, rel_f64, scales)
         self.given, self.ndim = given, int(ndim)
+        self.summary_nbins, self.summary_before = summary_nbins, int(summary_before)
         self.given_arr = given.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if given is not None else None
-        self.scales = tuple(float(v) for v in scales)
         self.ws = self._workspace(self.lib.of3d_flow_spread_workspace_bytes(self.roi_arr, len(self.boxes)), device)
         self.result_bytes = self.lib.of3d_flow_spread_result_bytes(len(self.boxes))
 
-    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, summary_ptr, summary_nbins, result_ptr, stream):
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
         """The accumulation and final kernels on `stream` (device pointers), after the summary
-        whose result lies at summary_ptr (summary_nbins: its ctypes nbins)."""
+        whose result lies summary_before bytes ahead of result_ptr."""
+        vx, vy, vz, rel, v_f32 = fields
         _lib.check(self.lib.of3d_flow_spread(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
                                              thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
-                                             keep_ptr or None, summary_ptr, summary_nbins, self.given_arr,
-                                             result_ptr, self.ws.data_ptr(), stream or None))
+                                             keep_ptr or None, result_ptr - self.summary_before, self.summary_nbins,
+                                             self.given_arr, result_ptr, self.ws.data_ptr(), stream or None))
 
     def decode(self, words, out):
         """The block's words (host int64) added to the dict `out` (flow_summary's keys)."""
@@ -736,10 +779,9 @@ class _QuiverCall(_BoxCall):
     the decoding."""
 
     def __init__(self, boxes, dims, rel_f64, quiver, ndim, scales, device):
-        super().__init__(boxes, dims, rel_f64)
+        super().__init__(boxes, dims, rel_f64, scales)
         self.ndim = int(ndim)
         self.gap, self.max_vectors = quiver.resolve(self.ndim)
-        self.scales = tuple(float(v) for v in scales)
         ext = self.boxes[:, 1::2] - self.boxes[:, 0::2]
         self.n_lattice = np.prod((ext - 1) // np.array(self.gap, dtype=np.int64) + 1, axis=1).astype(np.int64)
         self.capacity = np.ascontiguousarray(np.minimum(self.n_lattice, self.max_vectors), dtype=np.int64)
@@ -752,13 +794,9 @@ class _QuiverCall(_BoxCall):
         if self.result_bytes == 0:
             raise ValueError("of3d: " + _lib.last_error())
 
-    def new_result(self, device):
-        import torch
-
-        return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
-
-    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
         """The count, scan and emit kernels on `stream` (device pointers)."""
+        vx, vy, vz, rel, v_f32 = fields
         _lib.check(self.lib.of3d_quiver_sample(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
                                                thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
                                                self.gap_arr, self.cap_arr, keep_ptr or None, result_ptr,
@@ -857,30 +895,35 @@ class _ExportCall(_BoxCall):
     launch and the decoding.  v_f32: whether the velocity fields are float32."""
 
     def __init__(self, boxes, dims, rel_f64, v_f32, spec, ndim, scales):
-        super().__init__(boxes, dims, rel_f64)
+        super().__init__(boxes, dims, rel_f64, scales)
         self.ndim, self.v_f32 = int(ndim), int(bool(v_f32))
-        self.rois, self.names, bits, self.mask_mode, self.physical, self.out_f32 = spec.resolve(self.ndim,
-                                                                                                len(self.boxes))
-        self.scales = tuple(float(v) for v in scales)
-        f = bits | sum(1 << (_EXPORT_SKIP + r) for r in range(len(self.boxes)) if r not in self.rois)
-        self.fields = f - (1 << 32) if f >> 31 else f  # as a C int
+        self.rois, self.names, _, self.mask_mode, self.physical, self.out_f32 = spec.resolve(self.ndim,
+                                                                                             len(self.boxes))
+        self.fields, self.result_bytes = self.size(self.boxes, self.rel_f64, self.v_f32, spec, self.ndim)
         self.v_dtype = np.dtype(np.float32 if self.out_f32 or self.v_f32 else np.float64)
         self.rel_dtype = np.dtype(np.float32 if self.out_f32 or not self.rel_f64 else np.float64)
-        self.result_bytes = self.lib.of3d_field_export_result_bytes(self.roi_arr, len(self.boxes), self.fields,
-                                                                    self.v_f32, self.rel_f64, int(self.out_f32))
-        if self.result_bytes == 0:
+
+    @staticmethod
+    def size(boxes, rel_f64, v_f32, spec, ndim):
+        """(of3d_field_export's `fields` word, its result bytes) for spec (a FieldSpec) over boxes:
+        what a block costs, known from the boxes, the types and the spec alone — FlowStream sizes
+        its buffers with it before any call exists."""
+        boxes = np.ascontiguousarray(boxes, dtype=np.int64)
+        rois, _, bits, _, _, out_f32 = spec.resolve(int(ndim), len(boxes))
+        f = bits | sum(1 << (_EXPORT_SKIP + r) for r in range(len(boxes)) if r not in rois)
+        f = f - (1 << 32) if f >> 31 else f  # as a C int
+        nbytes = _lib.load().of3d_field_export_result_bytes(boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                            len(boxes), f, int(bool(v_f32)), int(bool(rel_f64)),
+                                                            int(out_f32))
+        if nbytes == 0:
             raise ValueError("of3d: " + _lib.last_error())
+        return f, nbytes
 
-    def new_result(self, device):
-        """The result block on `device`, 16-byte aligned as of3d_field_export asks."""
-        import torch
-
-        res = torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
-        assert res.data_ptr() % 16 == 0
-        return res
-
-    def enqueue(self, vx, vy, vz, rel, thresh_ptr, keep_ptr, result_ptr, stream):
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
         """The export kernel and its header on `stream` (device pointers)."""
+        vx, vy, vz, rel, v_f32 = fields
+        if self.v_f32 != int(bool(v_f32)):
+            raise ValueError("summary: the export was sized for the other velocity type")
         _lib.check(self.lib.of3d_field_export(vx, vy, vz or None, rel, self.v_f32, self.rel_f64, *self.dims,
                                               thresh_ptr, *self.scales, self.roi_arr, len(self.boxes), self.fields,
                                               self.mask_mode, int(self.physical), int(self.out_f32),
@@ -999,10 +1042,9 @@ class _ContractCall(_BoxCall):
     words, then ("largest") of3d_mask_largest's 4 counts per box."""
 
     def __init__(self, boxes, dims, rel_f64, request, ndim, scales, device):
-        super().__init__(boxes, dims, rel_f64)
+        super().__init__(boxes, dims, rel_f64, scales)
         self.mask, connectivity, self.given, nbins, edges = request.resolve(int(ndim))
         self._bind_bins(nbins, edges)
-        self.scales = tuple(float(v) for v in scales)
         self.given_arr = (self.given.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
                           if self.given is not None else None)
         self.ws = self._workspace(
@@ -1012,14 +1054,10 @@ class _ContractCall(_BoxCall):
                         if self.mask == "largest" else None)
         self.result_bytes = self.contract_bytes + (32 * len(self.boxes) if self.largest is not None else 0)
 
-    def new_result(self, device):
-        import torch
-
-        return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
-
-    def enqueue(self, vx, vy, vz, rel, v_f32, thresh_ptr, keep_ptr, result_ptr, stream):
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
         """("largest") the labelling and selection, then the moment, centre, reduction and final
         kernels on `stream` (device pointers); keep_ptr: the summary's mask for mask="summary"."""
+        vx, vy, vz, rel, v_f32 = fields
         if self.largest is not None:
             self.largest.enqueue(rel, thresh_ptr, result_ptr + self.contract_bytes, stream)
             keep_ptr = self.largest.keep.data_ptr()
@@ -1091,26 +1129,29 @@ class _ProfileCall(_BoxCall):
     """of3d_rel_profile bound to boxes: sizes and the decoding.  Its thresholds are the n_p
     percentiles' and then the selection box's minimum and maximum (percentiles 0 and 100 of the
     same select), so that one block holds everything the profile reports; the last two also are
-    the range of the auto edges."""
+    the range of the auto edges.  thresholds: the device tensor the select leaves them in (n_p + 2
+    elements of rel's dtype, or more: the first n_p + 2 count) — the pass reads these, whatever
+    single threshold the frame's other passes share."""
 
-    def __init__(self, boxes, dims, rel_f64, percentiles, nbins, edges):
+    def __init__(self, boxes, dims, rel_f64, percentiles, nbins, edges, thresholds):
         super().__init__(boxes, dims, rel_f64)
-        self.percentiles, self.nbins, self.edges = list(percentiles), int(nbins), edges
+        self.percentiles, self.nbins, self.edges, self.thresholds = list(percentiles), int(nbins), edges, thresholds
         self.n_t = len(self.percentiles) + 2
         self.result_bytes = self.lib.of3d_rel_profile_result_bytes(len(self.boxes), self.n_t, self.nbins)
         if self.result_bytes == 0:
             raise ValueError("of3d: bad reliability profile sizes")
 
-    def enqueue(self, rel, thresh_ptr, result_ptr, stream):
-        """thresh_ptr: n_p + 2 device elements of rel's dtype (the percentiles', then min, max)."""
-        esz = 8 if self.rel_f64 else 4
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
+        """The profile kernel on `stream`, of rel (fields[3]) alone, against self.thresholds."""
+        thresh_ptr = self.thresholds.data_ptr()
         given = self.edges.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if self.edges is not None else None
-        range_ptr = None if self.edges is not None else thresh_ptr + (self.n_t - 2) * esz
-        _lib.check(self.lib.of3d_rel_profile(rel, self.rel_f64, *self.dims, self.roi_arr, len(self.boxes), thresh_ptr,
-                                             self.n_t, self.nbins, given, range_ptr, result_ptr, stream or None))
+        range_ptr = None if self.edges is not None else thresh_ptr + (self.n_t - 2) * self.thresholds.element_size()
+        _lib.check(self.lib.of3d_rel_profile(fields[3], self.rel_f64, *self.dims, self.roi_arr, len(self.boxes),
+                                             thresh_ptr, self.n_t, self.nbins, given, range_ptr, result_ptr,
+                                             stream or None))
 
-    def decode(self, words):
-        """The block's words (host int64) as reliability_profile's dict."""
+    def decode(self, words, summary=None):
+        """The block's words (host int64) as reliability_profile's dict (also summary["rel_profile"])."""
         words = np.ascontiguousarray(words, dtype=np.int64)
         n_roi, n_p, nb = len(self.boxes), self.n_t - 2, self.nbins
         assert tuple(words[:3]) == (n_roi, self.n_t, nb), words[:3]
@@ -1125,6 +1166,8 @@ class _ProfileCall(_BoxCall):
                "hist": np.ascontiguousarray(body[:, 2 + self.n_t:]).view(np.uint64),
                "edges": words[3 + self.n_t:head].view(np.float64).copy()}
         out["fraction_above"] = out["n_above"] / out["n_voxels"][:, None].astype(np.float64)
+        if summary is not None:
+            summary["rel_profile"] = out
         return out
 
 
@@ -1149,8 +1192,7 @@ def _pair_spec(shape, rel_percentile, rois, min_size, connectivity, percentile_b
     min_size, connectivity = spec.opening(len(shape))
     if min_size < 1:
         raise ValueError("summary: the joint mask needs min_size >= 1 (1: no opening)")
-    shape = tuple(int(v) for v in shape)
-    return boxes, (shape if len(shape) == 3 else (1,) + shape), min_size, connectivity
+    return boxes, _dims(tuple(int(v) for v in shape)), min_size, connectivity
 
 
 class _PairCall(_BoxCall):
@@ -1168,9 +1210,8 @@ class _PairCall(_BoxCall):
         boxes, dims, min_size, connectivity = _pair_spec(shape, rel_percentile, rois, min_size, connectivity,
                                                          percentile_box, percentile_method)
         self.floor, self.combine = _pair_options(floor, combine)
-        super().__init__(boxes, dims, rel_dtype == torch.float64)
+        super().__init__(boxes, dims, rel_dtype == torch.float64, (xyscale, zscale, tscale))
         self._bind_bins(*SummarySpec._quantity_bins(bins, len(shape), "pair ", PAIR_QUANTITIES))
-        self.scales = (float(xyscale), float(zscale), float(tscale))
         lib = self.lib
         self.rel_dt = np.dtype(np.float64 if self.rel_f64 else np.float32)
         self.open = _OpenCall(self.boxes, self.dims, self.rel_f64, min_size, connectivity, device)
@@ -1252,69 +1293,64 @@ class _PairCall(_BoxCall):
 
 
 class _SummaryCall(_BoxCall):
-    """One resolved spec bound to a device: sizes, workspaces and the kernel launches.  quiver
-    (a QuiverSpec): also of3d_quiver_sample over the same boxes, threshold and opened mask, into
-    a result block of its own (self.quiver: the _QuiverCall; enqueue's quiver_ptr).  contract (a
-    ContractSpec): likewise of3d_flow_contract (self.contract: the _ContractCall; contract_ptr);
-    the quiver keeps the summary's mask whatever the contract's.  export (a FieldSpec): likewise
-    of3d_field_export, with the summary's threshold and opened mask, after all of them
-    (self.export: the _ExportCall; export_ptr); v_f32: whether the velocity fields it will be
-    given are float32 (its blocks are sized at construction)."""
+    """One resolved spec bound to a device: sizes, workspaces and the kernel launches, as two
+    ordered lists of (name, call, where its result goes).
+
+    parts — what shares the summary's result block, (name, call, byte offset), in the block's
+    order: "summary" (this call's own words, offset 0, no call of their own), "open" (min_size >= 1: of3d_mask_open's
+    counts), "axes", "whist", "spread", "profile" (each with its request in the spec).  One
+    download brings all of them.
+
+    addons — what follows into a result block of its own, (name, call, None), in launch order:
+    "quiver" (a QuiverSpec: of3d_quiver_sample), "contract" (a ContractSpec: of3d_flow_contract;
+    the quiver keeps the summary's mask whatever the contract's) and "export" (a FieldSpec:
+    of3d_field_export, last; v_f32: whether the velocity fields it will be given are float32 —
+    its block is sized at construction).  All take the summary's boxes, threshold and opened
+    mask; enqueue's `blocks` names a device block for each.  In a FlowStream the export's block
+    alone travels on the fields' download path, the others are copied behind the summary's words.
+
+    A part or add-on is read by name — call.open, call.spread, call.quiver, ... (None without
+    it) — and a part's offset as call.spread_off, ...  The next pass is one more line in
+    __init__: part(...) or an entry of `addons`."""
 
     def __init__(self, spec, shape, rel_dtype, device, quiver=None, contract=None, export=None, v_f32=False):
         import torch
 
         self.spec, self.shape = spec, tuple(int(v) for v in shape)
+        ndim = len(self.shape)
         boxes, nbins, edges = spec.resolve(shape)
-        if quiver is not None:
-            quiver.resolve(len(self.shape))  # a bad request fails before anything is allocated
-        if contract is not None:
-            contract.resolve(len(self.shape))
-        if export is not None:
-            export.resolve(len(self.shape), len(boxes))
-        self.min_size, self.connectivity = spec.opening(len(self.shape))
-        super().__init__(boxes, self.shape if len(self.shape) == 3 else (1,) + self.shape,
-                         rel_dtype == torch.float64)
+        for request, args in ((quiver, (ndim,)), (contract, (ndim,)), (export, (ndim, len(boxes)))):
+            if request is not None:
+                request.resolve(*args)  # a bad request fails before anything is allocated
+        min_size, connectivity = spec.opening(ndim)
+        super().__init__(boxes, _dims(self.shape), rel_dtype == torch.float64,
+                         (spec.xyscale, spec.zscale, spec.tscale))
         self._bind_bins(nbins, edges)
-        lib = self.lib
-        # the summary words, then (min_size >= 1) of3d_mask_open's 4 counts per box: one download
-        self.summary_bytes = lib.of3d_flow_summary_result_bytes(len(self.boxes), self.nb_arr)
-        self.result_bytes = self.summary_bytes + (32 * len(self.boxes) if self.min_size else 0)
-        # then (axes) of3d_mask_axes' block
-        request = spec.axes_request(len(self.shape))
-        self.axes, self.axes_off = None, self.result_bytes
+        lib, bound, scales = self.lib, (self.boxes, self.dims, self.rel_f64), self.scales
+        self.parts, self.result_bytes = [], 0
+
+        def part(name, call, nbytes):
+            self.parts.append((name, call, self.result_bytes))
+            self.result_bytes += nbytes
+
+        part("summary", None, lib.of3d_flow_summary_result_bytes(len(self.boxes), self.nb_arr))  # this call's own
+        if min_size:
+            opening = _OpenCall(*bound, min_size, connectivity, device)
+            part("open", opening, opening.result_bytes)
+        self.keep_ptr = opening.keep.data_ptr() if min_size else None
+        self.followers = len(self.parts)  # the parts from here on follow the summary's kernel
+        request = spec.axes_request(ndim)
         if request is not None:
-            self.axes = _AxesCall(self.boxes, self.dims, self.rel_f64, request, spec.axes_physical,
-                                  (spec.xyscale, spec.zscale, spec.tscale), device)
-            self.result_bytes += self.axes.result_bytes
-        # then (weighted_bins) of3d_flow_whist's block
-        wnbins, wedges = spec.weighted(len(self.shape))
-        self.whist, self.whist_off = None, self.result_bytes
+            call = _AxesCall(*bound, request, spec.axes_physical, scales, device)
+            part("axes", call, call.result_bytes)
+        wnbins, wedges = spec.weighted(ndim)
         if any(wnbins):
-            self.whist = _WhistCall(self.boxes, self.dims, self.rel_f64, wnbins, wedges,
-                                    (spec.xyscale, spec.zscale, spec.tscale), device)
-            self.result_bytes += self.whist.result_bytes
-        # then (spread) of3d_flow_spread's block
-        request = spec.spread_request(len(self.shape))
-        self.spread, self.spread_off = None, self.result_bytes
+            call = _WhistCall(*bound, wnbins, wedges, scales, device)
+            part("whist", call, call.result_bytes)
+        request = spec.spread_request(ndim)
         if request is not None:
-            self.spread = _SpreadCall(self.boxes, self.dims, self.rel_f64, request[0], len(self.shape),
-                                      (spec.xyscale, spec.zscale, spec.tscale), device)
-            self.result_bytes += self.spread.result_bytes
-        self.quiver = None
-        if quiver is not None:
-            self.quiver = _QuiverCall(self.boxes, self.dims, self.rel_f64, quiver, len(self.shape),
-                                      (spec.xyscale, spec.zscale, spec.tscale), device)
-        self.contract = None
-        if contract is not None:
-            self.contract = _ContractCall(self.boxes, self.dims, self.rel_f64, contract, len(self.shape),
-                                          (spec.xyscale, spec.zscale, spec.tscale), device)
-        self.export = None
-        if export is not None:
-            self.export = _ExportCall(self.boxes, self.dims, self.rel_f64, v_f32, export, len(self.shape),
-                                      (spec.xyscale, spec.zscale, spec.tscale))
-        self.open =_OpenCall(self.boxes, self.dims, self.rel_f64, self.min_size, self.connectivity,
-                              device) if self.min_size else None
+            call = _SpreadCall(*bound, request[0], ndim, scales, device, self.nb_arr, self.result_bytes)
+            part("spread", call, call.result_bytes)
         self.ws = torch.empty(lib.of3d_flow_summary_workspace_bytes(), dtype=torch.uint8, device=device)
         self.qws = torch.empty(lib.of3d_quantile_workspace_bytes(self.rel_f64), dtype=torch.uint8, device=device)
         self.thresh = torch.empty(1, dtype=rel_dtype, device=device)
@@ -1325,7 +1361,7 @@ class _SummaryCall(_BoxCall):
         # percentiles, the box's minimum and maximum and the summary's own percentile; then
         # (rel_profile) of3d_rel_profile's block after the spread's
         box, method, profile = spec.threshold_request(self.shape)
-        self.select, self.profile, self.profile_off = None, None, self.result_bytes
+        self.select = None
         if box is not None or method != "linear" or profile is not None:
             own = float(spec.rel_percentile)
             sel = (list(profile[0]) + [0.0, 100.0]) if profile is not None else []
@@ -1339,76 +1375,62 @@ class _SummaryCall(_BoxCall):
             self.thresh = torch.empty(len(sel), dtype=rel_dtype, device=device)
             self.thresh_ptr = self.thresh.data_ptr() + sel.index(own) * self.thresh.element_size()
             if profile is not None:
-                self.profile = _ProfileCall(self.boxes, self.dims, self.rel_f64, *profile)
-                self.result_bytes += self.profile.result_bytes
+                call = _ProfileCall(*bound, *profile, self.thresh)
+                part("profile", call, call.result_bytes)
+        self.addons = []
+        if quiver is not None:
+            self.addons.append(("quiver", _QuiverCall(*bound, quiver, ndim, scales, device), None))
+        if contract is not None:
+            self.addons.append(("contract", _ContractCall(*bound, contract, ndim, scales, device), None))
+        if export is not None:
+            self.addons.append(("export", _ExportCall(*bound, v_f32, export, ndim, scales), None))
 
-    def new_result(self, device):
-        import torch
+    def __getattr__(self, name):
+        """call.<name> of a part or add-on (None without it), call.<name>_off of a part."""
+        listed = {n: (call, off) for n, call, off in self.__dict__.get("parts", []) + self.__dict__.get("addons", [])}
+        if name in ("open", "axes", "whist", "spread", "profile", "quiver", "contract", "export"):
+            return listed.get(name, (None, None))[0]
+        if name.endswith("_off") and name[:-4] in listed:
+            return listed[name[:-4]][1]
+        raise AttributeError(name)
 
-        return torch.empty(self.result_bytes // 8, dtype=torch.int64, device=device)
-
-    def enqueue(self, vx, vy, vz, rel, v_f32, result_ptr, stream, quiver_ptr=None, contract_ptr=None,
-                export_ptr=None):
-        """Quantile + summary kernels on `stream` (device pointers; vz 0/None for 2D); with a
-        quiver request, its kernels after them into the block at quiver_ptr; with a contract
-        request, its kernels after those into the block at contract_ptr; with an export request,
-        its kernel last into the block at export_ptr."""
-        if (self.quiver is None) != (quiver_ptr is None):
-            raise ValueError("summary: quiver_ptr goes with a quiver request, and only with one")
-        if (self.contract is None) != (contract_ptr is None):
-            raise ValueError("summary: contract_ptr goes with a contract request, and only with one")
-        if (self.export is None) != (export_ptr is None):
-            raise ValueError("summary: export_ptr goes with an export request, and only with one")
-        if self.export is not None and self.export.v_f32 != int(bool(v_f32)):
-            raise ValueError("summary: the export was sized for the other velocity type")
+    def enqueue(self, fields, result_ptr, stream, blocks=None):
+        """Quantile + summary kernels on `stream`, then the other parts' and the add-ons' — fields:
+        (vx, vy, vz, rel, v_f32), device pointers (vz 0/None for 2D) and whether the velocities are
+        float32; blocks: add-on name -> device pointer of its result block, for exactly the
+        add-ons that were requested."""
+        blocks = blocks or {}
+        if set(blocks) != {name for name, _, _ in self.addons}:
+            raise ValueError(f"summary: result blocks for {sorted(blocks)}, but the requests are "
+                             f"{[name for name, _, _ in self.addons]}")
+        vx, vy, vz, rel, v_f32 = fields
         lo, hi, gamma = self.ranks
-        lib, s = self.lib, self.spec
-        thresh_ptr = self.thresh_ptr
+        lib, thresh_ptr, keep_ptr = self.lib, self.thresh_ptr, self.keep_ptr
         if self.select is None:
             _lib.check(lib.of3d_quantile(rel, self.rel_f64, self.n, lo, hi, float(gamma), thresh_ptr,
                                          self.qws.data_ptr(), stream or None))
         else:
             self.select.enqueue(rel, self.thresh.data_ptr(), stream)
-        args = (vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims, thresh_ptr,
-                float(s.xyscale), float(s.zscale), float(s.tscale), self.roi_arr, len(self.boxes), self.nb_arr,
-                self.edge_arr, result_ptr, self.ws.data_ptr(), stream or None)
-        if self.open is None:
+        args = (vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims, thresh_ptr, *self.scales,
+                self.roi_arr, len(self.boxes), self.nb_arr, self.edge_arr, result_ptr, self.ws.data_ptr(),
+                stream or None)
+        if keep_ptr is None:
             _lib.check(lib.of3d_flow_summary(*args))
         else:
-            self.open.enqueue(rel, thresh_ptr, result_ptr + self.summary_bytes, stream)
-            _lib.check(lib.of3d_flow_summary_masked(*args, self.open.keep.data_ptr()))
-        if self.axes is not None:
-            self.axes.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
-                              self.open.keep.data_ptr() if self.open is not None else None,
-                              result_ptr + self.axes_off, stream)
-        if self.whist is not None:
-            self.whist.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
-                               self.open.keep.data_ptr() if self.open is not None else None,
-                               result_ptr + self.whist_off, stream)
-        if self.spread is not None:
-            self.spread.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
-                                self.open.keep.data_ptr() if self.open is not None else None, result_ptr,
-                                self.nb_arr, result_ptr + self.spread_off, stream)
-        if self.profile is not None:
-            self.profile.enqueue(rel, self.thresh.data_ptr(), result_ptr + self.profile_off, stream)
-        if self.quiver is not None:
-            self.quiver.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
-                                self.open.keep.data_ptr() if self.open is not None else None, quiver_ptr, stream)
-        if self.contract is not None:
-            self.contract.enqueue(vx, vy, vz, rel, v_f32, thresh_ptr,
-                                  self.open.keep.data_ptr() if self.open is not None else None, contract_ptr,
-                                  stream)
-        if self.export is not None:
-            self.export.enqueue(vx, vy, vz, rel, thresh_ptr,
-                                self.open.keep.data_ptr() if self.open is not None else None, export_ptr, stream)
+            _, opening, off = self.parts[1]
+            opening.enqueue(rel, thresh_ptr, result_ptr + off, stream)
+            _lib.check(lib.of3d_flow_summary_masked(*args, keep_ptr))
+        for _, call, off in self.parts[self.followers:]:
+            call.enqueue(fields, thresh_ptr, keep_ptr, result_ptr + off, stream)
+        for name, call, _ in self.addons:
+            call.enqueue(fields, thresh_ptr, keep_ptr, blocks[name], stream)
 
     def decode(self, words):
         """The result words (host int64 array) as flow_summary's dict."""
         words = np.ascontiguousarray(words, dtype=np.int64)
         n_roi, ntot = len(self.boxes), sum(self.nbins)
         body = words[_HEAD:_HEAD + n_roi * (_ROI_HEAD + ntot)].reshape(n_roi, _ROI_HEAD + ntot)
-        rel_dt = np.dtype(np.float64 if self.rel_f64 else np.float32)
-        out = {"threshold": rel_dt.type(words[:1].view(np.float64)[0]), "rois": self.boxes.copy(),
+        out = {"threshold": _word_threshold(words, self.rel_f64), "rois": self.boxes.copy(),
                "n_valid": body[:, 0].copy(), "n_voxels": body[:, 1].copy()}
         sums = np.ascontiguousarray(body[:, 2:_ROI_HEAD]).view(np.float64)
         for i, k in enumerate(SUMS):
@@ -1422,17 +1444,80 @@ class _SummaryCall(_BoxCall):
         out["theta_mean_weighted"] = np.arctan2(out["sum_mag_sin"] / nv, out["sum_mag_cos"] / nv)
         out["hist"], out["edges"] = {}, {}
         _decode_hists(body, _ROI_HEAD, QUANTITIES, self.nbins, self.edges, np.uint64, out["hist"], out["edges"])
-        if self.min_size:
-            _decode_open_counts(words[self.summary_bytes // 8:], n_roi, out)
-        if self.axes is not None:
-            self.axes.decode(words[self.axes_off // 8:], out)
-        if self.whist is not None:
-            self.whist.decode(words[self.whist_off // 8:], out)
-        if self.spread is not None:
-            self.spread.decode(words[self.spread_off // 8:], out)
-        if self.profile is not None:
-            out["rel_profile"] = self.profile.decode(words[self.profile_off // 8:])
+        for _, call, off in self.parts[1:]:
+            call.decode(words[off // 8:], out)
         return out
+
+
+class _Frame:
+    """The inputs of one public entry — (vx, vy, vz or None, rel), or rel alone (vx None) — and
+    the only place that knows how they become device state.
+
+    The constructor validates what the host objects show (a TypeError for the dtypes, a
+    ValueError for the dimensions against vz; `name`, the entry's, is what the messages say) and
+    settles host (numpy input: results come back as numpy), dev (numpy: the default or given
+    device; tensors: their own), shape, ndim, dims (nz, ny, nx), rel_dtype (torch), rel_f64 and
+    v_f32 — enough to validate the entry's other arguments and to bind its _*Call objects before
+    anything is uploaded.  ``with frame:`` then uploads (numpy) or makes contiguous (tensors) the
+    fields, enters the device and holds tx, ty, tz, tr, `fields` (the passes' (vx, vy, vz, rel,
+    v_f32) of device pointers, None for an absent field) and `stream`, the current stream."""
+
+    def __init__(self, name, vx, vy, vz, rel, device, check=True):
+        import torch
+
+        self.inputs, first = (vx, vy, vz, rel), rel if vx is None else vx
+        self.host = isinstance(rel, np.ndarray)
+        if check and vx is None and _dtype_name(rel) not in ("float32", "float64"):
+            raise TypeError("rel must be float32 or float64")
+        if check and vx is not None and not {_dtype_name(vx), _dtype_name(rel)} <= {"float32", "float64"}:
+            raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
+        self.shape = shape = tuple(int(v) for v in first.shape)
+        if check and vx is None and len(shape) not in (2, 3):
+            raise ValueError(f"{name} needs a (nz, ny, nx) or (ny, nx) field")
+        if check and vx is not None and len(shape) != (3 if vz is not None else 2):
+            raise ValueError(f"{name} needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+        self.dev = _cuda_device(device) if self.host else first.device
+        self.ndim, self.dims = len(shape), _dims(shape)
+        self.rel_dtype = getattr(torch, _dtype_name(rel))
+        self.rel_f64, self.v_f32 = self.rel_dtype == torch.float64, vx is not None and _dtype_name(vx) == "float32"
+
+    def __enter__(self):
+        import torch
+
+        self.tx, self.ty, self.tz, self.tr = t = [_to_device(a, self.host, self.dev) for a in self.inputs]
+        self.fields = tuple(a.data_ptr() if a is not None else None for a in t) + (self.v_f32,)
+        self.device_guard = torch.cuda.device(self.dev)
+        self.device_guard.__enter__()
+        self.stream = torch.cuda.current_stream(self.dev).cuda_stream
+        return self
+
+    def __exit__(self, *exc):
+        return self.device_guard.__exit__(*exc)
+
+    def threshold(self, rel_percentile, threshold=None, percentile_box=None, percentile_method="linear"):
+        """The entry's threshold as a 1-element device tensor of rel's dtype: `threshold` if
+        given, else the percentile, selected on the device (_thresholds_device)."""
+        return _thresholds_device([self.tr], rel_percentile, None if threshold is None else [threshold],
+                                  percentile_box, percentile_method)
+
+    def threshold_value(self, thresh):
+        """That tensor's value as a numpy scalar of rel's dtype (a synchronising download)."""
+        return _np_dtype(self.tr).type(thresh.cpu().numpy()[0])
+
+    def open_mask(self, boxes, min_size, connectivity, thresh, counts_ptr=None):
+        """The optional opening ahead of a pass: with min_size >= 1 an _OpenCall over `boxes`,
+        enqueued on the stream (its counts at counts_ptr, or in a tensor of its own); returns the
+        keep volume's device pointer, None without an opening."""
+        import torch
+
+        if not min_size:
+            return None
+        self.opening = _OpenCall(boxes, self.dims, self.rel_f64, min_size, connectivity, self.dev)
+        if counts_ptr is None:
+            self.counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=self.dev)
+            counts_ptr = self.counts.data_ptr()
+        self.opening.enqueue(self.fields[3], thresh.data_ptr(), counts_ptr, self.stream)
+        return self.opening.keep.data_ptr()
 
 
 def _thresholds_device(rels, rel_percentile, given, percentile_box=None, percentile_method="linear"):
@@ -1484,8 +1569,7 @@ def reliability_thresholds(rel, percentiles, box=None, method="linear", out=None
     elif (out.dtype != tr.dtype or out.device != tr.device or out.numel() != len(ps) or out.dim() != 1
           or not out.is_contiguous()):
         raise ValueError("out must be len(percentiles) contiguous elements of rel's dtype on rel's device")
-    dims = shape if len(shape) == 3 else (1,) + shape
-    call = _SelectCall(dims, tr.dtype == torch.float64, b, ps, method, tr.device)
+    call = _SelectCall(_dims(shape), tr.dtype == torch.float64, b, ps, method, tr.device)
     call.enqueue(tr.data_ptr(), out.data_ptr(), torch.cuda.current_stream(tr.device).cuda_stream)
     return out
 
@@ -1513,26 +1597,19 @@ def reliability_profile(rel, percentiles=(85, 90, 95), box=None, method="linear"
     give the same bits on every run."""
     import torch
 
-    host = isinstance(rel, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
     shape = tuple(int(v) for v in rel.shape)
     spec = SummarySpec(rois=rois, percentile_box=box, percentile_method=method,
                        rel_profile=RelProfileSpec(percentiles=tuple(percentiles), bins=bins, edges=edges))
-    boxes = spec.resolve(shape)[0]
+    boxes = spec.resolve(shape)[0]  # its message for a field that is not 2D or 3D, ahead of the frame's
     b, method, profile = spec.threshold_request(shape)
-    tr = _to_device(rel, host, dev)
-    if tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("rel must be float32 or float64")
-    dims = shape if len(shape) == 3 else (1,) + shape
-    rel_f64 = tr.dtype == torch.float64
-    select = _SelectCall(dims, rel_f64, b, list(profile[0]) + [0.0, 100.0], method, tr.device)
-    call = _ProfileCall(boxes, dims, rel_f64, *profile)
-    with torch.cuda.device(tr.device):
-        stream = torch.cuda.current_stream(tr.device).cuda_stream
-        thresh = torch.empty(select.n_q, dtype=tr.dtype, device=tr.device)
-        res = torch.empty(call.result_bytes // 8, dtype=torch.int64, device=tr.device)
-        select.enqueue(tr.data_ptr(), thresh.data_ptr(), stream)
-        call.enqueue(tr.data_ptr(), thresh.data_ptr(), res.data_ptr(), stream)
+    f = _Frame("reliability_profile", None, None, None, rel, device)
+    select = _SelectCall(f.dims, f.rel_f64, b, list(profile[0]) + [0.0, 100.0], method, f.dev)
+    thresh = torch.empty(select.n_q, dtype=f.rel_dtype, device=f.dev)
+    call = _ProfileCall(boxes, f.dims, f.rel_f64, *profile, thresh)
+    with f:
+        res = call.new_result(f.dev)
+        select.enqueue(f.fields[3], thresh.data_ptr(), f.stream)
+        call.enqueue(f.fields, None, None, res.data_ptr(), f.stream)
         return call.decode(res.cpu().numpy())
 
 
@@ -1548,6 +1625,18 @@ def _mask_dict(keep, host, boxes, counts):
     else:
         out["mask"] = lambda r: ((k.view(torch.int16) >> r) & 1).bool()  # uint16 has no shifts in torch
     _decode_open_counts(counts.cpu().numpy().reshape(-1), len(boxes), out)
+    return out
+
+
+def _mask_entry(f, call, boxes, thresh):
+    """reliability_mask's / largest_component_mask's launch and dict: call (an _OpenCall or a
+    _LargestCall over boxes) on the entered frame f at the device threshold thresh."""
+    import torch
+
+    counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=f.dev)
+    call.enqueue(f.fields[3], thresh.data_ptr(), counts.data_ptr(), f.stream)
+    out = _mask_dict(call.keep.view(f.tr.shape), f.host, boxes, counts)
+    out["threshold"] = f.threshold_value(thresh)
     return out
 
 
@@ -1570,38 +1659,22 @@ def reliability_mask(rel, rel_percentile=90, threshold=None, min_size=1, connect
     percentile_box, percentile_method (see SummarySpec): the percentile of that one box of rel,
     read in place, by "linear" or "hazen" (MATLAB's prctile) — plot_figure5.m:80-84's
     ``prctile(relCrop(:), relPer)`` (of3d_rel_select); the default is the whole field, "linear"."""
-    import torch
-
-    host = isinstance(rel, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    tr = _to_device(rel, host, dev)
-    if tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("rel must be float32 or float64")
-    if tr.dim() not in (2, 3):
-        raise ValueError("reliability_mask needs a (nz, ny, nx) or (ny, nx) field")
+    f = _Frame("reliability_mask", None, None, None, rel, device)
     spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
-    boxes = spec.resolve(tuple(tr.shape))[0]
-    min_size, connectivity = spec.opening(tr.dim())
+    boxes = spec.resolve(f.shape)[0]
+    min_size, connectivity = spec.opening(f.ndim)
     if min_size < 1:
         raise ValueError("summary: reliability_mask needs min_size >= 1")
-    dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
-    call = _OpenCall(boxes, dims, tr.dtype == torch.float64, min_size, connectivity, tr.device)
-    with torch.cuda.device(tr.device):
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
-                                    percentile_box, percentile_method)
-        counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tr.device)
-        call.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(),
-                     torch.cuda.current_stream(tr.device).cuda_stream)
-        out = _mask_dict(call.keep.view(tr.shape), host, boxes, counts)
-        out["threshold"] = _np_dtype(tr).type(thresh.cpu().numpy()[0])
-    return out
+    call = _OpenCall(boxes, f.dims, f.rel_f64, min_size, connectivity, f.dev)
+    with f:
+        return _mask_entry(f, call, boxes, f.threshold(rel_percentile, threshold, percentile_box, percentile_method))
 
 
-def _rel_pair(rel0, rel1, device, what):
-    """Two rel fields as contiguous CUDA tensors of one dtype and shape (numpy input: uploaded);
-    TypeError / ValueError before anything reaches the device."""
-    import torch
-
+def _frame_pair(what, ch0, ch1, device):
+    """The frames of two channels ((vx, vy, vz or None, rel) each; rel alone: vx None) whose rel
+    fields are of one kind, dtype and shape, on one device; `what`'s own TypeError / ValueError
+    otherwise, before anything reaches the device.  The velocities are the caller's to check."""
+    rel0, rel1 = ch0[3], ch1[3]
     host = isinstance(rel0, np.ndarray)
     if host != isinstance(rel1, np.ndarray):
         raise TypeError(f"{what}: both channels must be numpy arrays or both torch tensors")
@@ -1611,8 +1684,9 @@ def _rel_pair(rel0, rel1, device, what):
     if tuple(rel0.shape) != tuple(rel1.shape) or len(rel0.shape) not in (2, 3):
         raise ValueError(f"{what}: the rel fields must share one (nz, ny, nx) or (ny, nx) shape, got "
                          f"{tuple(rel0.shape)} and {tuple(rel1.shape)}")
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    return host, (lambda: (_to_device(rel0, host, dev), _to_device(rel1, host, dev)))
+    f0, f1 = _Frame(what, *ch0, device, check=False), _Frame(what, *ch1, device, check=False)
+    f1.dev = f0.dev
+    return f0, f1
 
 
 def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor=0.0, combine="or", min_size=1,
@@ -1635,22 +1709,21 @@ def joint_reliability_mask(rel0, rel1, rel_percentile=90, thresholds=None, floor
     same box (plot_figure3_ROIfigures.m:70-84)."""
     import torch
 
-    host, upload = _rel_pair(rel0, rel1, device, "joint_reliability_mask")
-    boxes, dims, min_size, connectivity = _pair_spec(tuple(rel0.shape), rel_percentile, rois, min_size, connectivity,
+    f0, f1 = _frame_pair("joint_reliability_mask", (None, None, None, rel0), (None, None, None, rel1), device)
+    boxes, dims, min_size, connectivity = _pair_spec(f0.shape, rel_percentile, rois, min_size, connectivity,
                                                      percentile_box, percentile_method)
     floor, combine = _pair_options(floor, combine)
     if thresholds is not None and len(thresholds) != 2:
         raise ValueError("joint_reliability_mask: thresholds must be two values, one per channel")
-    t0, t1 = upload()
-    call = _OpenCall(boxes, dims, t0.dtype == torch.float64, min_size, connectivity, t0.device)
-    with torch.cuda.device(t0.device):
-        thresh = _thresholds_device([t0, t1], rel_percentile, thresholds, percentile_box, percentile_method)
-        counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=t0.device)
+    call = _OpenCall(boxes, dims, f0.rel_f64, min_size, connectivity, f0.dev)
+    with f0, f1:
+        thresh = _thresholds_device([f0.tr, f1.tr], rel_percentile, thresholds, percentile_box, percentile_method)
+        counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=f0.dev)
         esz = thresh.element_size()
-        call.enqueue_pair(t0.data_ptr(), thresh.data_ptr(), t1.data_ptr(), thresh.data_ptr() + esz, floor, combine,
-                          counts.data_ptr(), torch.cuda.current_stream(t0.device).cuda_stream)
-        out = _mask_dict(call.keep.view(t0.shape), host, boxes, counts)
-        out["thresholds"] = thresh.cpu().numpy().astype(_np_dtype(t0))
+        call.enqueue_pair(f0.fields[3], thresh.data_ptr(), f1.fields[3], thresh.data_ptr() + esz, floor, combine,
+                          counts.data_ptr(), f0.stream)
+        out = _mask_dict(call.keep.view(f0.tr.shape), f0.host, boxes, counts)
+        out["thresholds"] = thresh.cpu().numpy().astype(_np_dtype(f0.tr))
     return out
 
 
@@ -1680,14 +1753,13 @@ def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale
     hist[name] (n_roi, nbins) uint64 with edges[name].  An empty box gives NaN means.
     percentile_box, percentile_method as joint_reliability_mask.
     Bit-reproducible: the same inputs give the same bits on every run."""
-    import torch
-
     ch0, ch1 = tuple(ch0), tuple(ch1)
     if len(ch0) != 4 or len(ch1) != 4:
         raise ValueError("channel_compare: a channel is (vx, vy, vz or None, rel)")
-    host, upload_rel = _rel_pair(ch0[3], ch1[3], device, "channel_compare")
     if in_plane:
         ch0, ch1 = (ch0[0], ch0[1], None, ch0[3]), (ch1[0], ch1[1], None, ch1[3])
+    f0, f1 = _frame_pair("channel_compare", ch0, ch1, device)
+    host = f0.host
     if (ch0[2] is None) != (ch1[2] is None):
         raise ValueError("channel_compare: vz of both channels or of neither")
     shape = tuple(ch0[3].shape)
@@ -1703,18 +1775,10 @@ def channel_compare(ch0, ch1, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale
         raise TypeError("channel_compare: all velocity fields must be float64, or all float32")
     if any(tuple(a.shape) != shape for a in fields):
         raise ValueError(f"channel_compare: every field must have the shape {shape}")
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    if not host:
-        dev = ch0[3].device
-    rel_dtype = torch.float64 if str(ch0[3].dtype).endswith("float64") else torch.float32
-    call = _PairCall(shape, rel_dtype, dev, rel_percentile, xyscale, zscale, tscale, rois, bins, floor, combine,
+    call = _PairCall(shape, f0.rel_dtype, f0.dev, rel_percentile, xyscale, zscale, tscale, rois, bins, floor, combine,
                      min_size, connectivity, percentile_box, percentile_method)
-    r0, r1 = upload_rel()
-    t0, t1 = ([_to_device(a, host, dev) for a in ch[:3]] + [r] for ch, r in ((ch0, r0), (ch1, r1)))
-    ptrs = lambda t: tuple(a.data_ptr() if a is not None else None for a in t)
-    with torch.cuda.device(dev):
-        res = call.enqueue(ptrs(t0), ptrs(t1), t0[0].dtype == torch.float32,
-                           torch.cuda.current_stream(dev).cuda_stream)
+    with f0, f1:
+        res = call.enqueue(f0.fields[:4], f1.fields[:4], f0.v_f32, f0.stream)
         return call.decode(res.cpu().numpy())
 
 
@@ -1735,36 +1799,22 @@ def principal_axes(rel, rel_percentile=90, threshold=None, min_size=0, connectiv
     percentile_method as reliability_mask."""
     import torch
 
-    host = isinstance(rel, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    tr = _to_device(rel, host, dev)
-    if tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("rel must be float32 or float64")
-    if tr.dim() not in (2, 3):
-        raise ValueError("principal_axes needs a (nz, ny, nx) or (ny, nx) field")
+    f = _Frame("principal_axes", None, None, None, rel, device)
     spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity,
                        axes="mask", axes_physical=physical)
-    boxes = spec.resolve(tuple(tr.shape))[0]
-    min_size, connectivity = spec.opening(tr.dim())
-    dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
-    rel_f64 = tr.dtype == torch.float64
-    call = _AxesCall(boxes, dims, rel_f64, spec.axes_request(tr.dim()), physical, (xyscale, zscale, 1.0), tr.device)
-    opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tr.device) if min_size else None
-    with torch.cuda.device(tr.device):
-        stream = torch.cuda.current_stream(tr.device).cuda_stream
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
-                                    percentile_box, percentile_method)
-        res = torch.empty(call.result_bytes // 8 + 4 * len(boxes), dtype=torch.int64, device=tr.device)
-        counts_ptr = res.data_ptr() + call.result_bytes
-        if opening is not None:
-            opening.enqueue(tr.data_ptr(), thresh.data_ptr(), counts_ptr, stream)
-        call.enqueue(None, None, None, tr.data_ptr(), 0, thresh.data_ptr(),
-                     opening.keep.data_ptr() if opening is not None else None, res.data_ptr(), stream)
+    boxes = spec.resolve(f.shape)[0]
+    min_size, connectivity = spec.opening(f.ndim)
+    call = _AxesCall(boxes, f.dims, f.rel_f64, spec.axes_request(f.ndim), physical, (xyscale, zscale, 1.0), f.dev)
+    with f:
+        thresh = f.threshold(rel_percentile, threshold, percentile_box, percentile_method)
+        res = torch.empty(call.result_bytes // 8 + 4 * len(boxes), dtype=torch.int64, device=f.dev)
+        keep_ptr = f.open_mask(boxes, min_size, connectivity, thresh, res.data_ptr() + call.result_bytes)
+        call.enqueue(f.fields, thresh.data_ptr(), keep_ptr, res.data_ptr(), f.stream)
         words = res.cpu().numpy()
-        out = {"rois": boxes.copy(), "threshold": _np_dtype(tr).type(thresh.cpu().numpy()[0])}
+        out = {"rois": boxes.copy(), "threshold": f.threshold_value(thresh)}
     call.decode(words, out, projected=False)
     del out["axes_used"]
-    if opening is not None:
+    if min_size:
         _decode_open_counts(words[call.result_bytes // 8:], len(boxes), out)
     return out
 
@@ -1812,23 +1862,24 @@ def flow_summary(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, ts
     RelProfileSpec): the dict also holds rel_profile, reliability_profile's dict for the same box
     and method, from the same select.  Without the three the threshold is of3d_quantile's.
     Bit-reproducible: the same inputs give the same bits on every run."""
-    import torch
-
-    host = isinstance(vx, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
-    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
-    if tx.dim() != (3 if tz is not None else 2):
-        raise ValueError("flow_summary needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+    f = _Frame("flow_summary", vx, vy, vz, rel, device)
     spec = SummarySpec(rois, bins, rel_percentile, xyscale, zscale, tscale, min_size, connectivity, axes,
                        axes_physical, axis_bins, weighted_bins=weighted_bins, spread=spread,
                        percentile_box=percentile_box, percentile_method=percentile_method, rel_profile=rel_profile)
-    call = _SummaryCall(spec, tuple(tx.shape), tr.dtype, tx.device)
-    res = call.new_result(tx.device)
-    call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
-                 tx.dtype == torch.float32, res.data_ptr(), torch.cuda.current_stream(tx.device).cuda_stream)
-    return call.decode(res.cpu().numpy())
+    call = _SummaryCall(spec, f.shape, f.rel_dtype, f.dev)
+    with f:
+        res = call.new_result(f.dev)
+        call.enqueue(f.fields, res.data_ptr(), f.stream)
+        return call.decode(res.cpu().numpy())
+
+
+def _one_pass(f, call, boxes, min_size, connectivity, thresh):
+    """One pass of the common calling convention on the entered frame f at the device threshold
+    thresh, behind the optional opening of the mask: its result tensor, still on the device."""
+    res = call.new_result(f.dev)
+    call.enqueue(f.fields, thresh.data_ptr(), f.open_mask(boxes, min_size, connectivity, thresh), res.data_ptr(),
+                 f.stream)
+    return res
 
 
 # ---------------------------------------------------------------------------
@@ -1860,39 +1911,17 @@ def quiver_sample(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, t
     are held).  For each field f in physical units, v's column equals
     ``f[z0:z1:gz, y0:y1:gy, x0:x1:gx][valid]`` bit for bit.
     Bit-reproducible: the same inputs give the same bits, in the same order, on every run."""
-    import torch
-
-    host = isinstance(vx, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    shape = tuple(int(v) for v in vx.shape)
-    if len(shape) != (3 if vz is not None else 2):
-        raise ValueError("quiver_sample needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+    f = _Frame("quiver_sample", vx, vy, vz, rel, device)
     spec = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
-    boxes = spec.resolve(shape)[0]
-    min_size, connectivity = spec.opening(len(shape))
-    request = QuiverSpec(gap=gap, max_vectors=max_vectors)
-    request.resolve(len(shape))
-    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
-    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
-    dims = shape if len(shape) == 3 else (1,) + shape
-    rel_f64 = tr.dtype == torch.float64
-    call = _QuiverCall(boxes, dims, rel_f64, request, len(shape), (xyscale, zscale, tscale), tx.device)
-    opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tx.device) if min_size else None
-    with torch.cuda.device(tx.device):
-        stream = torch.cuda.current_stream(tx.device).cuda_stream
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
-                                    percentile_box, percentile_method)
-        if opening is not None:
-            counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tx.device)
-            opening.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(), stream)
-        res = call.new_result(tx.device)
-        call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
-                     tx.dtype == torch.float32, thresh.data_ptr(),
-                     opening.keep.data_ptr() if opening is not None else None, res.data_ptr(), stream)
-        words = res.cpu().numpy()
-    return {"threshold": _np_dtype(tr).type(words[:1].view(np.float64)[0]), "rois": boxes.copy(),
-            "gap": call.gap, "samples": call.decode(words)}
+    boxes = spec.resolve(f.shape)[0]
+    min_size, connectivity = spec.opening(f.ndim)
+    call = _QuiverCall(boxes, f.dims, f.rel_f64, QuiverSpec(gap=gap, max_vectors=max_vectors), f.ndim,
+                       (xyscale, zscale, tscale), f.dev)
+    with f:
+        words = _one_pass(f, call, boxes, min_size, connectivity,
+                          f.threshold(rel_percentile, threshold, percentile_box, percentile_method)).cpu().numpy()
+    return {"threshold": _word_threshold(words, f.rel_f64), "rois": boxes.copy(), "gap": call.gap,
+            "samples": call.decode(words)}
 
 
 def export_fields(vx, vy, vz, rel, rel_percentile=90, threshold=None, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None,
@@ -1911,40 +1940,18 @@ def export_fields(vx, vy, vz, rel, rel_percentile=90, threshold=None, xyscale=1.
     in 2D.  numpy inputs give numpy arrays, torch inputs device tensors; all of them view one
     result block.  With mask None, physical False and dtype None a block is ``f[z0:z1, y0:y1,
     x0:x1]`` bit for bit."""
-    import torch
-
-    host = isinstance(vx, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    shape = tuple(int(v) for v in vx.shape)
-    if len(shape) != (3 if vz is not None else 2):
-        raise ValueError("export_fields needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
+    f = _Frame("export_fields", vx, vy, vz, rel, device)
     summary = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
-    boxes = summary.resolve(shape)[0]
-    min_size, connectivity = summary.opening(len(shape))
-    spec = FieldSpec() if spec is None else spec
-    spec.resolve(len(shape), len(boxes))
-    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
-    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
-    dims = shape if len(shape) == 3 else (1,) + shape
-    rel_f64 = tr.dtype == torch.float64
-    call = _ExportCall(boxes, dims, rel_f64, tx.dtype == torch.float32, spec, len(shape), (xyscale, zscale, tscale))
-    opening = _OpenCall(boxes, dims, rel_f64, min_size, connectivity, tx.device) if min_size else None
-    with torch.cuda.device(tx.device):
-        stream = torch.cuda.current_stream(tx.device).cuda_stream
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
-                                    percentile_box, percentile_method)
-        if opening is not None:
-            counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tx.device)
-            opening.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(), stream)
-        res = call.new_result(tx.device)
-        call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
-                     thresh.data_ptr(), opening.keep.data_ptr() if opening is not None else None, res.data_ptr(),
-                     stream)
-        words = res.cpu().numpy() if host else res
-        head = words[:1] if host else words[:1].cpu().numpy()
-    return {"threshold": _np_dtype(tr).type(head.view(np.float64)[0]), "rois": boxes.copy(),
-            "blocks": call.decode(words)}
+    boxes = summary.resolve(f.shape)[0]
+    min_size, connectivity = summary.opening(f.ndim)
+    call = _ExportCall(boxes, f.dims, f.rel_f64, f.v_f32, FieldSpec() if spec is None else spec, f.ndim,
+                       (xyscale, zscale, tscale))
+    with f:
+        words = _one_pass(f, call, boxes, min_size, connectivity,
+                          f.threshold(rel_percentile, threshold, percentile_box, percentile_method))
+        head = words[:1].cpu().numpy()
+        words = words.cpu().numpy() if f.host else words
+    return {"threshold": _word_threshold(head, f.rel_f64), "rois": boxes.copy(), "blocks": call.decode(words)}
 
 
 _SPLIT_COLUMNS = {"vx": 0, "vy": 1, "vz": 2}
@@ -2013,28 +2020,12 @@ def largest_component_mask(rel, rel_percentile=90, threshold=None, connectivity=
     mask (r -> that bit plane as bool), rois, threshold and per ROI n_mask, n_components,
     n_components_kept (0 or 1), n_kept (int64).  percentile_box, percentile_method as
     reliability_mask."""
-    import torch
-
-    host = isinstance(rel, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    tr = _to_device(rel, host, dev)
-    if tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("rel must be float32 or float64")
-    if tr.dim() not in (2, 3):
-        raise ValueError("largest_component_mask needs a (nz, ny, nx) or (ny, nx) field")
-    boxes = SummarySpec(rois=rois, rel_percentile=rel_percentile).resolve(tuple(tr.shape))[0]
-    connectivity = ContractSpec(connectivity=connectivity).resolve(tr.dim())[1]
-    dims = tuple(tr.shape) if tr.dim() == 3 else (1,) + tuple(tr.shape)
-    call = _LargestCall(boxes, dims, tr.dtype == torch.float64, connectivity, tr.device)
-    with torch.cuda.device(tr.device):
-        thresh = _thresholds_device([tr], rel_percentile, None if threshold is None else [threshold],
-                                    percentile_box, percentile_method)
-        counts = torch.empty((len(boxes), 4), dtype=torch.int64, device=tr.device)
-        call.enqueue(tr.data_ptr(), thresh.data_ptr(), counts.data_ptr(),
-                     torch.cuda.current_stream(tr.device).cuda_stream)
-        out = _mask_dict(call.keep.view(tr.shape), host, boxes, counts)
-        out["threshold"] = _np_dtype(tr).type(thresh.cpu().numpy()[0])
-    return out
+    f = _Frame("largest_component_mask", None, None, None, rel, device)
+    boxes = SummarySpec(rois=rois, rel_percentile=rel_percentile).resolve(f.shape)[0]
+    connectivity = ContractSpec(connectivity=connectivity).resolve(f.ndim)[1]
+    call = _LargestCall(boxes, f.dims, f.rel_f64, connectivity, f.dev)
+    with f:
+        return _mask_entry(f, call, boxes, f.threshold(rel_percentile, threshold, percentile_box, percentile_method))
 
 
 def contractility(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, tscale=1.0, rois=None, spec=None,
@@ -2058,30 +2049,14 @@ def contractility(vx, vy, vz, rel, rel_percentile=90, xyscale=1.0, zscale=1.0, t
     percentile_box, percentile_method as reliability_mask.
     A cosine that rounding left a last bit beyond +-1 gives exactly 0 or 180 degrees where the
     notebook's arccos gives NaN.  Bit-reproducible: the same inputs give the same bits on every run."""
-    import torch
-
-    host = isinstance(vx, np.ndarray)
-    dev = torch.device("cuda", _lib.device_index() if device is None else device)
-    shape = tuple(int(v) for v in vx.shape)
-    if len(shape) != (3 if vz is not None else 2):
-        raise ValueError("contractility needs (nz, ny, nx) fields with vz, (ny, nx) fields without")
-    boxes = SummarySpec(rois=rois, rel_percentile=rel_percentile).resolve(shape)[0]
-    spec = ContractSpec() if spec is None else spec
-    spec.resolve(len(shape))
-    tx, ty, tz, tr = (_to_device(a, host, dev) for a in (vx, vy, vz, rel))
-    if tx.dtype not in (torch.float64, torch.float32) or tr.dtype not in (torch.float32, torch.float64):
-        raise TypeError("vx/vy/vz must be float64 or float32, rel float32 or float64")
-    dims = shape if len(shape) == 3 else (1,) + shape
-    call = _ContractCall(boxes, dims, tr.dtype == torch.float64, spec, len(shape), (xyscale, zscale, tscale),
-                         tx.device)
-    with torch.cuda.device(tx.device):
-        stream = torch.cuda.current_stream(tx.device).cuda_stream
-        thresh = _thresholds_device([tr], rel_percentile, None, percentile_box, percentile_method)
-        res = call.new_result(tx.device)
-        call.enqueue(tx.data_ptr(), ty.data_ptr(), tz.data_ptr() if tz is not None else None, tr.data_ptr(),
-                     tx.dtype == torch.float32, thresh.data_ptr(), None, res.data_ptr(), stream)
-        out = call.decode(res.cpu().numpy())
-        out["threshold"] = _np_dtype(tr).type(thresh.cpu().numpy()[0])
+    f = _Frame("contractility", vx, vy, vz, rel, device)
+    boxes = SummarySpec(rois=rois, rel_percentile=rel_percentile).resolve(f.shape)[0]
+    call = _ContractCall(boxes, f.dims, f.rel_f64, ContractSpec() if spec is None else spec, f.ndim,
+                         (xyscale, zscale, tscale), f.dev)
+    with f:
+        thresh = f.threshold(rel_percentile, None, percentile_box, percentile_method)
+        out = call.decode(_one_pass(f, call, boxes, 0, None, thresh).cpu().numpy())
+        out["threshold"] = f.threshold_value(thresh)
     return out
 
 

@@ -197,9 +197,9 @@ class FlowStream:
         if self.field_spec is not None:  # sized ahead of the buffers: _SummaryCall allocates on the device
             from .analysis import _ExportCall
 
-            export_bytes = _ExportCall(summary.resolve(self.shape)[0], (nz, ny, nx),
-                                       precision == "fp64" and (ndim == 2 or rel_fp64), precision == "fp32",
-                                       self.field_spec, ndim, (1.0, 1.0, 1.0)).result_bytes
+            export_bytes = _ExportCall.size(summary.resolve(self.shape)[0],
+                                            precision == "fp64" and (ndim == 2 or rel_fp64), precision == "fp32",
+                                            self.field_spec, ndim)[1]
         depth = self._fit_device_memory(depth, tdt, ndim, precision, rel_fp64, export_bytes=export_bytes)
         # nwin + 1 (+ lookahead) slots: a new frame's upload (and halo exchange) goes to the slot
         # the frame before last read, so it overlaps the previous frame's compute
@@ -249,7 +249,7 @@ class FlowStream:
                                [torch.empty(n, dtype=rel_t, device=None if pin else self.dev, pin_memory=pin)]
         self.dout = [mk(False) for _ in range(depth)]
         self.hout = [mk(True) if self.fields else None for _ in range(depth)]
-        self.summary = None
+        self.summary, self.addon = None, {}
         if summary is not None:
             from .analysis import _SummaryCall
 
@@ -258,18 +258,14 @@ class FlowStream:
             self.dsum = [self.summary.new_result(self.dev) for _ in range(depth)]
             self.hsum = [torch.empty(self.summary.result_bytes // 8, dtype=torch.int64, pin_memory=True)
                          for _ in range(depth)]
-            if quiver is not None:
-                self.dquiv = [self.summary.quiver.new_result(self.dev) for _ in range(depth)]
-                self.hquiv = [torch.empty(self.summary.quiver.result_bytes // 8, dtype=torch.int64, pin_memory=True)
-                              for _ in range(depth)]
-            if contract is not None:
-                self.dcont = [self.summary.contract.new_result(self.dev) for _ in range(depth)]
-                self.hcont = [torch.empty(self.summary.contract.result_bytes // 8, dtype=torch.int64,
-                                          pin_memory=True) for _ in range(depth)]
+            # the add-ons' own blocks per buffer set, name -> (device, pinned): copied behind the
+            # summary's words on the compute stream — but for "export", whose block travels on the
+            # fields' download path in their place (submit)
+            self.addon = {name: [(call.new_result(self.dev),
+                                  torch.empty(call.result_bytes // 8, dtype=torch.int64, pin_memory=True))
+                                 for _ in range(depth)] for name, call, _ in self.summary.addons}
             if self.field_spec is not None:
                 assert self.summary.export.result_bytes == export_bytes
-                self.dexp = [self.summary.export.new_result(self.dev) for _ in range(depth)]
-                self.hexp = [torch.empty(export_bytes // 8, dtype=torch.int64, pin_memory=True) for _ in range(depth)]
         # row slabs without row ranges: the plan writes all rows of its sub-volume here; the own
         # rows are copied out
         self.dfull = mk(False, max(self.nblock, 1)) if self.axis == 1 and not self.rows_direct else None
@@ -401,20 +397,14 @@ class FlowStream:
             # on the compute stream: behind this frame's kernels and ahead of every later frame's,
             # so a later submit() that reuses this set's device outputs (after its release()) is
             # ordered behind these reads by the stream itself
-            with_quiver = self.summary.quiver is not None
-            with_contract = self.summary.contract is not None
-            with_export = self.summary.export is not None
-            self.summary.enqueue(dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(),
-                                 self.precision == "fp32", self.dsum[b].data_ptr(), self.comp.cuda_stream,
-                                 quiver_ptr=self.dquiv[b].data_ptr() if with_quiver else None,
-                                 contract_ptr=self.dcont[b].data_ptr() if with_contract else None,
-                                 export_ptr=self.dexp[b].data_ptr() if with_export else None)
+            self.summary.enqueue((dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(),
+                                  self.precision == "fp32"), self.dsum[b].data_ptr(), self.comp.cuda_stream,
+                                 blocks={name: sets[b][0].data_ptr() for name, sets in self.addon.items()})
             with torch.cuda.stream(self.comp):
                 self.hsum[b].copy_(self.dsum[b], non_blocking=True)
-                if with_quiver:
-                    self.hquiv[b].copy_(self.dquiv[b], non_blocking=True)
-                if with_contract:
-                    self.hcont[b].copy_(self.dcont[b], non_blocking=True)
+                for name, sets in self.addon.items():
+                    if name != "export":
+                        sets[b][1].copy_(sets[b][0], non_blocking=True)
                 pending.sum_event = torch.cuda.Event()
                 pending.sum_event.record(self.comp)
         cev = torch.cuda.Event()
@@ -423,7 +413,7 @@ class FlowStream:
             self.slot_evt[s] = cev
         self.free.append(self.order.pop(0))  # the window's oldest frame is done with (after cev)
         if self.field_spec is not None:  # the export block travels as the fields would
-            hout, dout = [self.hexp[b]], [self.dexp[b]]
+            dout, hout = ([t] for t in self.addon["export"][b])
         elif not self.fields:
             return pending
         if self.d2h_mode == "dma":
@@ -489,22 +479,24 @@ class Pending:
         self.sum_event.synchronize()
         return self.fs.summary.decode(self.fs.hsum[self.b].numpy().copy())
 
+    def _addon(self, name):
+        """The decoded block of the add-on `name` of this frame, from a copy of its pinned words,
+        once the summary's copies are done."""
+        if self.sum_event is None or name not in self.fs.addon:
+            raise RuntimeError(f"FlowStream was created without a {name} request")
+        self.sum_event.synchronize()
+        return getattr(self.fs.summary, name).decode(self.fs.addon[name][self.b][1].numpy().copy())
+
     def quiver(self):
         """analysis.quiver_sample's per-ROI list of this frame (streams created with quiver=)."""
-        if self.sum_event is None or self.fs.summary.quiver is None:
-            raise RuntimeError("FlowStream was created without a quiver request")
-        self.sum_event.synchronize()
-        return self.fs.summary.quiver.decode(self.fs.hquiv[self.b].numpy().copy())
+        return self._addon("quiver")
 
     def contract(self):
         """analysis.contractility's dict of this frame (streams created with contract=)."""
-        if self.sum_event is None or self.fs.summary.contract is None:
-            raise RuntimeError("FlowStream was created without a contract request")
-        self.sum_event.synchronize()
-        out = self.fs.summary.contract.decode(self.fs.hcont[self.b].numpy().copy())
-        words = self.fs.hsum[self.b].numpy()
-        rel_dt = np.dtype(np.float64 if self.fs.summary.rel_f64 else np.float32)
-        out["threshold"] = rel_dt.type(words[:1].view(np.float64)[0])
+        from .analysis import _word_threshold
+
+        out = self._addon("contract")
+        out["threshold"] = _word_threshold(self.fs.hsum[self.b].numpy(), self.fs.summary.rel_f64)
         return out
 
     def _wait_download(self):
@@ -521,7 +513,7 @@ class Pending:
         if self.fs.field_spec is None:
             raise RuntimeError("FlowStream was created without a FieldSpec")
         self._wait_download()
-        return self.fs.summary.export.decode(self.fs.hexp[self.b].numpy())
+        return self.fs.summary.export.decode(self.fs.addon["export"][self.b][1].numpy())
 
     def result(self):
         """Host arrays: views of pinned buffers, valid until release()."""

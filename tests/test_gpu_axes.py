@@ -231,7 +231,7 @@ def test_deterministic_and_independent_of_other_boxes(vol3):
         t = [torch.as_tensor(a).to(dev) for a in (vx, vy, vz, rel)]
         call = analysis._SummaryCall(spec, SHAPE3, t[3].dtype, dev)
         res = call.new_result(dev)
-        call.enqueue(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), False, res.data_ptr(),
+        call.enqueue((t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), False), res.data_ptr(),
                      torch.cuda.current_stream(dev).cuda_stream)
         per_box = call.axes.result_bytes // 8 // len(call.boxes)
         return res.cpu().numpy()[call.axes_off // 8:], per_box

@@ -166,8 +166,8 @@ def _raw(f, rois, per, spec, scales=cr.SCALES):
                          len(shape), tuple(scales.values()), dev[0].device)
     res = torch.full((call.result_bytes // 8 + TAIL,), CANARY, dtype=torch.int64, device=dev[0].device)
     thresh = percentile_threshold_device(dev[3], per)
-    call.enqueue(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr() if dev[2] is not None else None,
-                 dev[3].data_ptr(), False, thresh.data_ptr(), None, res.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    call.enqueue((dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr() if dev[2] is not None else None,
+                  dev[3].data_ptr(), False), thresh.data_ptr(), None, res.data_ptr(), torch.cuda.current_stream().cuda_stream)
     return call, res.cpu().numpy()
 
 

@@ -29,7 +29,7 @@ def _export_into(result, f, spec, v_f32=False):
                           (KW["xyscale"], KW["zscale"], KW["tscale"]))
     assert call.result_bytes == result.numel() * result.element_size()
     thresh = an.percentile_threshold_device(t[3], KW["rel_percentile"])
-    call.enqueue(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), thresh.data_ptr(), None,
+    call.enqueue((t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), v_f32), thresh.data_ptr(), None,
                  result.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return call

@@ -204,7 +204,7 @@ def _raw(f, rois, gap, max_vectors, percentile=60):
                        tuple(SCALES.values()), dev[0].device)
     res = torch.full((call.result_bytes // 8 + TAIL,), int(CANARY), dtype=torch.int64, device=dev[0].device)
     thresh = percentile_threshold_device(dev[3], percentile)
-    call.enqueue(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), False, thresh.data_ptr(),
+    call.enqueue((dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), False), thresh.data_ptr(),
                  None, res.data_ptr(), torch.cuda.current_stream().cuda_stream)
     return call, res.cpu().numpy()
 

@@ -131,7 +131,7 @@ def _raw(fields, spec):
     dev = [torch.from_numpy(a).cuda() for a in fields]
     call = _SummaryCall(spec, fields[0].shape, dev[-1].dtype, dev[0].device)
     res = call.new_result(dev[0].device)
-    call.enqueue(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), False, res.data_ptr(),
+    call.enqueue((dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), False), res.data_ptr(),
                  torch.cuda.current_stream().cuda_stream)
     return call, res.cpu().numpy()
 

@@ -49,7 +49,7 @@ def main():
     spec = SummarySpec(min_size=args.min_size, connectivity=26, axes="mask", axis_bins=bins, **SCALES)
     call = _SummaryCall(spec, dims, rel.dtype, rel.device)
     res = call.new_result(rel.device)
-    call.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), vx.dtype == torch.float32,
+    call.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), vx.dtype == torch.float32),
                  res.data_ptr(), stream)  # leaves the threshold and keep on the device
     summary = call.decode(res.cpu().numpy())
     thresh, keep, ax = call.thresh, call.open.keep, call.axes
@@ -59,11 +59,11 @@ def main():
     out_full = torch.empty(ax.result_bytes // 8, dtype=torch.int64, device=rel.device)
     out_mask = torch.empty(mask_only.result_bytes // 8, dtype=torch.int64, device=rel.device)
     v_f32 = vx.dtype == torch.float32
-    b_full = lambda: ax.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32,
+    b_full = lambda: ax.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32),
                                 thresh.data_ptr(), keep.data_ptr(), out_full.data_ptr(), stream)
-    b_mask_keep = lambda: mask_only.enqueue(None, None, None, rel.data_ptr(), 0, thresh.data_ptr(), keep.data_ptr(),
+    b_mask_keep = lambda: mask_only.enqueue((None, None, None, rel.data_ptr(), 0), thresh.data_ptr(), keep.data_ptr(),
                                             out_mask.data_ptr(), stream)
-    b_mask_rel = lambda: mask_only.enqueue(None, None, None, rel.data_ptr(), 0, thresh.data_ptr(), None,
+    b_mask_rel = lambda: mask_only.enqueue((None, None, None, rel.data_ptr(), 0), thresh.data_ptr(), None,
                                            out_mask.data_ptr(), stream)
     host = {}
 

@@ -60,7 +60,7 @@ def main():
 
     def route_b(name):
         select()
-        calls[name].enqueue(*ptrs, thresh.data_ptr(), None, results[name].data_ptr(), stream)
+        calls[name].enqueue(ptrs, thresh.data_ptr(), None, results[name].data_ptr(), stream)
 
     hist = calls["hist"]
     counts = torch.empty((1, 4), dtype=torch.int64, device=rel.device)

@@ -59,8 +59,8 @@ def part1(args):
     def bound(spec):
         call = _ExportCall(boxes, dims, rel_f64, v_f32, spec, 3, scales)
         out = call.new_result(rel.device)
-        run = lambda: call.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), thresh.data_ptr(), None,
-                                   out.data_ptr(), stream)
+        run = lambda: call.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32), thresh.data_ptr(),
+                                   None, out.data_ptr(), stream)
         return call, out, run
 
     cases = [("whole", FieldSpec(rois=(0,), mask=None, physical=False), 0, 0),

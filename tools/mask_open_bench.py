@@ -52,8 +52,8 @@ def part1(args, trace_only=False):
     plain = _SummaryCall(SummarySpec(**SCALES), dims, rel.dtype, rel.device)
     opened = _SummaryCall(SummarySpec(min_size=args.min_size, connectivity=26, **SCALES), dims, rel.dtype, rel.device)
     res_p, res_o = plain.new_result(rel.device), opened.new_result(rel.device)
-    enq = lambda call, res: call.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(),
-                                         vx.dtype == torch.float32, res.data_ptr(), stream)
+    enq = lambda call, res: call.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(),
+                                          vx.dtype == torch.float32), res.data_ptr(), stream)
     run_plain, run_opened = (lambda: enq(plain, res_p)), (lambda: enq(opened, res_o))
     run_opened()  # leaves the threshold on the device
     thresh = opened.thresh

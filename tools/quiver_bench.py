@@ -68,7 +68,7 @@ def main():
         make = lambda cap: _QuiverCall(boxes, dims, rel.dtype == torch.float64, QuiverSpec(gap, cap), 3, scales, rel.device)
         call = make(0)  # the count alone first: the block is then sized to hold every valid record, no more
         out = call.new_result(rel.device)
-        call.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32, thresh.data_ptr(), None,
+        call.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32), thresh.data_ptr(), None,
                      out.data_ptr(), stream)
         call = make(call.decode(out.cpu().numpy())[0]["n_valid"])
         out = call.new_result(rel.device)
@@ -76,7 +76,7 @@ def main():
         got, lists = {}, {}
 
         def kernels_b():
-            call.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32, thresh.data_ptr(), None,
+            call.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32), thresh.data_ptr(), None,
                          out.data_ptr(), stream)
 
         def route_b():

@@ -69,7 +69,7 @@ def main():
     sel3 = _SelectCall(dims, f64, None, PCTS, "linear", rel.device)
     sel5 = _SelectCall(dims, f64, None, PCTS + [0.0, 100.0], "linear", rel.device)
     selbox = _SelectCall(dims, f64, box, PCTS, "linear", rel.device)
-    prof = _ProfileCall(rois, dims, f64, PCTS, 50, None)
+    prof = _ProfileCall(rois, dims, f64, PCTS, 50, None, out5)
     res_f = torch.empty(prof.result_bytes // 8, dtype=torch.int64, device=rel.device)
 
     def route_b(src=rel, out=out_q):
@@ -81,7 +81,7 @@ def main():
     route_e = lambda: selbox.enqueue(rel.data_ptr(), out_e.data_ptr(), stream)
     crop = lambda: rel[box[0]:box[1], box[2]:box[3], box[4]:box[5]].contiguous()
     route_e_copy = lambda: route_b(crop(), out_eq)
-    route_f = lambda: prof.enqueue(rel.data_ptr(), out5.data_ptr(), res_f.data_ptr(), stream)
+    route_f = lambda: prof.enqueue((None, None, None, rel.data_ptr(), 0), None, None, res_f.data_ptr(), stream)
     host = {}
 
     def route_a():

@@ -62,20 +62,19 @@ def main():
     plain = _SummaryCall(SummarySpec(**SCALES), dims, rel.dtype, rel.device)
     call = _SummaryCall(SummarySpec(spread="mean", **SCALES), dims, rel.dtype, rel.device)
     res_plain, res = plain.new_result(rel.device), call.new_result(rel.device)
-    call.enqueue(*ptrs, res.data_ptr(), stream)  # leaves the threshold and the summary's words on the device
+    call.enqueue(ptrs, res.data_ptr(), stream)  # leaves the threshold and the summary's words on the device
     summary = call.decode(res.cpu().numpy())
     thresh, spread = call.thresh, call.spread
     opening = _OpenCall(call.boxes, dims, call.rel_f64, 1, 26, rel.device)
     counts = torch.empty((len(call.boxes), 4), dtype=torch.int64, device=rel.device)
     opening.enqueue(rel.data_ptr(), thresh.data_ptr(), counts.data_ptr(), stream)
-    out_b = torch.empty(spread.result_bytes // 8, dtype=torch.int64, device=rel.device)
 
-    def run(keep_ptr):
-        spread.enqueue(*ptrs, thresh.data_ptr(), keep_ptr, res.data_ptr(), call.nb_arr, out_b.data_ptr(), stream)
+    def run(keep_ptr):  # into its own part of res, behind the summary's words it reads
+        spread.enqueue(ptrs, thresh.data_ptr(), keep_ptr, res.data_ptr() + call.spread_off, stream)
 
     route_b, route_c = (lambda: run(None)), (lambda: run(opening.keep.data_ptr()))
-    route_d0 = lambda: plain.enqueue(*ptrs, res_plain.data_ptr(), stream)
-    route_d1 = lambda: call.enqueue(*ptrs, res.data_ptr(), stream)
+    route_d0 = lambda: plain.enqueue(ptrs, res_plain.data_ptr(), stream)
+    route_d1 = lambda: call.enqueue(ptrs, res.data_ptr(), stream)
     host = {}
 
     def route_a():

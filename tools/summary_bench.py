@@ -114,8 +114,8 @@ def part1(args):
     def new_route(bins):
         call = _SummaryCall(SummarySpec(bins=bins, **SCALES), tuple(vx.shape), rel.dtype, vx.device)
         res = call.new_result(vx.device)
-        run = lambda: call.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(),
-                                   vx.dtype == torch.float32, res.data_ptr(), stream)
+        run = lambda: call.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(),
+                                    vx.dtype == torch.float32), res.data_ptr(), stream)
         return call, res, run
 
     lin = lambda a, b: np.linspace(a, b, 37)

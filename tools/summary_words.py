@@ -112,7 +112,7 @@ def generate(skip=()):
                                        weighted_bins=pick(WEIGHTED_BINS), **SCALES)
                     call = _SummaryCall(spec, shape, t0[3].dtype, dev)
                     res = call.new_result(dev)
-                    call.enqueue(ptr(t0[0]), ptr(t0[1]), ptr(t0[2]), ptr(t0[3]), v_f32, res.data_ptr(), stream)
+                    call.enqueue((ptr(t0[0]), ptr(t0[1]), ptr(t0[2]), ptr(t0[3]), v_f32), res.data_ptr(), stream)
                     out[f"{tag}/summary/m{min_size}/{axes_name}"] = res.cpu().numpy()
                     if min_size and axes_name == "mask" and not v_f32:
                         out[f"{case}/r{np.dtype(rdt).itemsize * 8}/keep"] = call.open.keep.cpu().numpy()
@@ -120,7 +120,7 @@ def generate(skip=()):
                         alone = _AxesCall(call.boxes, call.dims, call.rel_f64,
                                           SummarySpec(axes="mask").axes_request(nd), True, (0.4, 1.5, 1.0), dev)
                         ares = torch.empty(alone.result_bytes // 8, dtype=torch.int64, device=dev)
-                        alone.enqueue(None, None, None, ptr(t0[3]), 0, call.thresh.data_ptr(),
+                        alone.enqueue((None, None, None, ptr(t0[3]), 0), call.thresh.data_ptr(),
                                       call.open.keep.data_ptr(), ares.data_ptr(), stream)
                         out[f"{case}/r{np.dtype(rdt).itemsize * 8}/axes_alone"] = ares.cpu().numpy()
             # spread, quiver and contract: (spread, quiver, contract mask, contract centre) per run
@@ -140,8 +140,8 @@ def generate(skip=()):
                     res = call.new_result(dev)
                     qres = None if quiver is None else torch.zeros_like(call.quiver.new_result(dev))
                     cres = torch.zeros_like(call.contract.new_result(dev))
-                    call.enqueue(ptr(t0[0]), ptr(t0[1]), ptr(t0[2]), ptr(t0[3]), v_f32, res.data_ptr(), stream,
-                                 quiver_ptr=ptr(qres), contract_ptr=cres.data_ptr())
+                    blocks = {"contract": cres.data_ptr()} | ({} if quiver is None else {"quiver": qres.data_ptr()})
+                    call.enqueue((ptr(t0[0]), ptr(t0[1]), ptr(t0[2]), ptr(t0[3]), v_f32), res.data_ptr(), stream, blocks)
                     out[f"{tag}/contract/{cmask}/m{min_size}/{centre}"] = cres.cpu().numpy()
                     if spread is not None:
                         out[f"{tag}/spread/m{min_size}/{sp}"] = res[call.spread_off // 8:].cpu().numpy()

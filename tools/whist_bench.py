@@ -47,7 +47,7 @@ def main():
     spec = SummarySpec(weighted_bins={"phi": phi_edges}, **SCALES)
     call = _SummaryCall(spec, dims, rel.dtype, rel.device)
     res = call.new_result(rel.device)
-    call.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), vx.dtype == torch.float32,
+    call.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), vx.dtype == torch.float32),
                  res.data_ptr(), stream)  # leaves the threshold on the device
     summary = call.decode(res.cpu().numpy())
     thresh, one = call.thresh, call.whist
@@ -57,7 +57,7 @@ def main():
     out_one = torch.empty(one.result_bytes // 8, dtype=torch.int64, device=rel.device)
     out_all = torch.empty(allq.result_bytes // 8, dtype=torch.int64, device=rel.device)
     v_f32 = vx.dtype == torch.float32
-    run = lambda c, out: c.enqueue(vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32,
+    run = lambda c, out: c.enqueue((vx.data_ptr(), vy.data_ptr(), vz.data_ptr(), rel.data_ptr(), v_f32),
                                    thresh.data_ptr(), None, out.data_ptr(), stream)
     route_b, route_c = (lambda: run(one, out_one)), (lambda: run(allq, out_all))
     host = {}
