@@ -25,7 +25,9 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference/src/Python/calc_flow.py"
 sys.dont_write_bytecode = True
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(HERE))
 
+from domain_frames import block_frames, zero_tensor  # noqa: E402
 from oracle import cpu_ref  # noqa: E402
 
 
@@ -57,6 +59,16 @@ def wave_u16(shape, k, freq, speed):
     """A plane wave 2000 + 900 sin(freq (k . (x, y, z)) + speed t) (uint16)."""
     t, z, y, x = np.meshgrid(*(np.arange(n, dtype=np.float64) for n in shape), indexing="ij")
     return np.round(2000 + 900 * np.sin(freq * (k[0] * x + k[1] * y + k[2] * z) + speed * t)).astype(np.uint16)
+
+
+def flat_blocks_u16(shape, seed, sig):
+    """domain_frames.block_frames reduced to fixture size: full-range uint16 noise around a
+    saturated and a zero-filled block, the blocks' margins narrowed (z 1, y 1, x 2) until each
+    is wider than 2 (rd + rw) + 1 = 19 and some voxels keep an exactly zero tensor."""
+    img = block_frames(shape, seed, zm=1, ym=1, xm=2)
+    st = (cpu_ref.structure_tensor3d if img.ndim == 4 else cpu_ref.structure_tensor2d)(img, *sig)
+    assert zero_tensor(st).sum() >= 4 and img.max() == 65535 and (img >= 32768).mean() > 0.3
+    return img
 
 
 def smooth_noise_u16(shape, seed):
@@ -102,6 +114,9 @@ CASES_3D = [
     ("c3d_ramp_xy_planar", lambda: ramp_u16((7, 10, 24, 28), (1, 3, 0), 14, 5), (1, 1, 2)),
     ("c3d_wave_planar", lambda: wave_u16((7, 10, 24, 28), (1, 2, 0), 0.35, -0.3), (1, 1, 3)),
     ("c3d_iso_smoothed_noise", lambda: smooth_noise_u16((7, 12, 30, 32), 18), (1, 1, 4)),
+    # saturated and zero-filled blocks in full-range noise: exact zeros in every pass, signed-zero
+    # velocities, bit 15 of the frames set (tests/domain_frames.py)
+    ("c3d_flat_blocks", lambda: flat_blocks_u16((7, 21, 21, 48), 19, (1, 1, 2)), (1, 1, 2)),
 ]
 
 CASES_2D = [
@@ -113,6 +128,7 @@ CASES_2D = [
     ("c2d_smooth_translate", lambda: cpu_ref.synthetic_stack_np((7, 40, 36), seed=25), (1, 1, 3)),
     ("c2d_nonsquare", lambda: rand_u16((7, 3, 50), 26), (1, 1, 2)),
     ("c2d_big_sigmas", lambda: rand_u16((7, 40, 44), 27), (9, 1, 17)),
+    ("c2d_flat_blocks", lambda: flat_blocks_u16((7, 24, 48), 28, (1, 1, 2)), (1, 1, 2)),
 ]
 
 ERROR_CASES = [

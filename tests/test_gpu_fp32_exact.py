@@ -208,20 +208,18 @@ def _family_image(i):
     return img[:, 0] if nd == 2 else img
 
 
-@pytest.mark.parametrize("i,variant", _family_params())
-def test_family_fp32_exact(i, variant, monkeypatch):
-    shape, sig, nd = FAMILY_SHAPES[i]
+def assert_family_ran(variant, kernels, geom, shape, sig, nd, fp32):
+    """The forced variant ran the kernels it names, or, where the shape makes it ineligible on
+    purpose, the fallback did: from plan.kernels() and plan.geometry() after an execution on
+    shape (uint16 frames) at sigmas sig, in the fp32 mode or in fp64."""
     rd, rs, rt, rw = radii(*sig)
     nx = shape[-1]
-    img = _family_image(i)
     force = VARIANTS[variant]
-    out, kernels, geom = _run_plan(img, sig, nd, force, old=force is None, env=VARIANT_ENV.get(variant),
-                                   monkeypatch=monkeypatch)
-    print(f"{shape} {sig} {variant}: kernels {kernels} geometry {geom}")
-    # which kernels this shape can run (uint16 frames, float fields; of3d_host.hip)
-    k12_ok = nd == 3 and nx % 8 == 0 and rd in (3, 6, 9)
-    k5c_ok = nd == 3 and nx % 4 == 0 and rw in K5C_RW
-    assert "general" not in kernels and geom["general"] == 0 and geom["fp32"] == 1
+    # which kernels this shape can run (uint16 frames: 16-byte rows at nx % 8; fields of the pass
+    # type: at nx % 4 in float32, nx % 2 in fp64; K12 has no fp64 instance at rd 9; of3d_host.hip)
+    k12_ok = nd == 3 and nx % 8 == 0 and rd in ((3, 6, 9) if fp32 else (3, 6))
+    k5c_ok = nd == 3 and nx % (4 if fp32 else 2) == 0 and rw in K5C_RW
+    assert "general" not in kernels and geom["general"] == 0 and geom["fp32"] == int(fp32)
     if variant == "old":
         assert not set(kernels) & set(NEW_NAMES), kernels
         assert {"k_grad_xy", "k_prod_wy", "k_wx"} <= set(kernels), kernels
@@ -259,6 +257,17 @@ def test_family_fp32_exact(i, variant, monkeypatch):
         assert (geom["wxy_zt"] != 0) == (k5c_ok and nx % 32 == 0), geom
         if geom["wxy_zt"]:
             assert geom["wxy_zt"] == geom["cap_planes"] == shape[1], geom
+
+
+@pytest.mark.parametrize("i,variant", _family_params())
+def test_family_fp32_exact(i, variant, monkeypatch):
+    shape, sig, nd = FAMILY_SHAPES[i]
+    img = _family_image(i)
+    force = VARIANTS[variant]
+    out, kernels, geom = _run_plan(img, sig, nd, force, old=force is None, env=VARIANT_ENV.get(variant),
+                                   monkeypatch=monkeypatch)
+    print(f"{shape} {sig} {variant}: kernels {kernels} geometry {geom}")
+    assert_family_ran(variant, kernels, geom, shape, sig, nd, fp32=True)
     (_check3d if nd == 3 else _check2d)(out, _oracle(("family", i), img, sig, nd))
 
 

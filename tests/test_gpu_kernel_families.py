@@ -43,7 +43,7 @@ def _run(img, s, t, w, ndim, mode, old, force=None, kernels=None, geometry=None)
         rt = radii(s, t, w)[2]
         c = nt // 2
         win = np.ascontiguousarray(img[c - rt:c + rt + 1]).reshape((2 * rt + 1,) + vol)
-        d_in = torch.from_numpy(win.view(np.int16)).to(dev)
+        d_in = torch.from_numpy(win.view(np.uint8).reshape(2 * rt + 1, -1)).to(dev)  # any input type, as bytes
         fp32 = bool(mode & _lib.OF3D_FP32)
         vt = torch.float32 if fp32 else torch.float64
         n = nz * ny * nx
@@ -51,7 +51,7 @@ def _run(img, s, t, w, ndim, mode, old, force=None, kernels=None, geometry=None)
         (*outs, rel), check_all = poison.guarded_set(n, [vt, vt, vt, reld], dev)
         plan = _lib.Plan(ndim, nz, ny, nx, make_taps(s, t, w), device=0, mode=mode)
         try:
-            plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.OF3D_U16, 0, 0, nz,
+            plan.execute([d_in[i].data_ptr() for i in range(2 * rt + 1)], _lib.DTYPE_CODES[img.dtype], 0, 0, nz,
                          outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), rel.data_ptr())
             torch.cuda.synchronize(dev)
             check_all(used=(0, 1, 2, 3) if ndim == 3 else (0, 1, 3))  # (2D: no vz)

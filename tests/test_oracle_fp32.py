@@ -49,6 +49,15 @@ FP32_ORACLE_BOUND = 4 * 1.32e-5
 # float32 passes give other noise: measured 0.637 of max|v|.  Held to 4 x that; all it says is
 # that the result stays finite and of the golden's magnitude.
 FP32_ORACLE_BOUND_SINGULAR = {"c3d_ramp_xyz_rank1": 4 * 0.637}
+# c3d_flat_blocks / c2d_flat_blocks hold a block saturated at 65535.  Inside it the smoothing
+# passes return values near 65535, where a float32 ulp is 2^-8, and the derivative pass that
+# follows takes differences of them: what is left of the gradient deep in the block (the far
+# tails of the noise outside) is of that size, so the float32 tensor there is a few 1e-4 off
+# in relative terms and v with it.  The largest errors sit at such voxels (|v| of the order of
+# max|v|, e.g. (11, 13, 11) and (7, 12)): measured 5.9e-4 (3D, vz) and 1.2e-4 (2D, vx) of
+# max|v|.  Held to 4 x that, as above; outside the blocks the float32 oracle is as close as on
+# noise.  Its zeros, and their signs, are the fp64 oracle's exactly (test_value_domain_cpu.py).
+FP32_ORACLE_BOUND_SINGULAR.update({"c3d_flat_blocks": 4 * 5.9e-4, "c2d_flat_blocks": 4 * 1.2e-4})
 
 
 @pytest.mark.parametrize("name", golden_cases("c3d") + golden_cases("c2d"))
