@@ -54,13 +54,18 @@ def _check_args(images, ndim, tSig, msg_ndim):
         sys.exit(MSG_ODD)
 
 
+def _native(dtype):
+    """dtype in the machine's byte order (a big-endian TIFF's pixels are swapped on the way in)."""
+    return dtype.newbyteorder("=") if dtype.byteorder not in ("=", "|") else dtype
+
+
 def _device_array(images):
     """C-contiguous native-endian array of a dtype the kernels read directly.
 
     Other real dtypes are cast with astype(np.float64) — the same cast the
     reference applies to every input (calc_flow.py:225 / :67)."""
     a = np.asarray(images)
-    dt = a.dtype.newbyteorder("=") if a.dtype.byteorder not in ("=", "|") else a.dtype
+    dt = _native(a.dtype)
     if dt in _lib.DTYPE_CODES:
         a = np.ascontiguousarray(a, dtype=dt)
     else:
@@ -136,20 +141,14 @@ def _flow_fp32(images, ndim, xyzSig, tSig, wSig):
     a = np.asarray(images)
     rt = math.ceil(3 * tSig)
     c = a.shape[0] // 2
-    dt = a.dtype.newbyteorder("=") if a.dtype.byteorder not in ("=", "|") else a.dtype
     shape = a.shape[1:]
     if int(np.prod(shape)) == 0:
         out = np.empty(shape, np.float32)
         return tuple(out.copy() for _ in range(ndim + 1))
-    fs = FlowStream(ndim, shape, dt, xyzSig, tSig, wSig, depth=1, precision="fp32")
-    try:
-        for k in range(c - rt, c + rt + 1):
-            fs.push(a[k])
-        pend = fs.submit()
-        out = tuple(o.copy() for o in pend.result())
-        pend.release()
-    finally:
-        fs.close()
+    with FlowStream(ndim, shape, _native(a.dtype), xyzSig, tSig, wSig, depth=1, precision="fp32") as fs:
+        for _, pend in fs.windows(a.__getitem__, c - rt, 1):
+            out = tuple(o.copy() for o in pend.result())
+            pend.release()
     return out
 
 
@@ -296,18 +295,11 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
 
     rank, world = _dist_context()
     from .analysis import FieldSpec
+    from .stream import require_summary
 
-    if isinstance(save_fields, FieldSpec):
-        if summary is None:
-            raise ValueError("save_fields=FieldSpec needs a summary")
-        if matlab_output and save_fields.dtype is not None:
-            raise ValueError("matlab_output writes float64 files: use FieldSpec(dtype=None)")
-    if not save_fields and summary is None:
-        raise ValueError("save_fields=False needs a summary")
-    if quiver is not None and summary is None:
-        raise ValueError("quiver needs a summary")
-    if contract is not None and summary is None:
-        raise ValueError("contract needs a summary")
+    require_summary(summary, save_fields, quiver, contract, "", "save_fields")
+    if isinstance(save_fields, FieldSpec) and matlab_output and save_fields.dtype is not None:
+        raise ValueError("matlab_output writes float64 files: use FieldSpec(dtype=None)")
     if summary is not None and world > 1:
         raise ValueError("summary: sharded summaries (several ranks) are not supported")
     if summary is not None and NtChunk != 2 * math.ceil(3 * tSig) + 1:
@@ -432,6 +424,42 @@ class _Shape:
         self.shape = shape
 
 
+def _peek(load, i0):
+    """(frame i0, load): the frame read to learn a series' shape and dtype, and a loader that
+    hands that frame over at its one later request instead of reading it again."""
+    held = [np.asarray(load(i0))]
+    return held[0], lambda i: held.pop() if i == i0 and held else load(i)
+
+
+def _drive(fs, load, first, count, NtSlice, nfiles, finish):
+    """One stream through the windows first .. first + count - 1 of a series (FlowStream.windows
+    reads and uploads each frame once, ahead of the compute); finish(pool, frame, start, pending)
+    runs per window on a writer thread, in order, beside the next windows' transfer and
+    compute, with a pool of nfiles threads for its files.  `start` is when the previous window
+    was handed over (the first: when the uploads began)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from .stream import Writer
+
+    def job(frame, start, pending):
+        try:
+            finish(pool, frame, start, pending)
+        finally:
+            pending.release()
+
+    pool = ThreadPoolExecutor(nfiles)
+    writer = Writer(job)
+    try:
+        start = datetime.now()
+        for hh, pending in fs.windows(load, first, count):
+            writer.put(hh + NtSlice, start, pending)
+            start = datetime.now()
+    finally:
+        writer.close()
+        pool.shutdown()
+        fs.close()
+
+
 def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig, wSig, prefix, names,
                     precision="fp64", write_fn=None, summary=None, save_fields=True, quiver=None, contract=None):
     """process_flow's loop on a device-resident frame ring (stream.py): one
@@ -447,65 +475,42 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
     QuiverSpec): each frame's quiver vectors are written as <prefix>_quiver_t%04d.npz.  contract (a
     ContractSpec): each frame's contractility is collected and written as <prefix>_contract.csv /
     _contract_hist.npz at the end."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    from .stream import FlowStream, Writer
+    from .stream import FlowStream
 
     h0, h1 = out_range
-    first = np.asarray(load_frame(h0))
+    first, load = _peek(load_frame, h0)
     if len((NtChunk,) + first.shape) != ndim + 1:
         print(_now() + ' - Processing frame ' + str(NtSlice) + '...')
         _check_args(_Shape((NtChunk,) + first.shape), ndim + 1, tSig, MSG_NDIM_3D if ndim == 3 else MSG_NDIM_2D)
-    dt = first.dtype.newbyteorder('=') if first.dtype.byteorder not in ('=', '|') else first.dtype
-    fs = FlowStream(ndim, first.shape, dt, xyzSig, tSig, wSig, precision=precision,
+    fs = FlowStream(ndim, first.shape, _native(first.dtype), xyzSig, tSig, wSig, precision=precision,
                     rel_fp64=write_fn is not None and ndim == 3, summary=summary, fields=save_fields, quiver=quiver,
                     contract=contract)
     frames, summaries, contracts = [], [], []
 
-    def finish(frame, start, start_str, pending):
-        print(start_str + ' - Processing frame ' + str(frame) + '...')
-        try:
-            if summary is not None:
-                frames.append(frame)
-                summaries.append(pending.summary())
-            if contract is not None:
-                contracts.append(pending.contract())
-            if quiver is not None:
-                from .analysis import write_quiver
+    def finish(pool, frame, start, pending):
+        print(str(start) + ' - Processing frame ' + str(frame) + '...')
+        if summary is not None:
+            frames.append(frame)
+            summaries.append(pending.summary())
+        if contract is not None:
+            contracts.append(pending.contract())
+        if quiver is not None:
+            from .analysis import write_quiver
 
-                s = summaries[-1]
-                write_quiver(prefix + '_quiver_t' + str(frame).zfill(4) + '.npz',
-                             {"threshold": s["threshold"], "rois": s["rois"], "gap": fs.summary.quiver.gap,
-                              "samples": pending.quiver()})
-            if fs.field_spec is not None:
-                for blk in pending.fields():
-                    fields = fs.summary.export.names
-                    _write_frame(prefix, [n + '_roi' + str(blk["roi"]) for n in fields], frame,
-                                 [blk[n] for n in fields], pool, write_fn)
-            elif save_fields:
-                _write_frame(prefix, names, frame, pending.result(), pool, write_fn)
-        finally:
-            pending.release()
+            s = summaries[-1]
+            write_quiver(prefix + '_quiver_t' + str(frame).zfill(4) + '.npz',
+                         {"threshold": s["threshold"], "rois": s["rois"], "gap": fs.summary.quiver.gap,
+                          "samples": pending.quiver()})
+        if fs.field_spec is not None:
+            for blk in pending.fields():
+                fields = fs.summary.export.names
+                _write_frame(prefix, [n + '_roi' + str(blk["roi"]) for n in fields], frame,
+                             [blk[n] for n in fields], pool, write_fn)
+        elif save_fields:
+            _write_frame(prefix, names, frame, pending.result(), pool, write_fn)
         print(_now() + ' - Frame ' + str(frame) + ' saved.  Duration: ' + str(datetime.now() - start))
 
-    pool = ThreadPoolExecutor(len(names))
-    writer = Writer(finish)
-    try:
-        fs.push(first)
-        pushed = h0 + 1  # next frame to upload
-        for hh in range(h0, h1):
-            start = datetime.now()
-            start_str = str(start)
-            # the window's frames, and (lookahead: frame pipelining / K0 batching) the next frames
-            upto = min(hh + NtChunk + fs.lookahead, h1 + NtChunk - 1)
-            while pushed < upto:
-                fs.push(load_frame(pushed))
-                pushed += 1
-            writer.put(hh + NtSlice, start, start_str, fs.submit())
-    finally:
-        writer.close()
-        pool.shutdown()
-        fs.close()
+    _drive(fs, load, h0, h1 - h0, NtSlice, len(names), finish)
     if summary is not None:
         from .analysis import write_summaries
 
@@ -537,45 +542,25 @@ def _process_slab(load_part, axis, vol, nOut, NtChunk, NtSlice, xyzSig, tSig, wS
     frame's halo per output frame), and the rank writes its part of each output TIFF in place
     (tiff.write_planes / write_rows: the files end up byte-identical to single-GPU ones).
     Rank 0 prints the reference's per-frame lines once its own part is written."""
-    from concurrent.futures import ThreadPoolExecutor
-
     from .shard import zslab_bounds
-    from .stream import FlowStream, Writer
+    from .stream import FlowStream
 
-    Nz, Ny, Nx = vol
     a0, a1 = zslab_bounds(vol[axis], rank, world)
-    first = np.asarray(load_part(0, a0, a1))
-    dt = first.dtype.newbyteorder('=') if first.dtype.byteorder not in ('=', '|') else first.dtype
-    fs = FlowStream(3, vol, dt, xyzSig, tSig, wSig, precision=precision, zslab=(rank, world, None, axis))
+    first, load = _peek(lambda i: load_part(i, a0, a1), 0)
+    fs = FlowStream(3, vol, _native(first.dtype), xyzSig, tSig, wSig, precision=precision,
+                    zslab=(rank, world, None, axis))
     write = tf.write_planes if axis == 0 else tf.write_rows
 
-    def finish(frame, start, start_str, pending):
-        try:
-            out = pending.result()
-            tstr = str(frame).zfill(4)
-            for f in [pool.submit(write, prefix + '_' + n + '_t' + tstr + '.tiff', vol, a.dtype, a0, a)
-                      for n, a in zip(names, out)]:
-                f.result()
-        finally:
-            pending.release()
+    def finish(pool, frame, start, pending):
+        tstr = str(frame).zfill(4)
+        for f in [pool.submit(write, prefix + '_' + n + '_t' + tstr + '.tiff', vol, a.dtype, a0, a)
+                  for n, a in zip(names, pending.result())]:
+            f.result()
         if rank == 0:
-            print(start_str + ' - Processing frame ' + str(frame) + '...')
+            print(str(start) + ' - Processing frame ' + str(frame) + '...')
             print(_now() + ' - Frame ' + str(frame) + ' saved.  Duration: ' + str(datetime.now() - start))
 
-    pool = ThreadPoolExecutor(len(names))
-    writer = Writer(finish)
-    try:
-        fs.push(first)
-        for i in range(1, NtChunk - 1):
-            fs.push(load_part(i, a0, a1))
-        for hh in range(nOut):
-            start = datetime.now()
-            fs.push(load_part(hh + NtChunk - 1, a0, a1))
-            writer.put(hh + NtSlice, start, str(start), fs.submit())
-    finally:
-        writer.close()
-        pool.shutdown()
-        fs.close()
+    _drive(fs, load, 0, nOut, NtSlice, len(names), finish)
 
 
 def _fmt_csv(v):

@@ -20,10 +20,13 @@ from __future__ import annotations
 import queue
 import threading
 import time
+from collections import namedtuple
+from functools import partial
 
 import numpy as np
 
 from . import _lib
+from .shard import check_slab_split, halo_planes, zslab_bounds
 from .taps import make_taps, radii
 
 K0_BATCH_RADII = (3, 6, 9)  # temporal radii with a batched K0 instance (csrc/kt_grad.hip k0m_fn)
@@ -41,6 +44,135 @@ _TORCH_VIEW = {
 }
 
 
+def require_summary(summary, fields, quiver, contract, prefix, fields_name):
+    """The add-ons that ride on a summary refuse to go without one.  FlowStream and process_flow
+    share the checks; `prefix` and the name of their fields argument keep each one's messages."""
+    from .analysis import FieldSpec
+
+    if isinstance(fields, FieldSpec) and summary is None:
+        raise ValueError(f"{prefix}{fields_name}=FieldSpec needs a summary")
+    if not fields and summary is None:
+        raise ValueError(f"{prefix}{fields_name}=False needs a summary")
+    if quiver is not None and summary is None:
+        raise ValueError(f"{prefix}quiver needs a summary")
+    if contract is not None and summary is None:
+        raise ValueError(f"{prefix}contract needs a summary")
+
+
+def output_layout(ndim, precision, rel_fp64):
+    """(number of fields, velocity dtype, rel dtype) of a stream's outputs (numpy dtypes): every
+    torch dtype, byte size and rel_f64 / v_f32 flag of the outputs derives from this."""
+    if precision not in ("fp64", "fp32"):
+        raise ValueError("precision must be 'fp64' (bit-exact) or 'fp32'")
+    v_t = np.float32 if precision == "fp32" else np.float64
+    rel_t = np.float64 if precision == "fp64" and (ndim == 2 or rel_fp64) else np.float32
+    return (4 if ndim == 3 else 3), np.dtype(v_t), np.dtype(rel_t)
+
+
+class _Slab(namedtuple("_Slab", "axis n a0 a1 ai0 ai1 shape nvox nblock own0 plan_dims max_out_planes rows "
+                                "frame_z0 zo0 zo1")):
+    """The part of every frame one stream holds, as plain numbers (no device): the whole volume,
+    planes [a0, a1) of its n (axis 0) or rows [a0, a1) of the n of every plane (axis 1), with the
+    input range [ai0, ai1) along that axis that the own part's stencils reach (shard.halo_planes).
+    shape: what is pushed / returned, of nvox elements; nblock: elements of own part + halo, what
+    a ring slot holds, the own planes from own0 in it (row slabs: strided, from 0).  plan_dims,
+    max_out_planes: what the plan is created with; rows: a row slab's own rows within its plan's
+    volume (of3d_plan_set_rows), else None; frame_z0, zo0, zo1: the plan call's first frame plane
+    and output planes."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, vol_shape, ndim, zslab, rd, rw):
+        """zslab = None (whole volume) or (rank, world, group[, axis]) as FlowStream takes it."""
+        nz, ny, nx = vol_shape if ndim == 3 else (1,) + tuple(vol_shape)
+        if zslab is None:
+            return cls(0, nz, 0, nz, 0, nz, tuple(vol_shape), nz * ny * nx, nz * ny * nx, 0,
+                       (nz, ny, nx), 0, None, 0, 0, nz)
+        if ndim != 3:
+            raise ValueError("z-slabs need a 3D volume")
+        rank, world = zslab[:2]
+        axis = zslab[3] if len(zslab) > 3 else 0
+        n = (nz, ny)[axis]
+        check_slab_split(n, world)  # every rank owns planes (rows)
+        a0, a1 = zslab_bounds(n, rank, world)
+        ai0, ai1 = halo_planes(n, a0, a1, rd, rw)
+        if axis == 0:
+            plane = ny * nx
+            return cls(0, n, a0, a1, ai0, ai1, (a1 - a0, ny, nx), (a1 - a0) * plane,
+                       (ai1 - ai0) * plane, (a0 - ai0) * plane, (nz, ny, nx), a1 - a0, None, ai0, a0, a1)
+        # row slabs run the plan on the rank's rows + halo as a volume of its own
+        return cls(1, n, a0, a1, ai0, ai1, (nz, a1 - a0, nx), nz * (a1 - a0) * nx,
+                   nz * (ai1 - ai0) * nx, 0, (nz, ai1 - ai0, nx), 0, (a0 - ai0, a1 - ai0), 0, 0, nz)
+
+    def block(self, buf):
+        """A ring slot as the halo exchange takes it: (ai1 - ai0, ...) with the split axis first
+        (row slabs: a strided view); None for an empty block."""
+        if not self.nblock:
+            return None
+        nz, ny, nx = self.plan_dims
+        if self.axis == 0:
+            return buf[:self.nblock].reshape(self.ai1 - self.ai0, ny, nx)
+        return buf[:self.nblock].reshape(nz, ny, nx).swapaxes(0, 1)
+
+    def own(self, buf):
+        """The own part, of `shape`, of a ring slot or of an output buffer of a whole block."""
+        if self.rows is None:
+            return buf[self.own0:self.own0 + self.nvox].reshape(self.shape)
+        return buf[:self.nblock].reshape(self.plan_dims)[:, self.rows[0]:self.rows[1]]
+
+
+class _Buf(namedtuple("_Buf", "name pinned count elems dtypes")):
+    """One row of a stream's buffer table: `count` allocations, each one tensor of `elems`
+    elements per dtype, on the device or in pinned host memory."""
+    __slots__ = ()
+    nbytes = property(lambda self: self.count * self.elems * sum(d.itemsize for d in self.dtypes))
+
+
+def buffer_table(slab, nwin, in_dtype, layout, depth, L, fields=True, export_bytes=0, dfull=False):
+    """Every buffer of a stream with `depth` output sets and L frames of lookahead, as _Buf rows;
+    FlowStream allocates from it what _fit_device_memory counted.  fields: full-size pinned
+    sets; export_bytes: one export block (device and pinned) per set; dfull: a row-slab plan
+    without row ranges writes a whole block's outputs here first."""
+    nout, v_t, rel_t = layout
+    outs = (v_t,) * (nout - 1) + (rel_t,)
+    nv, nb = max(slab.nvox, 1), max(slab.nblock, 1)
+    # nwin + 1 (+ lookahead) slots: a new frame's upload (and halo exchange) goes to the slot
+    # the frame before last read, so it overlaps the previous frame's compute
+    rows = [_Buf("ring", False, nwin + 1 + L, nb, (in_dtype,)),
+            _Buf("stage", True, 2, nv, (in_dtype,)),
+            _Buf("dout", False, depth, nv, outs)]
+    if slab.rows is not None:  # strided own part: the upload lands here, a device copy spreads it
+        rows.append(_Buf("dstage", False, 1, nv, (in_dtype,)))
+    if fields:
+        rows.append(_Buf("hout", True, depth, nv, outs))
+    if export_bytes:
+        rows += [_Buf(name, pin, depth, export_bytes // 8, (np.dtype(np.int64),))
+                 for name, pin in (("export", False), ("hexport", True))]
+    if dfull:
+        rows.append(_Buf("dfull", False, 1, nb, outs))
+    return rows
+
+
+def device_bytes(rows):
+    return sum(b.nbytes for b in rows if not b.pinned)
+
+
+def _fit_device_memory(table, depth, batch, L, free, device=0):
+    """(depth, batch, L) that fit `free` bytes of device memory beside the plan's workspace
+    (already allocated), table(depth, L) being the buffers: fewer output sets first, then K0
+    batching M -> 2 -> none (frame pipelining: -> none); raises only when even one set and no
+    lookahead do not fit."""
+    need = lambda d, lk: device_bytes(table(d, lk))
+    while depth > 1 and need(depth, L) > free:
+        depth -= 1
+    while L and need(depth, L) > free:
+        batch, L = (2, 1) if batch > 2 else (0, 0)
+    if need(depth, L) > free:
+        raise MemoryError(f"FlowStream: {need(depth, L) / 2**30:.1f} GiB of frames and outputs do not fit "
+                          f"the {free / 2**30:.1f} GiB left on device {device}")
+    return depth, batch, L
+
+
 class FlowStream:
     """Device-resident sliding window over a frame sequence.
 
@@ -48,78 +180,44 @@ class FlowStream:
     resident, submit() computes the flow of the window's centre frame (the oldest
     2*rt+1 resident frames; the oldest is then retired) and returns a Pending whose
     .result() gives host arrays (vx, vy, [vz,] rel); .release() hands the buffer set
-    back (at most `depth` frames in flight).  With lookahead, push one frame more than
-    the window before submit() to pipeline the next window's temporal derivative.
+    back (at most `depth` frames in flight).  With lookahead, push `lookahead` frames more
+    than the window BEFORE submit() (fewer at a series' end): they pipeline the next windows'
+    temporal derivative.  windows(load, first, count) does all of that for a series:
+
+        with FlowStream(3, shape, dtype, xyzSig, tSig, wSig) as fs:
+            for k, p in fs.windows(load, 0, n_frames - fs.nwin + 1):
+                vx, vy, vz, rel = p.result()  # window k: frames k .. k + nwin - 1
+                p.release()
+
+    k0_batch=M (2..5; default 5 for whole-volume 3D streams unless `lookahead` is given): M-1
+    frames of lookahead, one K0 pass forms the temporal derivatives of M consecutive windows.
+    lookahead=True (with k0_batch unset or < 2): frame pipelining instead, one frame of
+    lookahead.  Bit-identical either way.
+    zslab=(rank, world, group[, axis]): this process holds one slab of every frame (3D only) —
+    axis 0 (default): planes shard.zslab_bounds(nz, rank, world); axis 1: those rows of every
+    plane.  push() takes the rank's own part and fetches the halo from its neighbours
+    (torch.distributed P2P) on the upload stream; results are the rank's part (no gather).
     summary=SummarySpec: the frame is also reduced on the device (.summary() gives
     analysis.flow_summary's dict); fields=False: only that, no field downloads;
-    fields=FieldSpec: the fields cropped to ROIs, masked and scaled on the device (.fields())."""
+    fields=FieldSpec: the fields cropped to ROIs, masked and scaled on the device (.fields());
+    quiver=QuiverSpec, contract=ContractSpec: .quiver(), .contract().  Whole-volume streams
+    only; each add-on is described in DESIGN.md §8a–§8o, the driver itself in §8p."""
 
     def __init__(self, ndim, vol_shape, dtype, xyzSig, tSig, wSig, device=None, depth=3, d2h="dma",
                  d2h_blocks=64, precision="fp64", rel_fp64=False, zslab=None, lookahead=None, k0_batch=None,
                  summary=None, fields=True, quiver=None, contract=None):
-        """summary=analysis.SummarySpec: submit() enqueues the percentile select and the summary
-        kernels (csrc/kt_summary.hip) on the compute stream right after the plan's kernels, on the
-        device outputs of that buffer set, and the copy of the few-kilobyte result to a pinned
-        slot of the set; Pending.summary() returns analysis.flow_summary's dict.  fields=False
-        (needs a summary): the fields are never downloaded, their pinned host buffers are not
-        allocated and Pending.result() raises.  Whole-volume streams only (no zslab).  A spec
-        with min_size >= 1 adds the mask opening (csrc/kt_ccl.hip) between the select and the
-        summary; its keep volume, labels and sizes are allocated once here, and its counts ride
-        in the same result words.  quiver=analysis.QuiverSpec (needs a summary): the quiver
-        vectors of every ROI (csrc/kt_quiver.hip) follow the summary's kernels, with its threshold
-        and opened mask, into a device block and a pinned host block of their own per buffer set;
-        Pending.quiver() returns analysis.quiver_sample's per-ROI list.  contract=
-        analysis.ContractSpec (needs a summary): the contractility kernels (csrc/kt_contract.hip;
-        with mask="largest" csrc/kt_ccl.hip's labelling and selection first) follow those, again
-        into a device block and a pinned host block of their own per buffer set, copied after the
-        summary words; Pending.contract() returns analysis.contractility's dict.  The quiver keeps
-        the summary's mask whatever the contract's.  fields=analysis.FieldSpec (needs a summary):
-        instead of the full-size fields, their crops to the spec's ROIs — masked with the summary's
-        threshold and opened mask, scaled, optionally narrowed (csrc/kt_export.hip) — are formed
-        behind the summary's kernels on the compute stream, in one device block per buffer set,
-        and downloaded by the d2h path the full-size fields would take into one pinned block of
-        the same size; no full-size pinned buffer is allocated, Pending.fields() returns
-        analysis.export_fields' `blocks` and Pending.result() raises.
-
-        zslab=(rank, world, group[, axis]): this process holds one slab of every frame (3D
-        only) — axis 0 (default): output planes shard.zslab_bounds(nz, rank, world); axis 1:
-        rows zslab_bounds(ny, rank, world) of every plane.  push() then takes the rank's own
-        part ((z1 - z0, ny, nx) or (nz, y1 - y0, nx)) and fetches the frame's rd + rw halo
-        planes / rows from its neighbours (torch.distributed P2P: RCCL over xGMI, or gloo) on
-        the upload stream — one frame's halo per output frame, overlapped with the previous
-        frame's compute; results are the rank's part of vx, vy, vz, rel (no gather).
-        Row slabs run the plan on the rank's rows + halo as a volume of its own (the y pass is
-        the first pass of both filter chains, so rows further than rd + rw from a cut are
-        exact: bit-identical), and keep the own rows.
-
-        k0_batch=M (2..5; default 5 for whole-volume 3D streams unless `lookahead` is given):
-        M-1 frames of lookahead resident before submit (push them BEFORE submitting the current
-        window), and one K0 pass forms the temporal derivatives of M consecutive windows
-        (of3d_plan_execute_ahead: 2rt+M frame reads for M windows); the ring then has 2*rt+1+M
-        slots.  lookahead=True (with k0_batch unset or < 2): frame pipelining instead — one more
-        frame resident, and the current window's W-z/solve kernel forms the next window's
-        temporal derivative (of3d_plan_execute_next); 2*rt+3 slots.  Bit-identical either way."""
         import torch
-
-        from .shard import check_slab_split, halo_planes, zslab_bounds
 
         from .analysis import FieldSpec
 
+        # validate (no device call before the last of these)
         self.torch = torch
         self.ndim = ndim
         self.field_spec = fields if isinstance(fields, FieldSpec) else None
-        fields = fields if self.field_spec is None else False  # no full-size downloads
         if summary is not None and zslab is not None:
             raise ValueError("FlowStream: summaries of slab streams are not supported (whole volumes only)")
-        if self.field_spec is not None and summary is None:
-            raise ValueError("FlowStream: fields=FieldSpec needs a summary")
-        if not fields and summary is None:
-            raise ValueError("FlowStream: fields=False needs a summary")
-        if quiver is not None and summary is None:
-            raise ValueError("FlowStream: quiver needs a summary")
-        if contract is not None and summary is None:
-            raise ValueError("FlowStream: contract needs a summary")
-        self.fields = bool(fields)
+        require_summary(summary, fields, quiver, contract, "FlowStream: ", "fields")
+        self.fields = bool(fields) and self.field_spec is None  # full-size downloads
         self.device = _lib.device_index() if device is None else device
         self.dev = torch.device("cuda", self.device)
         dt = np.dtype(dtype)
@@ -127,12 +225,6 @@ class FlowStream:
             dt = np.dtype(np.float64)
         self.np_dtype = dt
         self.code = _lib.DTYPE_CODES[dt]
-        tdt = getattr(torch, _TORCH_VIEW[dt])
-        if ndim == 3:
-            nz, ny, nx = vol_shape
-        else:
-            (ny, nx), nz = vol_shape, 1
-        self.nz, self.ny, self.nx = nz, ny, nx
         self.rd, self.rs, self.rt, self.rw = radii(xyzSig, tSig, wSig)
         self.nwin = 2 * self.rt + 1
         self.batch = 0
@@ -149,69 +241,51 @@ class FlowStream:
         if lookahead is None:
             lookahead = ndim == 3 and zslab is None
         self.L = self.batch - 1 if self.batch else (1 if lookahead else 0)
-        if zslab is not None and ndim != 3:
-            raise ValueError("z-slabs need a 3D volume")
+        # geometry
         self.rank, self.world, self.group = zslab[:3] if zslab is not None else (0, 1, None)
-        self.axis = zslab[3] if zslab is not None and len(zslab) > 3 else 0
-        if zslab is not None:
-            check_slab_split((nz, ny)[self.axis], self.world)  # every rank owns planes (rows)
-        plane = ny * nx
-        taps = make_taps(xyzSig, tSig, wSig)
-        if precision not in ("fp64", "fp32"):
-            raise ValueError("precision must be 'fp64' (bit-exact) or 'fp32'")
-        self.precision = precision
-        mode = (_lib.OF3D_FP32 if precision == "fp32" else 0) | (_lib.OF3D_REL_F64 if rel_fp64 else 0)
-        self.plan = None
-        self.z0, self.z1, self.zi0, self.zi1 = 0, nz, 0, nz
-        self.y0, self.y1, self.yi0, self.yi1 = 0, ny, 0, ny
-        self.rows_direct = False
-        if self.axis == 0:
-            self.z0, self.z1 = zslab_bounds(nz, self.rank, self.world)
-            if zslab is not None:
-                self.zi0, self.zi1 = halo_planes(nz, self.z0, self.z1, self.rd, self.rw)
-            self.shape = tuple(vol_shape) if zslab is None else (self.z1 - self.z0, ny, nx)  # pushed / returned
-            self.nvox = (self.z1 - self.z0) * plane
-            self.nblock = (self.zi1 - self.zi0) * plane
-            self.own0 = (self.z0 - self.zi0) * plane  # own planes' offset in a ring slot
-            if self.nvox > 0:
-                self.plan = _lib.Plan(ndim, nz, ny, nx, taps, device=self.device, mode=mode,
-                                      max_out_planes=self.z1 - self.z0 if zslab is not None else 0)
-                if zslab is not None:
-                    assert self.plan.input_range(self.z0, self.z1) == (self.zi0, self.zi1)
-        else:
-            self.y0, self.y1 = zslab_bounds(ny, self.rank, self.world)
-            self.yi0, self.yi1 = halo_planes(ny, self.y0, self.y1, self.rd, self.rw)
-            self.shape = (nz, self.y1 - self.y0, nx)
-            self.nvox = nz * (self.y1 - self.y0) * nx
-            self.nblock = nz * (self.yi1 - self.yi0) * nx
-            self.own0 = 0
-            self.rows_direct = False  # the plan writes only the own rows (of3d_plan_set_rows)
-            if self.nvox > 0:
-                self.plan = _lib.Plan(3, nz, self.yi1 - self.yi0, nx, taps, device=self.device, mode=mode)
-                try:
-                    self.plan.set_rows(self.y0 - self.yi0, self.y1 - self.yi0)
+        self.slab = slab = _Slab.of(vol_shape, ndim, zslab, self.rd, self.rw)
+        self.shape, self.nvox = slab.shape, slab.nvox
+        layout = output_layout(ndim, precision, rel_fp64)
+        v_f32, rel_f64 = layout[1].itemsize == 4, layout[2].itemsize == 8
+        if d2h not in ("dma", "kernel", "runtime"):
+            raise ValueError("d2h must be 'dma', 'kernel' or 'runtime'")
+        # plan
+        self.plan, self.rows_direct = None, False
+        if slab.nvox > 0:
+            mode = (_lib.OF3D_FP32 if v_f32 else 0) | (_lib.OF3D_REL_F64 if rel_fp64 else 0)
+            self.plan = _lib.Plan(ndim, *slab.plan_dims, make_taps(xyzSig, tSig, wSig), device=self.device, mode=mode,
+                                  max_out_planes=slab.max_out_planes)
+            if slab.max_out_planes:
+                assert self.plan.input_range(slab.a0, slab.a1) == (slab.ai0, slab.ai1)
+            if slab.rows is not None:
+                try:  # the plan writes only the own rows (of3d_plan_set_rows)
+                    self.plan.set_rows(*slab.rows)
                     self.rows_direct = True
                 except RuntimeError:  # kernels without row ranges: whole sub-volume, then a slice
                     pass
+        # buffer table (after the plan: rows_direct decides dfull), and what of it fits the device
         export_bytes = 0
         if self.field_spec is not None:  # sized ahead of the buffers: _SummaryCall allocates on the device
             from .analysis import _ExportCall
 
-            export_bytes = _ExportCall.size(summary.resolve(self.shape)[0],
-                                            precision == "fp64" and (ndim == 2 or rel_fp64), precision == "fp32",
-                                            self.field_spec, ndim)[1]
-        depth = self._fit_device_memory(depth, tdt, ndim, precision, rel_fp64, export_bytes=export_bytes)
-        # nwin + 1 (+ lookahead) slots: a new frame's upload (and halo exchange) goes to the slot
-        # the frame before last read, so it overlaps the previous frame's compute
-        nslot = self.nwin + 1 + self.L
-        self.ring = torch.empty((nslot, max(self.nblock, 1)), dtype=tdt, device=self.dev)
+            export_bytes = _ExportCall.size(summary.resolve(self.shape)[0], rel_f64, v_f32, self.field_spec, ndim)[1]
+        table = partial(buffer_table, slab, self.nwin, dt, layout, fields=self.fields, export_bytes=export_bytes,
+                        dfull=slab.rows is not None and not self.rows_direct)
+        free = torch.cuda.mem_get_info(self.dev)[0] - (1 << 30)  # a margin for the runtime and the summary
+        self.depth, self.batch, self.L = _fit_device_memory(table, depth, self.batch, self.L, free, self.device)
+        # allocate
+        bufs = {b.name: self._alloc(b) for b in table(self.depth, self.L)}
+        self.ring = bufs["ring"]  # one allocation: the slots are its rows
         self.order = []  # ring slots of the resident frames, oldest first
-        self.free = list(range(nslot))
-        self.dstage = torch.empty(max(self.nvox, 1), dtype=tdt, device=self.dev) if self.axis == 1 else None
-        self.stage = [torch.empty(max(self.nvox, 1), dtype=tdt).pin_memory() for _ in range(2)]
+        self.free = list(range(len(self.ring)))
+        self.dstage = bufs["dstage"][0][0] if "dstage" in bufs else None
+        self.stage = [s[0] for s in bufs["stage"]]
         self.stage_np = [t.numpy().view(dt)[:self.nvox].reshape(self.shape) for t in self.stage]
         self.stage_evt = [None, None]
         self.stage_i = 0
+        self.dout = bufs["dout"]
+        self.hout = bufs.get("hout", [None] * self.depth)
+        self.dfull = bufs["dfull"][0] if "dfull" in bufs else None
         # Downloads (d2h):
         #   "dma"     of3d_dma_copy on the SDMA engines from a download thread
         #             once the frame's kernels are done: no CU time, and the
@@ -222,9 +296,8 @@ class FlowStream:
         #             over the whole GPU.
         # Kernel-driven PCIe writes (the last two) back up the memory pipeline
         # shared with the compute kernels and slow them several-fold.
-        if d2h not in ("dma", "kernel", "runtime"):
-            raise ValueError("d2h must be 'dma', 'kernel' or 'runtime'")
         self.d2h_mode = d2h
+        self.d2h_blocks = d2h_blocks
         self.h2d = torch.cuda.Stream(device=self.dev)
         self.comp = torch.cuda.Stream(device=self.dev)
         self.d2h = torch.cuda.Stream(device=self.dev, priority=-1)
@@ -235,73 +308,48 @@ class FlowStream:
             self.dl_q = queue.Queue()
             self.dl_thread = threading.Thread(target=self._download_loop, daemon=True)
             self.dl_thread.start()
-        nout = 4 if ndim == 3 else 3
-        v_t = torch.float32 if precision == "fp32" else torch.float64
-        if precision == "fp32":
-            rel_t = torch.float32
-        else:
-            rel_t = torch.float64 if (ndim == 2 or rel_fp64) else torch.float32
-        self.depth = depth
-        self.d2h_blocks = d2h_blocks
-        nv = max(self.nvox, 1)
-        mk = lambda pin, n=nv: [torch.empty(n, dtype=v_t, device=None if pin else self.dev,
-                                            pin_memory=pin) for _ in range(nout - 1)] + \
-                               [torch.empty(n, dtype=rel_t, device=None if pin else self.dev, pin_memory=pin)]
-        self.dout = [mk(False) for _ in range(depth)]
-        self.hout = [mk(True) if self.fields else None for _ in range(depth)]
+        self.precision, self.v_f32 = precision, v_f32
         self.summary, self.addon = None, {}
         if summary is not None:
             from .analysis import _SummaryCall
 
-            self.summary = _SummaryCall(summary, self.shape, rel_t, self.dev, quiver=quiver, contract=contract,
-                                        export=self.field_spec, v_f32=precision == "fp32")
-            self.dsum = [self.summary.new_result(self.dev) for _ in range(depth)]
+            self.summary = _SummaryCall(summary, self.shape, getattr(torch, layout[2].name), self.dev, quiver=quiver,
+                                        contract=contract, export=self.field_spec, v_f32=v_f32)
+            self.dsum = [self.summary.new_result(self.dev) for _ in range(self.depth)]
             self.hsum = [torch.empty(self.summary.result_bytes // 8, dtype=torch.int64, pin_memory=True)
-                         for _ in range(depth)]
+                         for _ in range(self.depth)]
             # the add-ons' own blocks per buffer set, name -> (device, pinned): copied behind the
-            # summary's words on the compute stream — but for "export", whose block travels on the
-            # fields' download path in their place (submit)
+            # summary's words on the compute stream — but for "export", whose block (the table's)
+            # travels on the fields' download path in their place (submit)
             self.addon = {name: [(call.new_result(self.dev),
                                   torch.empty(call.result_bytes // 8, dtype=torch.int64, pin_memory=True))
-                                 for _ in range(depth)] for name, call, _ in self.summary.addons}
+                                 for _ in range(self.depth)]
+                          for name, call, _ in self.summary.addons if name != "export"}
             if self.field_spec is not None:
                 assert self.summary.export.result_bytes == export_bytes
-        # row slabs without row ranges: the plan writes all rows of its sub-volume here; the own
-        # rows are copied out
-        self.dfull = mk(False, max(self.nblock, 1)) if self.axis == 1 and not self.rows_direct else None
-        self.host_free = [threading.Event() for _ in range(depth)]  # set: writer released the set
+                self.addon["export"] = [(d[0], h[0]) for d, h in zip(bufs["export"], bufs["hexport"])]
+                assert all(d.data_ptr() % 16 == 0 for d, _ in self.addon["export"])  # as of3d_field_export asks
+        self.host_free = [threading.Event() for _ in range(self.depth)]  # set: writer released the set
         for e in self.host_free:
             e.set()
         self.slot_evt = {}               # ring slot -> event of the last compute that read it
         self.k = 0
 
-    def _fit_device_memory(self, depth, tdt, ndim, precision, rel_fp64, margin=1 << 30, export_bytes=0):
-        """Output sets in flight (each with its export block of export_bytes, if any) and frames of
-        lookahead that fit the device beside the plan's workspace (already allocated): fewer output sets first, then K0 batching M -> 2 -> none
-        (frame pipelining: -> none); raises only when even one set and no lookahead do not fit.
-        Returns the depth; self.batch / self.L are updated."""
+    def _alloc(self, b):
+        """The tensors of one buffer-table row: per allocation one tensor per dtype; the ring is
+        one (slots, elements) tensor."""
         torch = self.torch
-        free = torch.cuda.mem_get_info(self.dev)[0] - margin
-        nout = 4 if ndim == 3 else 3
-        v_sz = 4 if precision == "fp32" else 8
-        rel_sz = 4 if precision == "fp32" else (8 if (ndim == 2 or rel_fp64) else 4)
-        set_b = max(self.nvox, 1) * ((nout - 1) * v_sz + rel_sz) + export_bytes
-        slot_b = max(self.nblock, 1) * torch.empty((), dtype=tdt).element_size()
-        fixed = slot_b * (self.nwin + 1) + (max(self.nvox, 1) * slot_b // max(self.nblock, 1) if self.axis == 1 else 0)
-        if self.axis == 1:  # row slabs without row ranges write a whole sub-volume set first
-            fixed += max(self.nblock, 1) * ((nout - 1) * v_sz + rel_sz)
-        need = lambda d, lk: fixed + lk * slot_b + d * set_b
-        while depth > 1 and need(depth, self.L) > free:
-            depth -= 1
-        while self.L and need(depth, self.L) > free:
-            if self.batch > 2:
-                self.batch, self.L = 2, 1
-            else:
-                self.batch, self.L = 0, 0
-        if need(depth, self.L) > free:
-            raise MemoryError(f"FlowStream: {need(depth, self.L) / 2**30:.1f} GiB of frames and outputs do not fit "
-                              f"the {free / 2**30:.1f} GiB left on device {self.device}")
-        return depth
+        new = lambda shape, d: torch.empty(shape, dtype=getattr(torch, _TORCH_VIEW.get(d, d.name)),
+                                           device=None if b.pinned else self.dev, pin_memory=b.pinned)
+        if b.name == "ring":
+            return new((b.count, b.elems), b.dtypes[0])
+        return [[new(b.elems, d) for d in b.dtypes] for _ in range(b.count)]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def push(self, frame):
         torch = self.torch
@@ -319,12 +367,11 @@ class FlowStream:
         with torch.cuda.stream(self.h2d):
             if slot in self.slot_evt:
                 self.h2d.wait_event(self.slot_evt[slot])  # no compute still reads this slot
-            if self.nvox and self.axis == 0:
-                self.ring[slot, self.own0:self.own0 + self.nvox].copy_(st[:self.nvox], non_blocking=True)
+            if self.nvox and self.dstage is None:
+                self.slab.own(self.ring[slot]).copy_(st[:self.nvox].view(self.shape), non_blocking=True)
             elif self.nvox:
                 self.dstage.copy_(st, non_blocking=True)
-                self._rows(self.ring[slot])[:, self.y0 - self.yi0:self.y1 - self.yi0].copy_(
-                    self.dstage[:self.nvox].view(self.shape))
+                self.slab.own(self.ring[slot]).copy_(self.dstage[:self.nvox].view(self.shape))
             if self.world > 1:  # this frame's halo planes from / to the z-neighbours
                 self.exchange(slot)
             ev = torch.cuda.Event()
@@ -333,24 +380,14 @@ class FlowStream:
         self.stage_i ^= 1
         self.order.append(slot)
 
-    def _rows(self, flat):
-        """A ring slot / output buffer of a row-slab stream as (nz, yi1 - yi0, nx)."""
-        return flat[:self.nblock].view(self.nz, self.yi1 - self.yi0, self.nx)
-
     def exchange(self, slot):
         """Halo planes (rows) of the frame in ring slot `slot` (slab streams): issued on the
         current stream (the upload stream in push); every rank calls it for the same frame."""
         from .shard import exchange_frame_halo
 
-        if not self.nblock:
-            blk = None
-        elif self.axis == 0:
-            blk = self.ring[slot, :self.nblock].view(self.zi1 - self.zi0, self.ny, self.nx)
-        else:
-            blk = self._rows(self.ring[slot]).transpose(0, 1)  # rows first (strided)
-        lo, hi, i0, n = ((self.z0, self.z1, self.zi0, self.nz) if self.axis == 0 else
-                         (self.y0, self.y1, self.yi0, self.ny))
-        exchange_frame_halo(blk, i0, lo, hi, n, self.rd + self.rw, self.rank, self.world, self.group)
+        g = self.slab
+        exchange_frame_halo(g.block(self.ring[slot]), g.ai0, g.a0, g.a1, g.n, self.rd + self.rw, self.rank,
+                            self.world, self.group)
 
     @property
     def ready(self):
@@ -361,6 +398,20 @@ class FlowStream:
         """Frames past the window to push before submit (frame pipelining: 1; K0 batching: M-1)."""
         return self.L
 
+    def windows(self, load, first, count):
+        """The push-ahead protocol for the windows first .. first + count - 1 of a series (window
+        k: frames k .. k + nwin - 1): generates (k, Pending).  load(i) is called once per frame
+        those windows need, in increasing order, each frame resident `lookahead` submits early
+        (fewer at the series' end).  The ring must be empty (RuntimeError once iterated)."""
+        if self.order:
+            raise RuntimeError("FlowStream.windows: the ring already holds frames")
+        pushed, end = first, first + count + self.nwin - 1  # next frame to upload, one past the last
+        for k in range(first, first + count):
+            while pushed < min(k + self.nwin + self.L, end):
+                self.push(load(pushed))
+                pushed += 1
+            yield k, self.submit()
+
     def submit(self):
         torch = self.torch
         assert self.ready
@@ -370,35 +421,35 @@ class FlowStream:
         self.host_free[b].clear()  # which also means its D2H (and so its compute) finished
         dout, hout = self.dout[b], self.hout[b]
         self.comp.wait_stream(self.h2d)
-        window = self.order[:self.nwin]
-        ptrs = [self.ring[s].data_ptr() for s in window]
-        # lookahead: the next window (one frame on) is resident too -> its dt0 formed in this call
-        nxt = [self.ring[s].data_ptr() for s in self.order[1:self.nwin + 1]] \
-            if self.L and not self.batch and len(self.order) == self.nwin + 1 else None
-        # K0 batching: the resident frames past the window (up to M-1; fewer at a series' end)
-        ahead = [self.ring[s].data_ptr() for s in self.order[self.nwin:self.nwin + self.L]] if self.batch else None
+        g = self.slab
+        ptrs = [self.ring[s].data_ptr() for s in self.order[:self.nwin]]
+        look = {}
+        if g.rows is None:  # a row slab's plan sees a volume of its own: no lookahead through it
+            # frame pipelining: the next window (one frame on) is resident too -> its dt0 formed in
+            # this call; K0 batching: the resident frames past the window (up to M-1; fewer at a
+            # series' end)
+            nxt = [self.ring[s].data_ptr() for s in self.order[1:self.nwin + 1]] \
+                if self.L and not self.batch and len(self.order) == self.nwin + 1 else None
+            ahead = [self.ring[s].data_ptr() for s in self.order[self.nwin:self.nwin + self.L]] if self.batch else None
+            look = dict(next_ptrs=nxt, pipelined=bool(self.L) and not self.batch, ahead_ptrs=ahead)
         vz = dout[2].data_ptr() if self.ndim == 3 else 0
-        if self.plan is not None and self.axis == 0:
-            self.plan.execute(ptrs, self.code, self.zi0, self.z0, self.z1 if self.ndim == 3 else 1,
-                              dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(), self.comp.cuda_stream,
-                              next_ptrs=nxt, pipelined=bool(self.L) and not self.batch, ahead_ptrs=ahead)
-        elif self.plan is not None and self.rows_direct:  # row slab: the plan writes the own rows
-            self.plan.execute(ptrs, self.code, 0, 0, self.nz, dout[0].data_ptr(), dout[1].data_ptr(),
-                              dout[2].data_ptr(), dout[-1].data_ptr(), self.comp.cuda_stream)
-        elif self.plan is not None:  # row slab: whole sub-volume, then the own rows
-            full = self.dfull
-            self.plan.execute(ptrs, self.code, 0, 0, self.nz, full[0].data_ptr(), full[1].data_ptr(),
-                              full[2].data_ptr(), full[3].data_ptr(), self.comp.cuda_stream)
-            with torch.cuda.stream(self.comp):
-                for d, f in zip(dout, full):
-                    d[:self.nvox].view(self.shape).copy_(self._rows(f)[:, self.y0 - self.yi0:self.y1 - self.yi0])
+        if self.plan is not None:
+            # row slabs without row ranges: the plan writes all rows of its sub-volume to dfull,
+            # the own rows are copied out
+            to = [t.data_ptr() for t in (self.dfull or dout)]
+            self.plan.execute(ptrs, self.code, g.frame_z0, g.zo0, g.zo1, to[0], to[1], to[2] if self.ndim == 3 else 0,
+                              to[-1], self.comp.cuda_stream, **look)
+            if self.dfull is not None:
+                with torch.cuda.stream(self.comp):
+                    for d, f in zip(dout, self.dfull):
+                        d[:self.nvox].view(self.shape).copy_(g.own(f))
         pending = Pending(self, b)
         if self.summary is not None:
             # on the compute stream: behind this frame's kernels and ahead of every later frame's,
             # so a later submit() that reuses this set's device outputs (after its release()) is
             # ordered behind these reads by the stream itself
-            self.summary.enqueue((dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(),
-                                  self.precision == "fp32"), self.dsum[b].data_ptr(), self.comp.cuda_stream,
+            self.summary.enqueue((dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(), self.v_f32),
+                                 self.dsum[b].data_ptr(), self.comp.cuda_stream,
                                  blocks={name: sets[b][0].data_ptr() for name, sets in self.addon.items()})
             with torch.cuda.stream(self.comp):
                 self.hsum[b].copy_(self.dsum[b], non_blocking=True)

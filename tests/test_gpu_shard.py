@@ -36,7 +36,8 @@ def stream_slab_worker(rank, world, port, q, img, sig, axis, precision="fp64"):
     """One rank of a slab split on the product path: FlowStream(zslab=(rank, world, group,
     axis)) holds only the rank's planes (axis 0) or rows (axis 1) of every frame, fetches the
     halo with shard.exchange_frame_halo (gloo here, all ranks on the one GPU; RCCL on a
-    node), and returns the rank's part of vx, vy, vz, rel."""
+    node), and returns the rank's part of vx, vy, vz, rel, and whether its plan writes the own
+    rows itself (of3d_plan_set_rows accepted)."""
     import os
 
     import torch.distributed as dist
@@ -60,15 +61,17 @@ def stream_slab_worker(rank, world, port, q, img, sig, axis, precision="fp64"):
             pend = fs.submit()
             outs = [o.copy() for o in pend.result()]
             pend.release()
+            rows_direct = fs.rows_direct
         finally:
             fs.close()
-        q.put((rank, a0, a1, outs))
+        q.put((rank, a0, a1, outs, rows_direct))
     finally:
         dist.destroy_process_group()
 
 
-def run_stream_slabs(world, img, sig, axis, precision="fp64"):
-    """stream_slab_worker on `world` spawned processes; [(rank, a0, a1, outs)] by rank."""
+def run_stream_slabs(world, img, sig, axis, precision="fp64", report_rows=False):
+    """stream_slab_worker on `world` spawned processes; [(rank, a0, a1, outs)] by rank
+    (report_rows: [(rank, a0, a1, outs, rows_direct)])."""
     import multiprocessing as mp
     import socket
 
@@ -85,7 +88,7 @@ def run_stream_slabs(world, img, sig, axis, precision="fp64"):
     res = sorted(q.get(timeout=180) for _ in range(world))
     for p in procs:
         p.join(timeout=60)
-    return res
+    return res if report_rows else [r[:4] for r in res]
 
 
 @pytest.mark.parametrize("world,axis", [(2, 0), (3, 0), (2, 1), (3, 1)])
@@ -102,6 +105,27 @@ def test_slab_ranks_with_halo_exchange(world, axis):
             want = a[a0:a1] if axis == 0 else a[:, a0:a1]
             assert bits_equal(want, b.reshape(want.shape)), (rank, axis)
     assert covered == (30, 20)[axis]
+
+
+@pytest.mark.parametrize("world,env,precision", [(2, {"OF3D_K5C": "0"}, "fp64"), (3, {"OF3D_K5C": "0"}, "fp64"),
+                                                 (2, {"OF3D_K34": "0"}, "fp64"), (2, {"OF3D_K5C": "0"}, "fp32")])
+def test_row_slab_ranks_without_row_ranges(world, env, precision, monkeypatch):
+    """Row slabs whose plan cannot write row ranges (kernels other than the fused W ones refuse
+    of3d_plan_set_rows): the plan writes its whole sub-volume and the stream copies the own rows
+    out.  Each rank's rows equal the unsharded stream's bit for bit."""
+    from opticalflow3d_dev_amd import calc_flow3D_fp32
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)  # inherited by the spawned ranks
+    img = np.random.default_rng(7).integers(0, 4096, size=(13, 30, 20, 24)).astype(np.uint16)
+    full = calc_flow3D(img, 2, 2, 5) if precision == "fp64" else calc_flow3D_fp32(img, 2, 2, 5)
+    covered = 0
+    for rank, a0, a1, outs, rows_direct in run_stream_slabs(world, img, (2, 2, 5), 1, precision, report_rows=True):
+        assert rows_direct is False, (rank, env)
+        covered += a1 - a0
+        for a, b in zip(full, outs):
+            assert a.dtype == b.dtype and bits_equal(a[:, a0:a1], b.reshape(a[:, a0:a1].shape)), (rank, env)
+    assert covered == 20
 
 
 @pytest.mark.parametrize("rows", [(0, 60), (7, 41), (0, 1), (59, 60), (13, 14)])
