@@ -668,6 +668,70 @@ int of3d_field_export(const void* d_vx, const void* d_vy, const void* d_vz, cons
                       int mask_mode, int physical, int out_f32, const uint16_t* d_keep /* NULL: rel > *d_thresh */,
                       void* d_result, void* stream);
 
+/* Projection maps: per box of the frame summary and per axis a (z, y or x) one value per line of
+ * the box — the box's voxels that share the other two coordinates, taken in ascending order along
+ * a — so that a summary-only series can still return the picture every figure script draws its
+ * vectors on (max(myo,[],3) in plot_figure3_ROIfigures.m:298,313, plot_figure3_ChannelCompare.m:64,69
+ * and plot_figure5.m:915-917; sum(relMask,3) in plot_figure4_timeTraces.m:103, plot_figure5.m:90 and
+ * plot_figure5_Movie.m:91) and a 3D flow as a 2D vector map.  Fields, d_rel, dtypes, dims, d_thresh,
+ * scales and rois as of3d_flow_summary's; d_keep as of3d_quiver_sample's (NULL: the mask factor is
+ * rel > *d_thresh, else bit r of d_keep for box r; d_rel and d_thresh may then be NULL).  2D:
+ * d_vz == NULL and nz == 1 (a d_vz with nz == 1 is an error); the axes are then y and x only.
+ * axes: bit 0 z, 1 y, 2 x, one at least.  A map's plane has the box's two remaining extents in C
+ * order: axis z (dy, dx), axis y (dz, dx), axis x (dz, dy).
+ * maps: the maps produced, one at least; bit OF3D_PROJECT_SKIP_SHIFT + r: box r is listed but not
+ * projected — it keeps its index, and so its bit of d_keep, and takes no space.  Per voxel k of a
+ * line: m_k the mask factor; the physical velocity of3d_flow_summary's (v * m, an exact zero ->
+ * NaN, (v * scale) / tscale); valid <=> the magnitude's square is not NaN; magnitude = its root.
+ *   bit 0  n_mask         int64    the k with m_k = 1 (sum(relMask,3): a voxel inside the mask whose
+ *                                  velocity is an exact zero counts here and not in n_valid)
+ *   bit 1  n_valid        int64    the valid k
+ *   bit 2..4 sum_vx, sum_vy, sum_vz  float64  s = 0.0; for k ascending: if valid: s = s + v_k
+ *                                  (sum_vz: 3D only)
+ *   bit 5  sum_magnitude  float64  the same sequential sum of the magnitudes
+ *   bit 6  max_magnitude  float64  the largest magnitude of the valid k; NaN without one
+ *   bit 7  max_image      float64  m = NaN; for every k: m = fmax(m, (double)image_k) — a float
+ *                                  image's NaNs are ignored; the sign of a zero maximum is unspecified
+ *   bit 8  sum_image      float64  s = 0.0; for every k ascending: s = s + (double)image_k (unmasked)
+ * Every sum is that loop, one fp64 addition per step and no FMA contraction: a map depends on the
+ * inputs alone, never on the launch shape.  Bits 7 and 8 need d_image: a volume of the same dims of
+ * any of3d_dtype, read by image_dtype (uint16 / uint32 frames kept in signed storage are read as
+ * the unsigned values the code names).  Without those bits d_image is not read.
+ *
+ * Result (device, of3d_flow_project_result_bytes(...) bytes, 8-byte words; d_result 16-byte aligned):
+ *   word 0        the threshold as float64 (NaN without a d_thresh)
+ *   words 1..7    n_roi, axes, maps, has_vz, the image dtype code (0 without an image map), the
+ *                 total word count, 0 (int64)
+ *   then per box, 6 words: for axis z, y, x the plane's element count and the word offset of the
+ *   first map of (box, axis) — 0: not produced (a skipped box, an axis not asked for)
+ *   then the maps, box by box, axis by axis and in bit order: each starts on a 16-byte boundary,
+ *   holds the plane's elements in C order and is padded to whole 16 bytes with zeros — the maps of
+ *   one (box, axis) are ((count + 1) & ~1) words apart.
+ * Every byte of the result is written by the call, and nothing outside it.  Up to three launches on
+ * `stream`: axes z and y in one, grid (one-wave workgroups, box, axis), one lane per line with the plane's
+ * pixels flattened in C order over the lanes (consecutive lanes read consecutive x), a lane
+ * marching its line four voxels per trip; axis x, grid (workgroups, box): a workgroup takes 32
+ * consecutive lines and walks them 32 voxels of x per step — the tile is loaded coalesced along x,
+ * the loading lane forms the voxel's physical values and parks them in LDS, and one lane per
+ * (line, accumulator) adds the parked columns in ascending x; and a one-workgroup launch for the
+ * header and the pads.  Every output word has one writer: no atomics, no workspace, no host copy,
+ * no host synchronisation, no workgroup waits for another.
+ * of3d_flow_project_result_bytes: host arithmetic only; 0 (and of3d_last_error's text) on a
+ * refusal: a null pointer, an invalid box, more than 16 boxes, no axis or map bit set (or bits
+ * beyond them and the skip bits of the boxes), every box skipped, the z axis or sum_vz without
+ * has_vz, an image map without an image_dtype, an image_dtype that is no of3d_dtype, a box that
+ * needs 2^24 workgroups or more along an axis (64 lines each for z and y, 32 for x).  of3d_flow_project refuses the same, a missing pointer, and a
+ * d_result that is not 16-byte aligned (-1). */
+#define OF3D_PROJECT_HEAD_WORDS 8
+#define OF3D_PROJECT_ROI_WORDS 6
+#define OF3D_PROJECT_SKIP_SHIFT 16
+size_t of3d_flow_project_result_bytes(const int64_t* rois, int n_roi, int axes, int maps, int has_vz, int image_dtype);
+int of3d_flow_project(const void* d_vx, const void* d_vy, const void* d_vz, const void* d_rel, int v_f32, int rel_f64,
+                      int64_t nz, int64_t ny, int64_t nx, const void* d_thresh, double xyscale, double zscale,
+                      double tscale, const int64_t* rois, int n_roi, int axes /* bit 0 z, 1 y, 2 x */, int maps,
+                      const void* d_image /* NULL: no image maps */, int image_dtype,
+                      const uint16_t* d_keep /* NULL: rel > *d_thresh */, void* d_result, void* stream);
+
 /* Contractility: the flow with respect to the centroid of the mask, on the device — the
  * reference's figure 2 / movie S2 (plot_figure2_movie.ipynb cell 1: com = center_of_mass(relMask),
  * normalc = -(pos - com) / |pos - com| in physical units, vnorm = v / |v|,

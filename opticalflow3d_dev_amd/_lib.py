@@ -53,6 +53,7 @@ EXPORTED = (
     "of3d_flow_spread", "of3d_flow_spread_workspace_bytes", "of3d_flow_spread_result_bytes",
     "of3d_rel_select", "of3d_rel_select_workspace_bytes", "of3d_rel_profile", "of3d_rel_profile_result_bytes",
     "of3d_field_export", "of3d_field_export_result_bytes",
+    "of3d_flow_project", "of3d_flow_project_result_bytes",
 )
 
 CSRC = os.path.join(_HERE, "csrc")
@@ -299,6 +300,13 @@ def load():
                                           ctypes.POINTER(i64), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, P, P, P]
         lib.of3d_field_export.restype = ctypes.c_int
+        lib.of3d_flow_project_result_bytes.argtypes = [ctypes.POINTER(i64), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int, ctypes.c_int]
+        lib.of3d_flow_project_result_bytes.restype = ctypes.c_size_t
+        lib.of3d_flow_project.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int, i64, i64, i64, P, d, d, d,
+                                          ctypes.POINTER(i64), ctypes.c_int, ctypes.c_int, ctypes.c_int, P,
+                                          ctypes.c_int, P, P, P]
+        lib.of3d_flow_project.restype = ctypes.c_int
         lib.of3d_rel3d.argtypes = [P, i64, P, ctypes.c_int, P]
         lib.of3d_rel3d.restype = ctypes.c_int
         lib.of3d_plan_poison.argtypes = [P, ctypes.c_int, P]

@@ -844,24 +844,29 @@ class FieldSpec:
     physical: bool = True
     dtype: str | None = None
 
+    @staticmethod
+    def _roi_indices(given, n_roi, what):
+        """A `rois` request (FieldSpec's, ProjectionSpec's) as validated indices into the
+        summary's n_roi boxes; `what` begins the messages."""
+        is_int = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if given is None:
+            return tuple(range(1, n_roi)) or (0,)
+        try:
+            rois = tuple(given)
+        except TypeError:
+            raise ValueError(f"{what}: rois {given!r} is not a sequence of ROI indices") from None
+        if not rois or not all(is_int(r) for r in rois):
+            raise ValueError(f"{what}: rois {given!r} is not a non-empty sequence of ROI indices")
+        if any(not 0 <= r < n_roi for r in rois):
+            raise ValueError(f"{what}: ROI index out of range in {rois} (the summary has ROIs 0..{n_roi - 1})")
+        if len(set(rois)) != len(rois):
+            raise ValueError(f"{what}: duplicate ROI index in {rois}")
+        return tuple(int(r) for r in rois)
+
     def resolve(self, ndim, n_roi):
         """Validated (rois, names, field bits, mask_mode, physical, out_f32) for an ndim-D volume
         whose summary has n_roi boxes (the whole volume included); ValueError on a bad value."""
-        is_int = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
-        if self.rois is None:
-            rois = tuple(range(1, n_roi)) or (0,)
-        else:
-            try:
-                rois = tuple(self.rois)
-            except TypeError:
-                raise ValueError(f"fields: rois {self.rois!r} is not a sequence of ROI indices") from None
-            if not rois or not all(is_int(r) for r in rois):
-                raise ValueError(f"fields: rois {self.rois!r} is not a non-empty sequence of ROI indices")
-            if any(not 0 <= r < n_roi for r in rois):
-                raise ValueError(f"fields: ROI index out of range in {rois} (the summary has ROIs 0..{n_roi - 1})")
-            if len(set(rois)) != len(rois):
-                raise ValueError(f"fields: duplicate ROI index in {rois}")
-            rois = tuple(int(r) for r in rois)
+        rois = self._roi_indices(self.rois, n_roi, "fields")
         if self.fields is EXPORT_FIELDS:
             names = tuple(n for n in EXPORT_FIELDS if ndim == 3 or n != "vz")
         else:
@@ -957,6 +962,159 @@ class _ExportCall(_BoxCall):
                 entry[name] = flat.reshape(shape if self.ndim == 3 else shape[1:])
             out.append(entry)
         return out
+
+
+PROJECT_AXES = ("z", "y", "x")  # of3d_flow_project's axis bits, in order
+PROJECT_MAPS = ("n_mask", "n_valid", "sum_vx", "sum_vy", "sum_vz", "sum_magnitude", "max_magnitude", "max_image",
+                "sum_image")  # its map bits, in order
+PROJECT_IMAGE_MAPS = PROJECT_MAPS[7:]
+_PROJECT_HEAD, _PROJECT_ROI, _PROJECT_SKIP = 8, 6, 16  # OF3D_PROJECT_HEAD_WORDS, _ROI_WORDS, _SKIP_SHIFT
+
+
+@dataclasses.dataclass
+class ProjectionSpec:
+    """Projection maps of ROIs of the summary, asked of projection_maps / FlowStream(project=) /
+    process_flow(project=): one value per line of a ROI along an axis — the picture the figure
+    scripts draw their vectors on (``max(myo,[],3)``), the mask's footprint (``sum(relMask,3)``)
+    and the depth-summed flow.
+
+    axes: names among "z", "y", "x" (the axis projected away); None: ("z",) in 3D, ("y", "x") in
+    2D, where "z" is an error.  maps: names among PROJECT_MAPS; None: n_mask, n_valid, sum_vx,
+    sum_vy, sum_vz (3D), sum_magnitude, max_magnitude and, with image, max_image and sum_image.
+    rois: as FieldSpec.rois.  image: an image volume is projected too (projection_maps' image=;
+    in a stream the window's centre frame)."""
+    axes: tuple | None = None
+    maps: tuple | None = None
+    rois: tuple | None = None
+    image: bool = False
+
+    @staticmethod
+    def _names(given, allowed, what):
+        if isinstance(given, str):
+            raise ValueError(f"project: {what} {given!r} is not a sequence of names among {allowed}")
+        try:
+            names = tuple(given)
+        except TypeError:
+            raise ValueError(f"project: {what} {given!r} is not a sequence of names among {allowed}") from None
+        if not names:
+            raise ValueError(f"project: no name in {what}")
+        for n in names:
+            if n not in allowed:
+                raise ValueError(f"project: unknown name {n!r} in {what} (one of {allowed})")
+        if len(set(names)) != len(names):
+            raise ValueError(f"project: duplicate name in {what} {names}")
+        return tuple(n for n in allowed if n in names)  # in bit order
+
+    def resolve(self, ndim, n_roi):
+        """Validated (rois, axes, axis bits, maps, map bits) for an ndim-D volume whose summary
+        has n_roi boxes (the whole volume included), the names in bit order; ValueError on a bad
+        value."""
+        rois = FieldSpec._roi_indices(self.rois, n_roi, "project")
+        if self.axes is None:
+            axes = ("z",) if ndim == 3 else ("y", "x")
+        else:
+            axes = self._names(self.axes, PROJECT_AXES, "axes")
+            if ndim == 2 and "z" in axes:
+                raise ValueError("project: a 2D volume has no z axis to project along")
+        image = bool(self.image)
+        if self.maps is None:
+            maps = tuple(n for n in PROJECT_MAPS[:7] if ndim == 3 or n != "sum_vz") + (PROJECT_IMAGE_MAPS if image
+                                                                                     else ())
+        else:
+            maps = self._names(self.maps, PROJECT_MAPS, "maps")
+            if ndim == 2 and "sum_vz" in maps:
+                raise ValueError("project: a 2D volume has no sum_vz")
+            if not image and any(n in PROJECT_IMAGE_MAPS for n in maps):
+                raise ValueError("project: max_image and sum_image need image=True")
+        return (rois, axes, sum(1 << PROJECT_AXES.index(a) for a in axes), maps,
+                sum(1 << PROJECT_MAPS.index(n) for n in maps))
+
+
+class _ProjectCall(_BoxCall):
+    """of3d_flow_project bound to the summary's boxes, of which spec.rois are projected (the
+    others are listed and skipped, so every box keeps its bit of the keep volume): the size, the
+    launch and the decoding.  The image changes per frame: bind_image names it before enqueue."""
+
+    def __init__(self, boxes, dims, rel_f64, spec, ndim, scales):
+        super().__init__(boxes, dims, rel_f64, scales)
+        self.ndim = int(ndim)
+        self.rois, self.axes, self.axis_bits, self.names, _ = spec.resolve(self.ndim, len(self.boxes))
+        self.needs_image = any(n in PROJECT_IMAGE_MAPS for n in self.names)
+        self.maps, self.result_bytes = self.size(self.boxes, spec, self.ndim)
+        self.image_ptr, self.image_code = None, 0
+
+    @staticmethod
+    def size(boxes, spec, ndim):
+        """(of3d_flow_project's `maps` word, its result bytes) for spec (a ProjectionSpec) over
+        boxes: known from the boxes and the spec alone — FlowStream sizes its buffers with it
+        before any call exists.  The image's dtype does not change the layout."""
+        boxes = np.ascontiguousarray(boxes, dtype=np.int64)
+        rois, _, axis_bits, names, bits = spec.resolve(int(ndim), len(boxes))
+        m = bits | sum(1 << (_PROJECT_SKIP + r) for r in range(len(boxes)) if r not in rois)
+        m = m - (1 << 32) if m >> 31 else m  # as a C int
+        image = _lib.OF3D_F64 if any(n in PROJECT_IMAGE_MAPS for n in names) else 0
+        nbytes = _lib.load().of3d_flow_project_result_bytes(boxes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                            len(boxes), axis_bits, m, int(ndim == 3), image)
+        if nbytes == 0:
+            raise ValueError("of3d: " + _lib.last_error())
+        return m, nbytes
+
+    def bind_image(self, ptr, code):
+        """The image volume of the next enqueue: its device pointer and of3d_dtype code."""
+        self.image_ptr, self.image_code = ptr, int(code)
+
+    def enqueue(self, fields, thresh_ptr, keep_ptr, result_ptr, stream):
+        """The line kernels and the header on `stream` (device pointers)."""
+        vx, vy, vz, rel, v_f32 = fields
+        if self.needs_image and not self.image_ptr:
+            raise ValueError("project: the image maps need an image (bind_image)")
+        _lib.check(self.lib.of3d_flow_project(vx, vy, vz or None, rel, int(v_f32), self.rel_f64, *self.dims,
+                                              thresh_ptr, *self.scales, self.roi_arr, len(self.boxes),
+                                              self.axis_bits, self.maps, self.image_ptr if self.needs_image else None,
+                                              self.image_code if self.needs_image else 0, keep_ptr or None,
+                                              result_ptr, stream or None))
+
+    def decode(self, words):
+        """The result words (host int64 array) as projection_maps' `maps`: per projected ROI a
+        dict roi, box and per axis a dict of map arrays with the plane's shape — views of
+        `words`, no copy —, the means formed here on the host."""
+        words = np.ascontiguousarray(words, dtype=np.int64)
+        n_roi = len(self.boxes)
+        assert (words[1] == n_roi and words[2] == self.axis_bits and words[3] == self.maps & 0xFFFFFFFF
+                and words[4] == (self.ndim == 3) and words[6] * 8 == self.result_bytes), words[:8]
+        out = []
+        for r in self.rois:
+            box = tuple(int(v) for v in self.boxes[r])
+            ext = tuple(box[2 * a + 1] - box[2 * a] for a in range(3))
+            head = words[_PROJECT_HEAD + _PROJECT_ROI * r:_PROJECT_HEAD + _PROJECT_ROI * (r + 1)]
+            entry = {"roi": r, "box": box}
+            for axis in self.axes:
+                a = PROJECT_AXES.index(axis)
+                shape = tuple(e for i, e in enumerate(ext) if i != a)
+                n, off = int(head[2 * a]), int(head[2 * a + 1])
+                assert n == int(np.prod(shape)) and off > 0, (r, axis, n, off)
+                step, m = (n + 1) & ~1, {}
+                for i, name in enumerate(self.names):
+                    flat = words[off + i * step:off + i * step + n]
+                    flat = flat if name in PROJECT_MAPS[:2] else flat.view(np.float64)
+                    m[name] = flat.reshape(shape if self.ndim == 3 else shape[1:])
+                _projection_means(m, ext[a])
+                entry[axis] = m
+            out.append(entry)
+        return out
+
+
+def _projection_means(m, length):
+    """The host's part of one (ROI, axis): mean_vx, mean_vy, mean_vz, mean_magnitude = sum /
+    n_valid (NaN where 0) and mean_image = sum_image / the line's length, for the sums present."""
+    if "n_valid" in m:
+        nv = m["n_valid"].astype(np.float64)
+        nv[nv == 0] = np.nan
+        for k in ("vx", "vy", "vz", "magnitude"):
+            if "sum_" + k in m:
+                m["mean_" + k] = m["sum_" + k] / nv
+    if "sum_image" in m:
+        m["mean_image"] = m["sum_image"] / float(length)
 
 
 @dataclasses.dataclass
@@ -1303,7 +1461,8 @@ class _SummaryCall(_BoxCall):
 
     addons — what follows into a result block of its own, (name, call, None), in launch order:
     "quiver" (a QuiverSpec: of3d_quiver_sample), "contract" (a ContractSpec: of3d_flow_contract;
-    the quiver keeps the summary's mask whatever the contract's) and "export" (a FieldSpec:
+    the quiver keeps the summary's mask whatever the contract's), "project" (a ProjectionSpec:
+    of3d_flow_project; its image is bound per frame, call.project.bind_image) and "export" (a FieldSpec:
     of3d_field_export, last; v_f32: whether the velocity fields it will be given are float32 —
     its block is sized at construction).  All take the summary's boxes, threshold and opened
     mask; enqueue's `blocks` names a device block for each.  In a FlowStream the export's block
@@ -1313,13 +1472,15 @@ class _SummaryCall(_BoxCall):
     it) — and a part's offset as call.spread_off, ...  The next pass is one more line in
     __init__: part(...) or an entry of `addons`."""
 
-    def __init__(self, spec, shape, rel_dtype, device, quiver=None, contract=None, export=None, v_f32=False):
+    def __init__(self, spec, shape, rel_dtype, device, quiver=None, contract=None, export=None, v_f32=False,
+                 project=None):
         import torch
 
         self.spec, self.shape = spec, tuple(int(v) for v in shape)
         ndim = len(self.shape)
         boxes, nbins, edges = spec.resolve(shape)
-        for request, args in ((quiver, (ndim,)), (contract, (ndim,)), (export, (ndim, len(boxes)))):
+        for request, args in ((quiver, (ndim,)), (contract, (ndim,)), (export, (ndim, len(boxes))),
+                              (project, (ndim, len(boxes)))):
             if request is not None:
                 request.resolve(*args)  # a bad request fails before anything is allocated
         min_size, connectivity = spec.opening(ndim)
@@ -1382,13 +1543,15 @@ class _SummaryCall(_BoxCall):
             self.addons.append(("quiver", _QuiverCall(*bound, quiver, ndim, scales, device), None))
         if contract is not None:
             self.addons.append(("contract", _ContractCall(*bound, contract, ndim, scales, device), None))
+        if project is not None:
+            self.addons.append(("project", _ProjectCall(*bound, project, ndim, scales), None))
         if export is not None:
             self.addons.append(("export", _ExportCall(*bound, v_f32, export, ndim, scales), None))
 
     def __getattr__(self, name):
         """call.<name> of a part or add-on (None without it), call.<name>_off of a part."""
         listed = {n: (call, off) for n, call, off in self.__dict__.get("parts", []) + self.__dict__.get("addons", [])}
-        if name in ("open", "axes", "whist", "spread", "profile", "quiver", "contract", "export"):
+        if name in ("open", "axes", "whist", "spread", "profile", "quiver", "contract", "project", "export"):
             return listed.get(name, (None, None))[0]
         if name.endswith("_off") and name[:-4] in listed:
             return listed[name[:-4]][1]
@@ -1952,6 +2115,101 @@ def export_fields(vx, vy, vz, rel, rel_percentile=90, threshold=None, xyscale=1.
         head = words[:1].cpu().numpy()
         words = words.cpu().numpy() if f.host else words
     return {"threshold": _word_threshold(head, f.rel_f64), "rois": boxes.copy(), "blocks": call.decode(words)}
+
+
+# ---------------------------------------------------------------------------
+# Projection maps (csrc/kt_project.hip): the image every figure script draws its vectors on —
+# max(myo,[],3) (plot_figure3_ROIfigures.m:298,313, plot_figure3_ChannelCompare.m:64,69,
+# plot_figure5.m:915-917), the mask's footprint sum(relMask,3) (plot_figure4_timeTraces.m:103,
+# plot_figure5.m:90, plot_figure5_Movie.m:91) — and the flow reduced along an axis, on the
+# resident fields, so that a series run with save_fields=False can still return a picture.
+# Rendering stays with the caller.
+# ---------------------------------------------------------------------------
+def _image_frame(image, f):
+    """projection_maps' image argument checked against the entered frame f: (tensor on the
+    frame's device, of3d_dtype code).  uint16 / uint32 travel as their signed views, as the
+    frame ring keeps them."""
+    import torch
+
+    dt = _np_dtype(image)
+    if dt not in _lib.DTYPE_CODES:
+        raise TypeError(f"project: image dtype {dt} is not one of {[d.name for d in _lib.DTYPE_CODES]}")
+    if tuple(int(v) for v in image.shape) != f.shape:
+        raise ValueError(f"project: image shape {tuple(image.shape)} != the fields' {f.shape}")
+    if isinstance(image, np.ndarray):
+        a = np.ascontiguousarray(image)
+        signed = {"uint16": np.int16, "uint32": np.int32}.get(dt.name)
+        t = torch.as_tensor(a.view(signed) if signed else a).to(f.dev)
+    else:
+        t = image.to(f.dev).contiguous()
+    return t, _lib.DTYPE_CODES[dt]
+
+
+def projection_maps(vx, vy, vz, rel, image=None, spec=None, rel_percentile=90, threshold=None, xyscale=1.0,
+                    zscale=1.0, tscale=1.0, rois=None, min_size=0, connectivity=None, percentile_box=None,
+                    percentile_method="linear", device=None):
+    """Projection maps of one frame, per ROI and axis, by of3d_flow_project: one value per line
+    of the ROI along the axis, only the maps leave the device.
+
+    Inputs, scales, rois, min_size and connectivity as flow_summary (numpy arrays or torch
+    tensors, vz None for 2D; ROI 0 is the whole volume); threshold, percentile_box and
+    percentile_method as quiver_sample.  spec: a ProjectionSpec (default ProjectionSpec(): every
+    ROI after 0, along z — 2D: along y and x —, the seven flow maps).  image: a numpy array or
+    tensor of the volume's shape in one of the seven input dtypes, required iff the spec names an
+    image map (ProjectionSpec(image=True)).
+    Returns a dict: threshold, rois (n_roi, 6), axes (the names) and maps, a list with one dict
+    per projected ROI: roi (its index), box (6 ints) and per axis a dict of arrays of the plane's
+    shape — axis z (dy, dx), y (dz, dx), x (dz, dy); 2D: 1-D profiles —: n_mask and n_valid
+    (int64), sum_vx, sum_vy, sum_vz, sum_magnitude, max_magnitude, max_image, sum_image
+    (float64) as requested, and formed on the host mean_vx, mean_vy, mean_vz, mean_magnitude
+    (sum / n_valid, NaN where 0) and mean_image (sum_image / the line's length).  A sum is the
+    loop ``s = 0.0; for k ascending along the axis: if valid: s = s + v`` bit for bit.
+    Bit-reproducible: the same inputs give the same bits on every run."""
+    f = _Frame("projection_maps", vx, vy, vz, rel, device)
+    summary = SummarySpec(rois=rois, rel_percentile=rel_percentile, min_size=min_size, connectivity=connectivity)
+    boxes = summary.resolve(f.shape)[0]
+    min_size, connectivity = summary.opening(f.ndim)
+    call = _ProjectCall(boxes, f.dims, f.rel_f64, ProjectionSpec() if spec is None else spec, f.ndim,
+                        (xyscale, zscale, tscale))
+    if call.needs_image != (image is not None):
+        raise ValueError("project: an image is needed by max_image / sum_image (ProjectionSpec(image=True)), "
+                         "and only by them")
+    with f:
+        if image is not None:
+            timg, code = _image_frame(image, f)
+            call.bind_image(timg.data_ptr(), code)
+        words = _one_pass(f, call, boxes, min_size, connectivity,
+                          f.threshold(rel_percentile, threshold, percentile_box, percentile_method)).cpu().numpy()
+    return {"threshold": _word_threshold(words, f.rel_f64), "rois": boxes.copy(), "axes": call.axes,
+            "maps": call.decode(words)}
+
+
+def write_projections(path, result):
+    """One frame's projection maps (projection_maps' dict) as an npz: threshold, rois, axes, the
+    projected ROIs' indices (projected) and per ROI r, axis a and map m the array <m>_<a>_<r>,
+    the host's means included."""
+    arrays = {"threshold": np.asarray(result["threshold"]), "rois": np.asarray(result["rois"], dtype=np.int64),
+              "axes": np.asarray(list(result["axes"])),
+              "projected": np.asarray([e["roi"] for e in result["maps"]], dtype=np.int64)}
+    for e in result["maps"]:
+        for a in result["axes"]:
+            for name, v in e[a].items():
+                arrays[f"{name}_{a}_{e['roi']}"] = np.asarray(v)
+    np.savez(path, **arrays)
+
+
+def read_projections(path):
+    """write_projections' file as projection_maps' dict."""
+    with np.load(path) as f:
+        rois, axes = f["rois"], tuple(str(a) for a in f["axes"])
+        out = {"threshold": f["threshold"][()], "rois": rois, "axes": axes, "maps": []}
+        for r in (int(v) for v in f["projected"]):
+            entry = {"roi": r, "box": tuple(int(v) for v in rois[r])}
+            for a in axes:
+                tail = f"_{a}_{r}"
+                entry[a] = {k[:-len(tail)]: f[k] for k in f.files if k.endswith(tail)}
+            out["maps"].append(entry)
+    return out
 
 
 _SPLIT_COLUMNS = {"vx": 0, "vy": 1, "vz": 2}

@@ -186,7 +186,7 @@ def _dist_context():
 
 def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSig=3, tSig=1, wSig=4,
                  precision="fp64", matlab_output=False, parallel="auto", summary=None, save_fields=True,
-                 quiver=None, contract=None):
+                 quiver=None, contract=None, project=None):
     """Parse a TIFF time lapse, run the flow per output frame, write TIFFs.
 
     Mirrors calc_flow.py:362-625: same checks and messages, the same
@@ -228,7 +228,12 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     reduced on the device and written at the end as ``<imNameSave>_contract.csv`` (one row per
     frame and ROI: analysis.CONTRACT_CSV_COLUMNS) and ``<imNameSave>_contract_hist.npz``
     (analysis.write_contract); without it no file differs, and a quiver in the same call still
-    uses the summary's mask.  Single
+    uses the summary's mask.  project=analysis.ProjectionSpec (needs a summary): every saved
+    frame's projection maps — per ROI and axis the mask's footprint, the valid count, the flow
+    summed along the axis and, with image=True, the maximum and sum of the input frame itself
+    (analysis.projection_maps) — are reduced on the device and written per saved frame as
+    ``<imNameSave>_project_t%04d.npz`` (analysis.write_projections); without it no file differs.
+    Single
     process, device-ring path only: with several ranks, or a window that differs from the
     temporal taps, a summary raises ValueError.
 
@@ -297,7 +302,7 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
     from .analysis import FieldSpec
     from .stream import require_summary
 
-    require_summary(summary, save_fields, quiver, contract, "", "save_fields")
+    require_summary(summary, save_fields, quiver, contract, "", "save_fields", project=project)
     if isinstance(save_fields, FieldSpec) and matlab_output and save_fields.dtype is not None:
         raise ValueError("matlab_output writes float64 files: use FieldSpec(dtype=None)")
     if summary is not None and world > 1:
@@ -378,7 +383,7 @@ def process_flow(imDir, imName, fileType="SequenceT", spatialDimensions=3, xyzSi
         if h1 > h0 and NtChunk == 2 * rt + 1:
             _process_stream(load_frame, (h0, h1), NtChunk, NtSlice, spatialDimensions, xyzSig, tSig, wSig, prefix,
                             names, precision, writer, summary=summary, save_fields=save_fields, quiver=quiver,
-                            contract=contract)
+                            contract=contract, project=project)
         else:  # window and temporal taps disagree (non-integer 6*tSig+1): one upload per window
             for hh in range(h0, h1):
                 loopStart = datetime.now()
@@ -461,7 +466,8 @@ def _drive(fs, load, first, count, NtSlice, nfiles, finish):
 
 
 def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig, wSig, prefix, names,
-                    precision="fp64", write_fn=None, summary=None, save_fields=True, quiver=None, contract=None):
+                    precision="fp64", write_fn=None, summary=None, save_fields=True, quiver=None, contract=None,
+                    project=None):
     """process_flow's loop on a device-resident frame ring (stream.py): one
     frame read + upload per output frame; compute, download and TIFF writing
     of consecutive frames overlap.  Files and stdout lines are the reference's
@@ -474,7 +480,8 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
     <prefix>_fields.csv at the end; no full-size TIFFs.  quiver (a
     QuiverSpec): each frame's quiver vectors are written as <prefix>_quiver_t%04d.npz.  contract (a
     ContractSpec): each frame's contractility is collected and written as <prefix>_contract.csv /
-    _contract_hist.npz at the end."""
+    _contract_hist.npz at the end.  project (a ProjectionSpec): each frame's projection maps are
+    written as <prefix>_project_t%04d.npz."""
     from .stream import FlowStream
 
     h0, h1 = out_range
@@ -484,7 +491,7 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
         _check_args(_Shape((NtChunk,) + first.shape), ndim + 1, tSig, MSG_NDIM_3D if ndim == 3 else MSG_NDIM_2D)
     fs = FlowStream(ndim, first.shape, _native(first.dtype), xyzSig, tSig, wSig, precision=precision,
                     rel_fp64=write_fn is not None and ndim == 3, summary=summary, fields=save_fields, quiver=quiver,
-                    contract=contract)
+                    contract=contract, project=project)
     frames, summaries, contracts = [], [], []
 
     def finish(pool, frame, start, pending):
@@ -501,6 +508,10 @@ def _process_stream(load_frame, out_range, NtChunk, NtSlice, ndim, xyzSig, tSig,
             write_quiver(prefix + '_quiver_t' + str(frame).zfill(4) + '.npz',
                          {"threshold": s["threshold"], "rois": s["rois"], "gap": fs.summary.quiver.gap,
                           "samples": pending.quiver()})
+        if project is not None:
+            from .analysis import write_projections
+
+            write_projections(prefix + '_project_t' + str(frame).zfill(4) + '.npz', pending.projections())
         if fs.field_spec is not None:
             for blk in pending.fields():
                 fields = fs.summary.export.names

@@ -44,7 +44,7 @@ _TORCH_VIEW = {
 }
 
 
-def require_summary(summary, fields, quiver, contract, prefix, fields_name):
+def require_summary(summary, fields, quiver, contract, prefix, fields_name, project=None):
     """The add-ons that ride on a summary refuse to go without one.  FlowStream and process_flow
     share the checks; `prefix` and the name of their fields argument keep each one's messages."""
     from .analysis import FieldSpec
@@ -57,6 +57,8 @@ def require_summary(summary, fields, quiver, contract, prefix, fields_name):
         raise ValueError(f"{prefix}quiver needs a summary")
     if contract is not None and summary is None:
         raise ValueError(f"{prefix}contract needs a summary")
+    if project is not None and summary is None:
+        raise ValueError(f"{prefix}project needs a summary")
 
 
 def output_layout(ndim, precision, rel_fp64):
@@ -128,11 +130,11 @@ class _Buf(namedtuple("_Buf", "name pinned count elems dtypes")):
     nbytes = property(lambda self: self.count * self.elems * sum(d.itemsize for d in self.dtypes))
 
 
-def buffer_table(slab, nwin, in_dtype, layout, depth, L, fields=True, export_bytes=0, dfull=False):
+def buffer_table(slab, nwin, in_dtype, layout, depth, L, fields=True, export_bytes=0, dfull=False, project_bytes=0):
     """Every buffer of a stream with `depth` output sets and L frames of lookahead, as _Buf rows;
     FlowStream allocates from it what _fit_device_memory counted.  fields: full-size pinned
-    sets; export_bytes: one export block (device and pinned) per set; dfull: a row-slab plan
-    without row ranges writes a whole block's outputs here first."""
+    sets; export_bytes / project_bytes: one export / projection block (device and pinned) per
+    set; dfull: a row-slab plan without row ranges writes a whole block's outputs here first."""
     nout, v_t, rel_t = layout
     outs = (v_t,) * (nout - 1) + (rel_t,)
     nv, nb = max(slab.nvox, 1), max(slab.nblock, 1)
@@ -148,6 +150,9 @@ def buffer_table(slab, nwin, in_dtype, layout, depth, L, fields=True, export_byt
     if export_bytes:
         rows += [_Buf(name, pin, depth, export_bytes // 8, (np.dtype(np.int64),))
                  for name, pin in (("export", False), ("hexport", True))]
+    if project_bytes:
+        rows += [_Buf(name, pin, depth, project_bytes // 8, (np.dtype(np.int64),))
+                 for name, pin in (("project", False), ("hproject", True))]
     if dfull:
         rows.append(_Buf("dfull", False, 1, nb, outs))
     return rows
@@ -200,12 +205,13 @@ class FlowStream:
     summary=SummarySpec: the frame is also reduced on the device (.summary() gives
     analysis.flow_summary's dict); fields=False: only that, no field downloads;
     fields=FieldSpec: the fields cropped to ROIs, masked and scaled on the device (.fields());
-    quiver=QuiverSpec, contract=ContractSpec: .quiver(), .contract().  Whole-volume streams
-    only; each add-on is described in DESIGN.md §8a–§8o, the driver itself in §8p."""
+    quiver=QuiverSpec, contract=ContractSpec, project=ProjectionSpec: .quiver(), .contract(),
+    .projections() (the image projected is the window's centre frame).  Whole-volume streams
+    only; each add-on is described in DESIGN.md §8a–§8o and §8q, the driver itself in §8p."""
 
     def __init__(self, ndim, vol_shape, dtype, xyzSig, tSig, wSig, device=None, depth=3, d2h="dma",
                  d2h_blocks=64, precision="fp64", rel_fp64=False, zslab=None, lookahead=None, k0_batch=None,
-                 summary=None, fields=True, quiver=None, contract=None):
+                 summary=None, fields=True, quiver=None, contract=None, project=None):
         import torch
 
         from .analysis import FieldSpec
@@ -216,7 +222,7 @@ class FlowStream:
         self.field_spec = fields if isinstance(fields, FieldSpec) else None
         if summary is not None and zslab is not None:
             raise ValueError("FlowStream: summaries of slab streams are not supported (whole volumes only)")
-        require_summary(summary, fields, quiver, contract, "FlowStream: ", "fields")
+        require_summary(summary, fields, quiver, contract, "FlowStream: ", "fields", project=project)
         self.fields = bool(fields) and self.field_spec is None  # full-size downloads
         self.device = _lib.device_index() if device is None else device
         self.dev = torch.device("cuda", self.device)
@@ -269,8 +275,13 @@ class FlowStream:
             from .analysis import _ExportCall
 
             export_bytes = _ExportCall.size(summary.resolve(self.shape)[0], rel_f64, v_f32, self.field_spec, ndim)[1]
+        project_bytes = 0
+        if project is not None:
+            from .analysis import _ProjectCall
+
+            project_bytes = _ProjectCall.size(summary.resolve(self.shape)[0], project, ndim)[1]
         table = partial(buffer_table, slab, self.nwin, dt, layout, fields=self.fields, export_bytes=export_bytes,
-                        dfull=slab.rows is not None and not self.rows_direct)
+                        dfull=slab.rows is not None and not self.rows_direct, project_bytes=project_bytes)
         free = torch.cuda.mem_get_info(self.dev)[0] - (1 << 30)  # a margin for the runtime and the summary
         self.depth, self.batch, self.L = _fit_device_memory(table, depth, self.batch, self.L, free, self.device)
         # allocate
@@ -314,17 +325,22 @@ class FlowStream:
             from .analysis import _SummaryCall
 
             self.summary = _SummaryCall(summary, self.shape, getattr(torch, layout[2].name), self.dev, quiver=quiver,
-                                        contract=contract, export=self.field_spec, v_f32=v_f32)
+                                        contract=contract, export=self.field_spec, v_f32=v_f32, project=project)
             self.dsum = [self.summary.new_result(self.dev) for _ in range(self.depth)]
             self.hsum = [torch.empty(self.summary.result_bytes // 8, dtype=torch.int64, pin_memory=True)
                          for _ in range(self.depth)]
             # the add-ons' own blocks per buffer set, name -> (device, pinned): copied behind the
             # summary's words on the compute stream — but for "export", whose block (the table's)
-            # travels on the fields' download path in their place (submit)
+            # travels on the fields' download path in their place (submit); the projection's
+            # blocks are the table's too (counted against the device's memory), copied like the others
             self.addon = {name: [(call.new_result(self.dev),
                                   torch.empty(call.result_bytes // 8, dtype=torch.int64, pin_memory=True))
                                  for _ in range(self.depth)]
-                          for name, call, _ in self.summary.addons if name != "export"}
+                          for name, call, _ in self.summary.addons if name not in ("export", "project")}
+            if project is not None:
+                assert self.summary.project.result_bytes == project_bytes
+                self.addon["project"] = [(d[0], h[0]) for d, h in zip(bufs["project"], bufs["hproject"])]
+                assert all(d.data_ptr() % 16 == 0 for d, _ in self.addon["project"])  # as of3d_flow_project asks
             if self.field_spec is not None:
                 assert self.summary.export.result_bytes == export_bytes
                 self.addon["export"] = [(d[0], h[0]) for d, h in zip(bufs["export"], bufs["hexport"])]
@@ -448,6 +464,8 @@ class FlowStream:
             # on the compute stream: behind this frame's kernels and ahead of every later frame's,
             # so a later submit() that reuses this set's device outputs (after its release()) is
             # ordered behind these reads by the stream itself
+            if "project" in self.addon:  # the image under the maps: the window's centre frame
+                self.summary.project.bind_image(self.ring[self.order[self.rt]].data_ptr(), self.code)
             self.summary.enqueue((dout[0].data_ptr(), dout[1].data_ptr(), vz, dout[-1].data_ptr(), self.v_f32),
                                  self.dsum[b].data_ptr(), self.comp.cuda_stream,
                                  blocks={name: sets[b][0].data_ptr() for name, sets in self.addon.items()})
@@ -541,6 +559,16 @@ class Pending:
     def quiver(self):
         """analysis.quiver_sample's per-ROI list of this frame (streams created with quiver=)."""
         return self._addon("quiver")
+
+    def projections(self):
+        """analysis.projection_maps' dict of this frame (streams created with project=); the
+        image under max_image / sum_image is the window's centre frame."""
+        from .analysis import _word_threshold
+
+        maps = self._addon("project")
+        call = self.fs.summary.project
+        return {"threshold": _word_threshold(self.fs.hsum[self.b].numpy(), call.rel_f64), "rois": call.boxes.copy(),
+                "axes": call.axes, "maps": maps}
 
     def contract(self):
         """analysis.contractility's dict of this frame (streams created with contract=)."""
